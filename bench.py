@@ -2,7 +2,20 @@
 """Throughput benchmark of the MI355X pseudo-alignment engine.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c2|c3|c3raw|c2mix|c2rc|c5|c1]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...            (one rank per GPU)
+
+A plain run does what the headline figure needs and no more: genomes, the
+serving index, the device-made reads, W warmup steps, K timed steps, the
+result line (value, ms_per_step, the kernels' HIP-event times of the timed
+steps).  --dump-outputs DIR then writes the counters of the last timed step
+(stats, unique, ambiguous, first_key: what a caller fetches) as
+DIR/<name>.npy, float64; the genomes and reads are seeded, so two runs with
+the same arguments align the same inputs.  Everything else described below --
+the job as the product runs it (job index, neighbour-bit break-even), the
+counter pass behind traffic / measured_frac, cpu_baseline with its parity
+sample, and the end-to-end CLI figure -- runs only with --full (where
+--no-cpu-baseline, --no-traffic and --no-e2e trim it).
 
 With --gpus N > 1 and no torchrun environment (WORLD_SIZE unset), this
 process starts the N rank processes itself (RANK / LOCAL_RANK / WORLD_SIZE and
@@ -520,6 +533,23 @@ def counters_digest(result) -> dict:
     return {"stats": [int(x) for x in stats], "sha256": h.hexdigest()}
 
 
+def dump_outputs(directory: str, result) -> dict:
+    """--dump-outputs: the counters a caller of the timed step receives
+    (pa_result_fetch after the last step; at N > 1 the reduced ones), one
+    float64 .npy per array: stats (6), unique / ambiguous / first_key (one
+    entry per genome).  The counts and the first keys (read << 20 | list
+    position, or 2^63 - 1 for a genome never mapped to) are far below 2^53
+    apart from that sentinel, so float64 holds them exactly.  Returns
+    {name: shape}."""
+    os.makedirs(directory, exist_ok=True)
+    shapes = {}
+    for name, a in zip(("stats", "unique", "ambiguous", "first_key"), result.fetch()):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(directory, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks (GPUs); default WORLD_SIZE, else 1")
@@ -533,6 +563,13 @@ def main():
     ap.add_argument("--job-table", choices=("auto", "full"), default="auto",
                     help="the job index's k-mer table: compact below the break-even (auto, as the CLI) or the "
                          "serving index's (full: the line's neighbour-bit break-even is then measurable)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the job as the product runs it (job "
+                         "index, break-even), the CPU baseline and parity sample, the counter pass (traffic, SQ "
+                         "shares) and the end-to-end CLI figure; the --no-* options below trim a --full run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the counters of the last step (what pa_result_fetch hands a "
+                         "caller: stats, unique, ambiguous, first_key) to DIR/<name>.npy as float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-traffic", action="store_true", help="skip the in-run counter pass (traffic, SQ shares)")
@@ -551,6 +588,8 @@ def main():
     ap.add_argument("--plan", action="store_true",
                     help="print the job plan (every rank's reads, reduction, backend) and exit; no device call")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_traffic = args.no_e2e = True
     if args.plan:
         import torch
         # (device_count does not initialise the GPU on this image)
@@ -734,10 +773,11 @@ def main():
     # 1) the job as the product runs it: the index built for this rank's npg
     #    reads (the neighbour bits only past their break-even), then one pass of
     #    them (timed over a few passes: fewer than would bring the reads aligned
-    #    past the break-even, where the align would make the bits itself)
+    #    past the break-even, where the align would make the bits itself);
+    #    --full only
     product = None
     job_tm = None
-    if not args.traffic_child:
+    if args.full and not args.traffic_child:
         jix, _, job_tm = build_index(npg)
         job_bytes = int(jix.info().device_bytes)
         jreads, _ = make_reads(jix)
@@ -820,6 +860,9 @@ def main():
     else:
         ranks_kern = [mine]
     job_counters = counters_digest(result)
+    if args.dump_outputs and rank == 0:
+        log(f"[rank 0] outputs of the last step written to {args.dump_outputs}: "
+            f"{dump_outputs(args.dump_outputs, result)}")
 
     total_reads = world * npg * args.steps
     value = total_reads / elapsed
@@ -874,8 +917,8 @@ def main():
                    "filters_note": (f"{'/'.join(elided)} elided (q_min = {q_min}: a threshold at or below the batch's "
                                     "smallest quality byte filters nothing, strict <, quirk 5; measured when the reads "
                                     "are made, outside the timed step)") if elided else None,
-                   "index": ("serving: the full align-side view, neighbour bits included (built anew after the "
-                             "job-index passes, pa_index_prepare)"),
+                   "index": ("serving: the full align-side view, neighbour bits included (pa_index_prepare"
+                             + ("; built anew after the job-index passes)" if product is not None else ")")),
                    "parallelism": f"read-sharded x{world}, index replicated",
                    "reduce": args.reduce if world > 1 else None, "backend": backend, "rccl_ranks": rccl_ranks,
                    "read_mix": {"reverse_complement": cfg.get("rc_rate", 0.0), "foreign": cfg.get("foreign_rate", 0.0),
@@ -953,7 +996,7 @@ def main():
         N.mem_trim(local)
         per, tnote = counter_pass(args, cfg, kept_path, args.profile_dir)
     else:
-        tnote = "not measured (--no-traffic, or a rank of a multi-GPU run)"
+        tnote = "not measured (a run without --full, --no-traffic, or a rank of a multi-GPU run)"
     rl = out["roofline"]
     rl["traffic_basis"] = tnote
     dom_rank_ms = [r["kernels_ms"].get(dominant) for r in ranks_kern]

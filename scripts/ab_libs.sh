@@ -11,7 +11,7 @@ for c in $CONFIGS; do
   for rep in 1 2; do
     for l in $LIBS; do
       lib=$P/libpa_$l.so; [ "$l" = base ] && lib=$P/libpa.so
-      PA_LIBRARY=$lib timeout -k 10 300 python3 $R/bench.py --config $c --steps 10 --warmup 3 --no-cpu-baseline --no-traffic --no-e2e > $OUT/${c}_${l}_$rep.json 2> $OUT/${c}_${l}_$rep.err || { tail -5 $OUT/${c}_${l}_$rep.err; exit 1; }
+      PA_LIBRARY=$lib timeout -k 10 300 python3 $R/bench.py --full --config $c --steps 10 --warmup 3 --no-cpu-baseline --no-traffic --no-e2e > $OUT/${c}_${l}_$rep.json 2> $OUT/${c}_${l}_$rep.err || { tail -5 $OUT/${c}_${l}_$rep.err; exit 1; }
       python3 -c "
 import json; d=json.load(open('$OUT/${c}_${l}_$rep.json')); print('$c $l $rep', round(d['value']/1e9, 4), 'G reads/s; job index', round(d['job_index']['reads_per_s']/1e9, 4), 'lane ms', round(d['roofline']['kernels']['k_align_lane']['ms_avg'], 3))"
     done

@@ -13,7 +13,7 @@ i=0
 for v in $ENVS; do
   i=$((i+1))
   e=""; [ "$v" != base ] && e=${v//,/ }
-  env PA_CLI_TIMING=1 $e timeout -k 10 ${LIMIT:-400} python bench.py --config $CFG --steps ${STEPS:-10} --warmup 2 $([ "$CPU" = 1 ] || echo --no-cpu-baseline) --no-e2e --no-traffic > $OUT/$i.json 2> $OUT/$i.err || { tail -5 $OUT/$i.err; exit 1; }
+  env PA_CLI_TIMING=1 $e timeout -k 10 ${LIMIT:-400} python bench.py --full --config $CFG --steps ${STEPS:-10} --warmup 2 $([ "$CPU" = 1 ] || echo --no-cpu-baseline) --no-e2e --no-traffic > $OUT/$i.json 2> $OUT/$i.err || { tail -5 $OUT/$i.err; exit 1; }
   python3 -c "
 import json, re
 d=json.load(open('$OUT/$i.json')); r=d['roofline']; ix=d['index']

@@ -10,7 +10,7 @@ cd $R
 l=${LIB:-base}
 lib=$P/libpa_$l.so; [ "$l" = base ] && lib=$P/libpa.so
 for c in $CONFIGS; do
-  PA_LIBRARY=$lib timeout -k 10 ${CFG_LIMIT:-300} python bench.py --config $c --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-e2e $BENCH_ARGS > $OUT/$c.json 2> $OUT/$c.err || { tail -5 $OUT/$c.err; exit 1; }
+  PA_LIBRARY=$lib timeout -k 10 ${CFG_LIMIT:-300} python bench.py --full --config $c --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-e2e $BENCH_ARGS > $OUT/$c.json 2> $OUT/$c.err || { tail -5 $OUT/$c.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$OUT/$c.json')); r=d['roofline']
 print('$c', round(d['value']/1e6,1), 'Mreads/s frac', r.get('frac'), 'kernel', round(r['algorithmic']['kernel_ms'],3), 'ms,', {k: round(v['ms_avg'],3) for k, v in r['kernels'].items()})"

@@ -15,7 +15,7 @@ if [ -n "$LIBS" ]; then
   REPS=${REPS:-1} bash scripts/ab.sh $1 || exit 1
 fi
 if [ -n "$DEFAULT" ]; then
-  timeout -k 10 580 python bench.py --gpus 1 --steps 20 --warmup 5 $DEFAULT_ARGS > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
+  timeout -k 10 580 python bench.py --full --gpus 1 --steps 20 --warmup 5 $DEFAULT_ARGS > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$OUT/bench_default.json')); r=d['roofline']
 print('default', d['config']['workload'][:40], round(d['value']/1e9,3), 'G reads/s frac', r['frac'], 'parity', d.get('parity_sample',{}).get('bit_exact'), 'e2e', (d.get('end_to_end') or {}).get('cli_wall_s'))"

@@ -13,7 +13,7 @@ OUT=$R/gpurun_out/ms_$TAG
 mkdir -p $OUT
 echo "$CFG $*" > $OUT/args
 cd $R
-timeout -k 10 1100 python bench.py --config $CFG --profile-dir $OUT "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 1100 python bench.py --full --config $CFG --profile-dir $OUT "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 echo bench done
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run -- python3 $R/bench.py --config $CFG --no-cpu-baseline --no-traffic --no-e2e "$@" > $OUT/trace.log 2>&1 || { tail -5 $OUT/trace.log; exit 1; }

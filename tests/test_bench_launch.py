@@ -84,6 +84,64 @@ def test_two_ranks_launched_by_bench_equal_one_process():
     index.close()
 
 
+def test_dump_outputs_writes_the_fetched_counters(tmp_path):
+    """--dump-outputs: one float64 .npy per array a caller fetches, values kept
+    exactly (the never-mapped sentinel 2^63 - 1 rounds to 2^63)."""
+    sys.path.insert(0, REPO)
+    import bench
+
+    class Fetched:
+        def fetch(self):
+            return (np.array([5, 1, 2, 0, 0, 7], dtype=np.uint64), np.array([3, 2, 0], dtype=np.uint64),
+                    np.array([1, 1, 0], dtype=np.uint64),
+                    np.array([(61_000_000 << 20) | 3, 17, 2 ** 63 - 1], dtype=np.uint64))
+
+    out = tmp_path / "dump"
+    shapes = bench.dump_outputs(str(out), Fetched())
+    assert shapes == {"stats": [6], "unique": [3], "ambiguous": [3], "first_key": [3]}
+    assert sorted(os.listdir(out)) == ["ambiguous.npy", "first_key.npy", "stats.npy", "unique.npy"]
+    for name, want in zip(("stats", "unique", "ambiguous", "first_key"), Fetched().fetch()):
+        a = np.load(out / (name + ".npy"))
+        assert a.dtype == np.float64 and a.tolist() == [float(int(x)) for x in want]
+    assert int(np.load(out / "first_key.npy")[0]) == (61_000_000 << 20) | 3
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline figure and none of the extra
+    measurements; --steps is the number of timed steps; the dumped arrays are
+    the counters of the last step (job_counters) and repeat from run to run."""
+    env = dict(os.environ)
+    for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(v, None)
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--config", "c2", "--reads-per-gpu", "200000",
+                            "--genome-len", "200000", "--steps", "3", "--warmup", "1", "--dump-outputs",
+                            str(tmp_path / d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                           timeout=280)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["value"] > 0 and line["unit"] == "reads/s" and line["higher_is_better"] is True
+    assert abs(line["value"] * line["ms_per_step"] / 1e3 - 200000) < 1e-3 * 200000
+    timed = [k["launches"] for k in line["roofline"]["kernels"].values()]  # (HIP events of the timed steps only)
+    assert timed and all(n > 0 and n % 3 == 0 for n in timed)
+    assert line["job"] is None and line["job_index"] is None and line["cpu_baseline"] is None
+    assert "parity_sample" not in line and "end_to_end" not in line and line["roofline"]["traffic"] is None
+    arrays = [np.load(tmp_path / "a" / (n + ".npy")) for n in ("stats", "unique", "ambiguous", "first_key")]
+    assert all(a.dtype == np.float64 for a in arrays)
+    assert [int(x) for x in arrays[0]] == line["job_counters"]["stats"]
+    assert sum(line["job_counters"]["stats"][:4]) == 200000
+    assert [a.shape for a in arrays[1:]] == [(50,)] * 3
+    assert arrays[1].sum() == line["job_counters"]["stats"][0]  # (a uniquely mapped read counts for one genome)
+    for n in ("stats", "unique", "ambiguous", "first_key"):
+        assert np.array_equal(np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy")))
+    assert lines[1]["job_counters"] == line["job_counters"]
+
+
 def test_default_is_the_north_star_job():
     """With no --config, bench.py measures the metric's configuration C4
     (BASELINE.json configs[3]): 500 x 2 Mbp genomes, k = 31, 150 bp reads, and
