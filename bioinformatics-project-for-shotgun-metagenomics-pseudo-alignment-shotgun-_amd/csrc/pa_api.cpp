@@ -121,7 +121,8 @@ pa_status pa_index_build_ex(int32_t device, const char *genomes, const uint64_t 
                             int64_t k, uint32_t flags, void *stream, pa_index **out) {
     PA_CHECK(out != nullptr, PA_EINVAL, "out must not be NULL");
     *out = nullptr;
-    PA_CHECK((flags & ~(PA_BUILD_DEFER_TILES | PA_BUILD_COMPACT)) == 0, PA_EINVAL, "unknown build flag bits");
+    PA_CHECK((flags & ~(PA_BUILD_DEFER_TILES | PA_BUILD_COMPACT | PA_BUILD_BOTH_STRANDS)) == 0, PA_EINVAL,
+             "unknown build flag bits");
     PA_CHECK(genome_off != nullptr, PA_EINVAL, "genome_off must not be NULL");
     PA_CHECK(k <= PA_MAX_K, PA_EUNSUPPORTED, "k-mer length above PA_MAX_K (255) is not supported");
     PA_CHECK(n_genomes <= PA_MAX_GENOMES, PA_EUNSUPPORTED,
@@ -143,6 +144,7 @@ pa_status pa_index_build_ex(int32_t device, const char *genomes, const uint64_t 
     PA_CHECK(idx != nullptr, PA_ENOMEM, "out of host memory");
     idx->device = device;
     idx->compact_table = (flags & PA_BUILD_COMPACT) != 0;
+    idx->both_strands = (flags & PA_BUILD_BOTH_STRANDS) != 0;
     pa_status rc = pa::index_build(idx, genomes, genome_off, n_genomes, k, as_stream(stream),
                                    (flags & PA_BUILD_DEFER_TILES) != 0);
     if (rc != PA_OK) {
@@ -207,6 +209,12 @@ pa_status pa_index_get_info(const pa_index *idx, pa_index_info *out) {
     out->table_bytes = idx->cap * (uint64_t)pa::slot_bytes(idx->nw);
     out->total_windows = idx->total_windows;
     out->device_bytes = idx->device_bytes;
+    return PA_OK;
+}
+
+pa_status pa_index_strands(const pa_index *idx, uint32_t *both) {
+    PA_CHECK(idx && both, PA_EINVAL, "NULL argument");
+    *both = idx->both_strands ? 1u : 0u;
     return PA_OK;
 }
 
@@ -573,6 +581,9 @@ pa_status pa_index_dumpref(const pa_index *idx, const uint8_t *keep, const uint3
              "NULL argument");
     PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
     PA_CHECK(fd >= 0, PA_EINVAL, "bad file descriptor");
+    PA_CHECK(!idx->both_strands, PA_EUNSUPPORTED,
+             "pa_index_dumpref: a both-strand index holds reverse-complement k-mers the forward k-mer database "
+             "does not list; dump from a forward index of the same genomes");
     for (uint32_t d = 0; d < n_desc; d++) PA_CHECK(desc_json[d], PA_EINVAL, "NULL description");
     PA_HIP(hipSetDevice(idx->device));
     return pa::index_dumpref(idx, keep, desc_of, n_desc, desc_json, fd, threads > 0 ? threads : 8, desc_unique,

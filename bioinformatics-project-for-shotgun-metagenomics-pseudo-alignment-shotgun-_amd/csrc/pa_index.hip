@@ -144,6 +144,113 @@ __global__ void k_encode(const uint8_t *__restrict__ ascii, uint8_t *__restrict_
     if (first != ~0ull) atomicMin(bad, first);
 }
 
+// 16 bytes starting at any byte address, from three aligned 8-B loads (the
+// caller guarantees that the aligned words holding them can be read: the ASCII
+// staging buffer is aligned and padded by kExpandPad).
+__device__ __forceinline__ void load16_any(const uint8_t *__restrict__ p, uint64_t &lo, uint64_t &hi) {
+    const uint64_t *a = (const uint64_t *)((uintptr_t)p & ~(uintptr_t)7);
+    const uint32_t sh = (uint32_t)((uintptr_t)p & 7) * 8;
+    const uint64_t w0 = a[0], w1 = a[1], w2 = a[2];
+    lo = sh ? (w0 >> sh) | (w1 << (64 - sh)) : w0;
+    hi = sh ? (w1 >> sh) | (w2 << (64 - sh)) : w1;
+}
+
+// The ASCII -> code pass of a both-strand index (PA_BUILD_BOTH_STRANDS): genome
+// g's forward text ascii[fgoff[g] .. +L) becomes the region codes[egoff[g] ..
+// +2L+1) = forward codes, one N code, the reverse complement's codes (3 - code
+// read back to front, N stays N); an empty genome has an empty region.  One
+// thread makes kExpandRun output bytes, stored as one 16-B word; where they lie
+// in one half of one region their source is one run of text, fetched with
+// load16_any (ascending for the forward half, descending for the reverse), else
+// byte by byte (region ends, the join).  *bad = the first byte outside A C G T N
+// as an offset into the forward text, ~0 if none: every forward byte is encoded
+// once by the forward halves, which alone report it.
+constexpr int kExpandRun = 16;
+constexpr uint64_t kExpandPad = 32;
+__global__ __launch_bounds__(256) void k_encode_strands(const uint8_t *__restrict__ ascii,
+                                                        const uint64_t *__restrict__ fgoff,
+                                                        const uint64_t *__restrict__ egoff, uint32_t G,
+                                                        uint8_t *__restrict__ codes, unsigned long long *bad) {
+    const uint64_t etotal = egoff[G];
+    uint64_t e0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * kExpandRun;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x * kExpandRun;
+    unsigned long long first = ~0ull;
+    for (; e0 < etotal; e0 += stride) {
+        const uint64_t e1 = min(e0 + (uint64_t)kExpandRun, etotal);
+        // region holding e0: the last g with egoff[g] <= e0 that is not empty
+        uint32_t lo = 0, hi = G;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (egoff[mid] <= e0)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        uint32_t g = lo;
+        uint64_t rs = egoff[g], re = egoff[g + 1];
+        while (re <= e0 && g + 1 < G) rs = re, re = egoff[++g + 1];
+        uint64_t fs = fgoff[g], L = fgoff[g + 1] - fs;
+        uint8_t out[kExpandRun];
+        const bool whole = e1 - e0 == kExpandRun && e1 <= re;
+        if (whole && e1 - rs <= L) {  // inside the forward half
+            const uint64_t src = fs + (e0 - rs);
+            uint64_t w[2];
+            load16_any(ascii + src, w[0], w[1]);
+#pragma unroll
+            for (int i = 0; i < kExpandRun; i++) {
+                const uint32_t ch = (uint32_t)(w[i >> 3] >> (8 * (i & 7))) & 0xFFu;
+                const uint32_t c = base_code(ch);
+                out[i] = (uint8_t)c;
+                if (c > 3 && ch != 'N' && first == ~0ull) first = src + i;
+            }
+        } else if (whole && e0 - rs > L) {  // inside the reverse half: output p <- forward 2L - p
+            const uint64_t src = fs + 2 * L - (e1 - 1 - rs);  // the lowest forward byte read
+            uint64_t w[2];
+            load16_any(ascii + src, w[0], w[1]);
+#pragma unroll
+            for (int i = 0; i < kExpandRun; i++) {
+                const int j = kExpandRun - 1 - i;
+                const uint32_t c = base_code((uint32_t)(w[j >> 3] >> (8 * (j & 7))) & 0xFFu);
+                out[i] = (uint8_t)(c > 3 ? 4u : 3u - c);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < kExpandRun; i++) {
+                const uint64_t e = e0 + i;
+                out[i] = 4;
+                if (e >= e1) continue;
+                while (e >= re && g + 1 < G) {
+                    rs = re, re = egoff[++g + 1];
+                    fs = fgoff[g], L = fgoff[g + 1] - fs;
+                }
+                const uint64_t p = e - rs;
+                if (p < L) {
+                    const uint32_t ch = ascii[fs + p];
+                    const uint32_t c = base_code(ch);
+                    out[i] = (uint8_t)c;
+                    if (c > 3 && ch != 'N' && first == ~0ull) first = fs + p;
+                } else if (p > L) {
+                    const uint32_t c = base_code(ascii[fs + 2 * L - p]);
+                    out[i] = (uint8_t)(c > 3 ? 4u : 3u - c);
+                }
+            }
+        }
+        if (e1 - e0 == kExpandRun) {  // (e0 is a multiple of 16: one aligned 16-B store)
+            uint4 v;
+            v.x = out[0] | out[1] << 8 | out[2] << 16 | (uint32_t)out[3] << 24;
+            v.y = out[4] | out[5] << 8 | out[6] << 16 | (uint32_t)out[7] << 24;
+            v.z = out[8] | out[9] << 8 | out[10] << 16 | (uint32_t)out[11] << 24;
+            v.w = out[12] | out[13] << 8 | out[14] << 16 | (uint32_t)out[15] << 24;
+            *(uint4 *)(codes + e0) = v;
+        } else {
+#pragma unroll
+            for (int i = 0; i < kExpandRun; i++)
+                if (e0 + i < e1) codes[e0 + i] = out[i];
+        }
+    }
+    if (first != ~0ull) atomicMin(bad, first);
+}
+
 __global__ void k_fill_u64(uint64_t *p, uint64_t n, uint64_t v) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -1547,7 +1654,8 @@ __device__ __forceinline__ uint64_t rng(uint64_t seed, uint64_t a, uint64_t b) {
 __global__ void k_synth_reads(const uint8_t *__restrict__ codes, const uint64_t *__restrict__ goff,
                               const uint32_t *__restrict__ eligible, uint32_t n_eligible, uint64_t n_reads,
                               uint32_t len, uint64_t first, uint64_t seed, uint32_t sub_thresh, uint32_t rc_thresh,
-                              uint32_t foreign_thresh, uint8_t *seq, uint8_t *qual, uint64_t *off) {
+                              uint32_t foreign_thresh, uint8_t *seq, uint8_t *qual, uint64_t *off,
+                              const uint64_t *__restrict__ fwd_len) {  // both-strand index: the forward halves' lengths
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t total = n_reads * len;
@@ -1558,7 +1666,7 @@ __global__ void k_synth_reads(const uint8_t *__restrict__ codes, const uint64_t 
         uint64_t gr = first + r;
         uint64_t h0 = rng(seed, gr, 0xFFFFFFFFull);
         uint32_t g = eligible[(uint32_t)((h0 >> 32) * n_eligible >> 32)];
-        uint64_t glen = goff[g + 1] - goff[g];
+        uint64_t glen = fwd_len ? fwd_len[g] : goff[g + 1] - goff[g];
         uint64_t start = __umul64hi(rng(seed, gr, 0xFFFFFFFEull), glen - len + 1);
         uint32_t kind = 0;  // 0 forward, 1 reverse complement, 2 foreign
         if (rc_thresh | foreign_thresh) {
@@ -2251,6 +2359,8 @@ void index_release(pa_index *idx) {
     pa::dev_free(idx->class_mask);
     pa::dev_free(idx->codes);
     pa::dev_free(idx->goff);
+    pa::dev_free(idx->fwd_len);
+    idx->fwd_len = nullptr;
     pa::dev_free(idx->tile_cls);
     pa::dev_free(idx->tile_pk);
     pa::dev_free(idx->tile_lw);
@@ -2379,11 +2489,37 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
     idx->k = k;
     idx->nw = k > 0 ? key_words(k) : 1;
     idx->n_genomes = n;
+    // Both strands: the index is the forward index of the regions T(g) = g + N +
+    // reverse complement(g) -- everything below (sizing included) sees those
+    // regions as its genomes; the caller's text and offsets are forward only.
+    // (dev_codes, index_reduce: goff already describes the gathered regions.)
+    const bool both = idx->both_strands != 0;
+    const uint64_t text_off = goff[0], fwd_total = goff[n] - goff[0];  // the caller's text
+    std::vector<uint64_t> fwd_goff, region_goff;
+    if (both) {
+        idx->h_fwd_len.resize(n);
+        for (uint32_t g = 0; g < n; g++) {
+            const uint64_t len = goff[g + 1] - goff[g];
+            idx->h_fwd_len[g] = dev_codes ? (len ? (len - 1) / 2 : 0) : len;
+        }
+        if (!dev_codes) {
+            fwd_goff.assign(goff, goff + n + 1);
+            for (auto &o : fwd_goff) o -= goff[0];
+            region_goff.assign(n + 1, 0);
+            for (uint32_t g = 0; g < n; g++) region_goff[g + 1] = region_goff[g] + strand_region(idx->h_fwd_len[g]);
+            goff = region_goff.data();
+        }
+    }
     idx->h_goff.assign(goff, goff + n + 1);
     const uint64_t total = goff[n] - goff[0];
     uint64_t windows = 0;
     for (uint32_t g = 0; g < n; g++) {
         uint64_t len = goff[g + 1] - goff[g];
+        if (both) {  // (the windows across the join hold its N: they are counted on each strand only)
+            len = idx->h_fwd_len[g];
+            if (k > 0 && (uint64_t)k <= len) windows += 2 * (len - (uint64_t)k + 1);
+            continue;
+        }
         if (k > 0 && (uint64_t)k <= len) windows += len - (uint64_t)k + 1;
     }
     for (auto &o : idx->h_goff) o -= goff[0];
@@ -2411,7 +2547,39 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
     PA_HIP(pa::dev_malloc(&idx->counters, 32 * 8));
     PA_HIP(hipMemsetAsync(idx->counters, 0, 32 * 8, st));
     PA_HIP(hipMemcpyAsync(idx->goff, idx->h_goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-    if (total > 0 && !dev_codes) {
+    if (both) {
+        PA_HIP(pa::dev_malloc(&idx->fwd_len, std::max<uint64_t>(n, 1) * 8));
+        PA_HIP(hipMemcpyAsync(idx->fwd_len, idx->h_fwd_len.data(), (uint64_t)n * 8, hipMemcpyHostToDevice, st));
+    }
+    if (total > 0 && !dev_codes && both) {
+        // only the forward text is uploaded; k_encode_strands writes the regions
+        uint8_t *ascii = nullptr;
+        uint64_t *d_fgoff = nullptr;
+        unsigned long long *bad = nullptr, h_bad = ~0ull;
+        PA_HIP(pa::dev_malloc(&ascii, fwd_total + kExpandPad));
+        PA_HIP(pa::dev_malloc(&d_fgoff, (n + 1) * 8));
+        PA_HIP(pa::dev_malloc(&bad, 8));
+        tm.mark("alloc");
+        hipError_t e = hipMemsetAsync(bad, 0xFF, 8, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_fgoff, fwd_goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(ascii, genomes + text_off, fwd_total, hipMemcpyHostToDevice, st);
+        tm.mark("upload");
+        if (e == hipSuccess) {
+            const unsigned grid = grid_for((total + kExpandRun - 1) / kExpandRun);
+            hipLaunchKernelGGL(k_encode_strands, dim3(grid > 65536 ? 65536 : grid), dim3(kBlock), 0, st, ascii, d_fgoff,
+                               idx->goff, n, idx->codes, bad);
+            e = hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, st);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        pa::dev_free(ascii);
+        pa::dev_free(d_fgoff);
+        pa::dev_free(bad);
+        PA_HIP(e);
+        if (h_bad != ~0ull) {
+            set_error("genome text may only contain A, C, G, T and N (byte " + std::to_string(h_bad) + ")");
+            return PA_EINVAL;
+        }
+    } else if (total > 0 && !dev_codes) {
         uint8_t *ascii = nullptr;  // ASCII staging buffer, freed before the table is allocated
         unsigned long long *bad = nullptr, h_bad = ~0ull;
         PA_HIP(pa::dev_malloc(&ascii, total));
@@ -2526,7 +2694,8 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
         }
         if (cap == 0) {
             set_error("index build: the k-mer table of ~" + std::to_string(distinct) +
-                      " distinct k-mers does not fit the free device memory");
+                      " distinct k-mers does not fit the free device memory" +
+                      (both ? " (a both-strand index needs about twice a forward index's memory)" : ""));
             return PA_ENOMEM;
         }
     }
@@ -2536,7 +2705,7 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
     idx->home = pad::HomeCfg{cap};
     PA_HIP(pa::dev_malloc(&idx->table, idx->cap * sb));
     PA_HIP(hipMemsetAsync(idx->table, 0xFF, idx->cap * sb, st));
-    idx->device_bytes = idx->cap * sb + total + (n + 1) * 8;
+    idx->device_bytes = idx->cap * sb + total + (n + 1) * 8 + (both ? (uint64_t)n * 8 : 0);
     tm.mark("table");
     if (k <= 0 || windows == 0) return PA_OK;
     pa_status rc = PA_EUNSUPPORTED;
@@ -2589,6 +2758,7 @@ pa_status index_reduce(pa_index *idx, const uint32_t *sel, uint32_t n, hipStream
     const int device = idx->device;
     const bool profile = idx->profile;  // (set through the C ABI: kept across the rebuild)
     const int compact = idx->compact_table;  // (pa_index_reduce's flags)
+    const int both = idx->both_strands;      // (fixed at the build: whole regions are gathered, so it is kept)
     // pa.h: on failure the index holds nothing and may only be freed -- so a
     // failed copy never leaves half-compacted codes behind a valid-looking index
     auto empty_index = [&]() {
@@ -2597,6 +2767,7 @@ pa_status index_reduce(pa_index *idx, const uint32_t *sel, uint32_t n, hipStream
         idx->device = device;
         idx->profile = profile;
         idx->compact_table = compact;
+        idx->both_strands = both;
     };
     auto fail = [&](hipError_t err, uint8_t *scratch) -> pa_status {
         (void)hipStreamSynchronize(st);  // (the queued copies may still read or write scratch)
@@ -2756,7 +2927,7 @@ pa_status reads_synthesize(const pa_index *idx, pa_reads *r, uint64_t n, uint32_
                            uint64_t seed, double sub_rate, double rc_rate, double foreign_rate, hipStream_t st) {
     std::vector<uint32_t> elig;
     for (uint32_t g = 0; g < idx->n_genomes; g++)
-        if (idx->h_goff[g + 1] - idx->h_goff[g] >= len) elig.push_back(g);
+        if ((idx->both_strands ? idx->h_fwd_len[g] : idx->h_goff[g + 1] - idx->h_goff[g]) >= len) elig.push_back(g);
     if (elig.empty()) {
         set_error("pa_reads_synthesize: no genome is at least read_len long");
         return PA_EINVAL;
@@ -2780,7 +2951,7 @@ pa_status reads_synthesize(const pa_index *idx, pa_reads *r, uint64_t n, uint32_
         };
         hipLaunchKernelGGL(k_synth_reads, dim3(grid_for(r->n_bases) > 65536 ? 65536 : grid_for(r->n_bases)),
                            dim3(kBlock), 0, st, idx->codes, idx->goff, d_elig, (uint32_t)elig.size(), n, len, first,
-                           seed, th(sub_rate), th(rc_rate), th(foreign_rate), r->seq, r->qual, r->off);
+                           seed, th(sub_rate), th(rc_rate), th(foreign_rate), r->seq, r->qual, r->off, idx->fwd_len);
     }
     PA_HIP(hipGetLastError());
     PA_HIP(hipStreamSynchronize(st));

@@ -100,6 +100,12 @@ struct pa_index {
     int released = 0;                  // a failed pa_index_reduce emptied it: it may only be freed
     int force_large = 0;               // PA_LAYOUT=large: the layout of a reference too large for the default one
     int compact_table = 0;             // PA_BUILD_COMPACT: 2 slots per genome window (a job of few reads)
+    // PA_BUILD_BOTH_STRANDS: genome g is held as the region T(g) = g + N + reverse complement(g)
+    // (an empty genome stays empty); codes, goff and h_goff describe those regions, and the
+    // forward lengths below give the caller's genome coordinates (positions, read synthesis)
+    int both_strands = 0;
+    std::vector<uint64_t> h_fwd_len;   // [n_genomes] forward bases of genome g (both_strands only)
+    uint64_t *fwd_len = nullptr;       // device copy (both_strands only, else null)
     // genome tiling (single-word keys, < 2^32 genome bases): the genomes as one
     // concatenated 2-bit string plus the class of the k-mer starting at every
     // position (NONE where no indexed window starts); slots point into it (tpos)
@@ -202,6 +208,8 @@ inline bool nb_repaid(uint64_t reads, uint64_t bases, int nw = 1) {
     const uint64_t per_k = nw >= 3 ? PA_NB_READS_PER_KBASE_3W : nw == 2 ? PA_NB_READS_PER_KBASE_2W : kNbReadsPerKBase;
     return reads >= (bases * per_k + 999) / 1000;
 }
+// bases of the region that holds a genome of `len` bases in a both-strand index
+inline uint64_t strand_region(uint64_t len) { return len ? 2 * len + 1 : 0; }
 // complete: also make neighbour bits left pending, when reads_hint (the reads
 // still to come; ~0: unknown) passes the break-even (pa_index_prepare[_ex]).
 pa_status index_prepare(pa_index *idx, hipStream_t st, uint64_t reads_hint = ~0ull, bool complete = false);

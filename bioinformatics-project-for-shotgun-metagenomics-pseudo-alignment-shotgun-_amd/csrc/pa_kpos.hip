@@ -62,7 +62,8 @@ inline uint64_t host_fmix64(uint64_t x) {
 template <int NW>
 __global__ void k_kmer_scan(const uint8_t *__restrict__ codes, const uint64_t *__restrict__ goff, uint32_t G,
                             int k, uint64_t mask0, const QEnt<NW> *__restrict__ qt, uint64_t qmask,
-                            unsigned long long *__restrict__ n_hits, DevHit *__restrict__ hits, uint64_t cap) {
+                            unsigned long long *__restrict__ n_hits, DevHit *__restrict__ hits, uint64_t cap,
+                            const uint64_t *__restrict__ fwd_len) {  // both-strand index: scan forward halves only
     const uint64_t total = goff[G];
     const uint64_t t0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * kScanRun;
     if (t0 >= total) return;
@@ -97,6 +98,9 @@ __global__ void k_kmer_scan(const uint8_t *__restrict__ codes, const uint64_t *_
         key_push(key, c & 3, mask0);
         while (t >= gend && g + 1 < G) gend = goff[++g + 1];
         if (bad >= (int64_t)t || t + k > gend) continue;  // N inside, or across a genome end
+        // (both strands: positions are the caller's genome coordinates -- the reverse halves are the
+        // index's own copy, and a reverse-complement query is answered from the forward text as ever)
+        if (fwd_len && t + k > goff[g] + fwd_len[g]) continue;
         uint64_t e = key_hash(key) & qmask;
         for (;;) {
             const QEnt<NW> q = qt[e];
@@ -184,7 +188,8 @@ pa_status scan_nw(const pa_index *idx, const std::vector<uint64_t> &keys, size_t
         if (hipMemsetAsync(d_n, 0, 8, st) != hipSuccess) rc = PA_EDEVICE;
         if (rc == PA_OK && total >= (uint64_t)k && k > 0)
             hipLaunchKernelGGL(k_kmer_scan<NW>, dim3(grid), dim3(kBlock), 0, st, idx->codes, idx->goff,
-                               idx->n_genomes, k, mask0_host(k, NW), d_qt, qsize - 1, d_n, d_hits, cap);
+                               idx->n_genomes, k, mask0_host(k, NW), d_qt, qsize - 1, d_n, d_hits, cap,
+                               idx->fwd_len);
         if (rc == PA_OK && (hipGetLastError() != hipSuccess ||
                             hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
                             hipStreamSynchronize(st) != hipSuccess)) {

@@ -202,10 +202,17 @@ class KmerReference:
 
     def __init__(self, k: int, fasta_record_container: FASTARecordContainer, filter_similar: bool = False,
                  similarity_threshold: float = 0.95, device: Optional[int] = None, *,
-                 compact_table: bool = False) -> None:
+                 compact_table: bool = False, both_strands: bool = False) -> None:
         """compact_table (not in the reference): the k-mer table at 2 slots per
         genome window (PA_BUILD_COMPACT) -- for a job of few reads per genome
-        base, as the CLI's dumpalign / align jobs are (main.create_reference)."""
+        base, as the CLI's dumpalign / align jobs are (main.create_reference).
+        both_strands (not in the reference, whose --reverse-complement flag is
+        parsed and never read): reads align against both strands -- a k-mer's
+        genomes are its own and its reverse complement's (the merge of
+        get_kmer_and_reverse_references), exactly as if every genome g were
+        g + "N" + reverse_complement(g) (PA_BUILD_BOTH_STRANDS; about twice the
+        device memory).  EXTSIM then compares those k-mer sets.  ``kmers``, the
+        position lookups and the dumpref summary stay in forward coordinates."""
         if filter_similar and not (0 <= similarity_threshold <= 1):
             raise ValueError("similarity_threshold must be between 0 and 1")
         if not isinstance(k, int):
@@ -218,6 +225,7 @@ class KmerReference:
         self.kmer_len: int = k
         self._device = N.default_device() if device is None else int(device)
         self._compact = bool(compact_table)
+        self._both_strands = bool(both_strands)
         self._build()
         if filter_similar:
             self._filter_similar_genomes(similarity_threshold)
@@ -230,7 +238,8 @@ class KmerReference:
         packed, self._packed = getattr(self, "_packed", None), None  # (only for the first build)
         self._index = N.Index(None if packed is not None else [g["genome"] for g in self.genomes], self.kmer_len,
                               device=self._device, defer_tiles=True, packed=packed,
-                              compact=getattr(self, "_compact", False))
+                              compact=getattr(self, "_compact", False),
+                              both_strands=getattr(self, "_both_strands", False))
         self._view: Optional[Dict[str, Dict[Record, Set[int]]]] = None
 
     @property
@@ -239,7 +248,9 @@ class KmerReference:
 
     @property
     def n_kmers(self) -> int:
-        """Number of distinct k-mers (== len(self.kmers))."""
+        """Number of distinct k-mers (== len(self.kmers)).  For a both-strand
+        reference it counts the distinct k-mers over both strands, and no longer
+        equals len(self.kmers), which stays the forward k-mer database."""
         return self._index.n_kmers
 
     # -- EXTSIM (src/kmer.py:152-263) --------------------------------------
@@ -277,12 +288,14 @@ class KmerReference:
             self._device = N.default_device()
             if "similarity_info" in state:
                 self.similarity_info = state["similarity_info"]
+            self._both_strands = False  # (the reference looks up forward k-mers only)
             self._build()
             self._ref_kmers = state["kmers"]
             self._view = self._ref_kmers
             return
         self.__dict__.update(state)
         self.__dict__.setdefault("_ref_kmers", None)
+        self.__dict__.setdefault("_both_strands", False)  # (a file from before the property: forward)
         self._build()
         if self._ref_kmers is not None:
             self._view = self._ref_kmers
@@ -370,8 +383,14 @@ class KmerReference:
         if self._ref_kmers is not None:  # a reference-written .kdb: its own dict is the k-mer order
             _write_fd(fd, json.dumps(self._summary_from_view(), indent=4).encode())
             return
-        if self._all_genomes is None:
+        if self._all_genomes is None and not self._both_strands:
             index, genomes, keep, tmp = self._index, self.genomes, None, False
+        elif self._all_genomes is None:
+            # both strands: the dump is of the forward k-mer database, which the
+            # index no longer is (pa_index_dumpref: PA_EUNSUPPORTED) -- dump a
+            # forward index of the same genomes
+            genomes, keep, tmp = self.genomes, None, True
+            index = N.Index([g["genome"] for g in genomes], self.kmer_len, device=self._device, defer_tiles=True)
         else:
             # EXTSIM dropped genomes: the reference deletes their entries from the
             # full dict (src/kmer.py:232-245), so the k-mers keep the full

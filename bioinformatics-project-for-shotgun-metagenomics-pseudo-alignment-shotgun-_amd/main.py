@@ -148,6 +148,8 @@ def parse_arguments(args: Optional[List[str]] = None) -> argparse.Namespace:
     parser.add_argument("-m", "--unique-threshold", help="unique k-mer threshold", type=int)
     parser.add_argument("-p", "--ambiguous-threhold", help="ambiguous k-mer threshold", type=int)
     parser.add_argument("--reverse-complement", action="store_true")  # parsed, unused (as in the reference)
+    # not in the reference: align against both strands (building from -g; with -r the file's property decides)
+    parser.add_argument("--both-strands", action="store_true")
     parser.add_argument("--min-read-quality", type=int, default=None)
     parser.add_argument("--min-kmer-quality", type=int, default=None)
     parser.add_argument("--max-genomes", type=int, default=None)
@@ -184,12 +186,21 @@ def compact_for_job(reads_file: Optional[str], container, shards: int = 1) -> bo
 
 
 def create_reference(fasta_file: str, kmer_size: int, filter_similar: bool = False,
-                     similarity_threshold: float = 0.95, reads_file: Optional[str] = None) -> KmerReference:
+                     similarity_threshold: float = 0.95, reads_file: Optional[str] = None,
+                     both_strands: bool = False) -> KmerReference:
     container = FASTAFile(fasta_file).container
     _stage("fasta parsed")
     return KmerReference(kmer_size, container, filter_similar=filter_similar,
                          similarity_threshold=similarity_threshold,
-                         compact_table=compact_for_job(reads_file, container))
+                         compact_table=compact_for_job(reads_file, container), both_strands=both_strands)
+
+
+def _check_strands(args: argparse.Namespace, ref) -> None:
+    """--both-strands with -r: the stored property decides, and a forward-only
+    file cannot serve the request."""
+    if args.both_strands and not getattr(ref, "_both_strands", False):
+        sys.exit(f"Error: --both-strands was given, but reference file '{args.referencefile}' is forward-only; "
+                 "rebuild it with -t reference --both-strands.")
 
 
 def _prefetch_reads(reads_file: str):
@@ -296,7 +307,8 @@ def _dumpalign_sharded(args: argparse.Namespace, filt) -> Optional[PseudoAlignme
     _stage("fasta parsed")
     refs = pa_shard.build_replicas(args.kmer_size, container, devices, args.filter_similar,
                                    args.similarity_threshold,
-                                   compact_table=compact_for_job(args.reads, container, len(devices)))
+                                   compact_table=compact_for_job(args.reads, container, len(devices)),
+                                   both_strands=args.both_strands)
     _stage(f"{len(refs)} references built")
     pa = pa_shard.align_sharded(refs, args.reads, *filt)
     _stage("reads aligned (sharded)" if pa is not None else "sharded path not taken")
@@ -314,7 +326,7 @@ def _run(args: argparse.Namespace) -> None:
         validate_file_readable(args.genomefile, "Genome FASTA")
         validate_file_writable(args.referencefile, "Reference database output")
         create_reference(args.genomefile, args.kmer_size, args.filter_similar,
-                         args.similarity_threshold).save(args.referencefile)
+                         args.similarity_threshold, both_strands=args.both_strands).save(args.referencefile)
     elif args.task == "dumpref":
         if args.referencefile:
             validate_file_readable(args.referencefile, "Reference database")
@@ -329,10 +341,11 @@ def _run(args: argparse.Namespace) -> None:
         if args.referencefile and args.reads and args.alignfile:
             validate_file_readable(args.referencefile, "Reference database")
             ref = _load_reference(args.referencefile)
+            _check_strands(args, ref)
         else:
             validate_file_readable(args.genomefile, "Genome FASTA")
             ref = create_reference(args.genomefile, args.kmer_size, args.filter_similar, args.similarity_threshold,
-                                   reads_file=args.reads)
+                                   reads_file=args.reads, both_strands=args.both_strands)
             # saved unconditionally, as src/main.py:370 does: without -r that is
             # gzip.open(None), a TypeError the reference does not catch
             # (src/main.py:401), so the command ends with a traceback and exit
@@ -344,6 +357,7 @@ def _run(args: argparse.Namespace) -> None:
             validate_file_readable(args.reads, "FASTQ reads")
             pf = _prefetch_reads(args.reads)
             ref = _load_reference(args.referencefile)
+            _check_strands(args, ref)
             _print_json(create_alignment_from_reference(ref, args.reads, *filt, prefetch=pf).get_summary())
         elif args.genomefile and args.kmer_size and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
@@ -354,7 +368,7 @@ def _run(args: argparse.Namespace) -> None:
                 return
             pf = _prefetch_reads(args.reads)
             ref = create_reference(args.genomefile, args.kmer_size, args.filter_similar, args.similarity_threshold,
-                                   reads_file=args.reads)
+                                   reads_file=args.reads, both_strands=args.both_strands)
             _print_json(create_alignment_from_reference(ref, args.reads, *filt, prefetch=pf).get_summary())
         elif args.alignfile:
             validate_file_readable(args.alignfile, "Alignment output")

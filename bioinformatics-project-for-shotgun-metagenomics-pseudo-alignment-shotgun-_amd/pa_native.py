@@ -28,6 +28,7 @@ HAS_MRQ, HAS_MKQ, HAS_MG = 1, 2, 4
 NO_FIRST_KEY = np.uint64(2 ** 63 - 1)  # PA_NO_FIRST_KEY
 PA_BUILD_DEFER_TILES = 1
 PA_BUILD_COMPACT = 2
+PA_BUILD_BOTH_STRANDS = 4
 PA_COMPACT_READS_PER_BASE = 3  # (include/pa.h: the measured break-even of the compact table)
 PA_POS_REVERSE, PA_POS_RC_BIT = 1, 0x80000000
 PA_READS_UNKNOWN = 2 ** 64 - 1
@@ -37,7 +38,7 @@ PA_NB_READS_PER_KBASE_2W, PA_NB_READS_PER_KBASE_3W = 10000, 18000  # (two- / thr
 # every symbol declared in include/pa.h
 EXPORTS = (
     "pa_last_error", "pa_version", "pa_device_count", "pa_runtime_start",
-    "pa_index_build", "pa_index_build_ex", "pa_index_reduce", "pa_index_prepare", "pa_index_prepare_ex", "pa_index_free", "pa_index_get_info", "pa_index_lookup", "pa_index_class_genomes",
+    "pa_index_build", "pa_index_build_ex", "pa_index_reduce", "pa_index_prepare", "pa_index_prepare_ex", "pa_index_free", "pa_index_get_info", "pa_index_strands", "pa_index_lookup", "pa_index_class_genomes",
     "pa_index_positions",
     "pa_index_extsim_stats", "pa_index_dumpref",
     "pa_reads_upload", "pa_reads_synthesize", "pa_reads_synthesize_mix", "pa_reads_info", "pa_params_effective",
@@ -123,6 +124,7 @@ def lib():
         "pa_index_prepare_ex": (I32, [P, U64, P]),
         "pa_index_free": (None, [P]),
         "pa_index_get_info": (I32, [P, ctypes.POINTER(IndexInfo)]),
+        "pa_index_strands": (I32, [P, ctypes.POINTER(U32)]),
         "pa_index_lookup": (I32, [P, ctypes.c_char_p, U64, U32, P, P, P]),
         "pa_index_class_genomes": (I32, [P, I64, P, U32, ctypes.POINTER(U32), P]),
         "pa_index_positions": (I32, [P, ctypes.c_char_p, U64, U32, U32, P, U64, ctypes.POINTER(U64), P]),
@@ -389,12 +391,16 @@ class Index:
 
     def __init__(self, genomes: Sequence, k: int, device: Optional[int] = None, stream=None,
                  defer_tiles: bool = False, packed: Optional[Tuple[np.ndarray, np.ndarray]] = None,
-                 compact: bool = False):
+                 compact: bool = False, both_strands: bool = False):
         """defer_tiles: build the table and genome sets only (PA_BUILD_DEFER_TILES);
         the align-side view is made by prepare() or the first align.  packed:
         the genomes already concatenated (uint8 bytes, uint64 offsets).
         compact: the table at 2 slots per genome window (PA_BUILD_COMPACT: a
-        job of few reads per genome base; kept by reduce())."""
+        job of few reads per genome base; kept by reduce()).
+        both_strands: a reverse-complement aware index (PA_BUILD_BOTH_STRANDS):
+        every result is that of a forward index of the genomes g + "N" +
+        reverse_complement(g); positions() and Reads.synthesize() stay in the
+        forward genomes' coordinates; about twice the memory; kept by reduce()."""
         t0 = time.perf_counter()
         buf, off = packed if packed is not None else concat(genomes)
         t1 = time.perf_counter()
@@ -405,17 +411,26 @@ class Index:
         _check(lib().pa_index_build_ex(self.device, buf.ctypes.data_as(ctypes.c_char_p) if buf.size else None,
                                        _ptr(off), len(off) - 1, kk,
                                        (PA_BUILD_DEFER_TILES if defer_tiles else 0) |
-                                       (PA_BUILD_COMPACT if compact else 0), _stream(stream), ctypes.byref(h)))
+                                       (PA_BUILD_COMPACT if compact else 0) |
+                                       (PA_BUILD_BOTH_STRANDS if both_strands else 0), _stream(stream),
+                                       ctypes.byref(h)))
         if _TIMING:
             print(f"[pa_index] concat {1e3 * (t1 - t0):.1f} ms, pa_index_build_ex {1e3 * (time.perf_counter() - t1):.1f} "
                   "ms", file=sys.stderr, flush=True)
         self._h = h
         self.n_genomes = len(off) - 1
         self.compact = bool(compact)
+        self.both_strands = bool(both_strands)
 
     @property
     def handle(self):
         return self._h
+
+    def strands(self) -> int:
+        """1 for a both-strand index, else 0, as the library holds it (pa_index_strands)."""
+        both = U32(0)
+        _check(lib().pa_index_strands(self._h, ctypes.byref(both)))
+        return int(both.value)
 
     def reduce(self, keep: Sequence[int], stream=None, defer_tiles: bool = True) -> None:
         """Rebuild this index over the genomes numbered ``keep`` (ascending), in

@@ -133,15 +133,17 @@ def _run_threads(fns) -> list:
 
 
 def build_replicas(k: int, container, devices: Sequence[int], filter_similar: bool = False,
-                   similarity_threshold: float = 0.95, compact_table: bool = False):
+                   similarity_threshold: float = 0.95, compact_table: bool = False, both_strands: bool = False):
     """One KmerReference per device, built concurrently on host threads
     (KmerReference(k, container, ..., device=d) each: the same genomes, the same
-    EXTSIM outcome; compact_table: PA_BUILD_COMPACT, main.compact_for_job)."""
+    EXTSIM outcome; compact_table: PA_BUILD_COMPACT, main.compact_for_job;
+    both_strands: PA_BUILD_BOTH_STRANDS on every replica -- the sharded align
+    then runs on both-strand indexes, nothing else changes)."""
     from kmer import KmerReference
     N.lib()  # (bound once, before the threads)
     return _run_threads([lambda d=d: KmerReference(k, container, filter_similar=filter_similar,
                                                    similarity_threshold=similarity_threshold, device=d,
-                                                   compact_table=compact_table)
+                                                   compact_table=compact_table, both_strands=both_strands)
                          for d in devices])
 
 

@@ -142,6 +142,29 @@ def sample_reads(genomes: Sequence[np.ndarray], n_reads: int, read_len: int, see
     return seq, qual, origin
 
 
+_COMPLEMENT = np.arange(256, dtype=np.uint8)
+_COMPLEMENT[ACGT] = ACGT[::-1]
+
+
+def reverse_complement(seq: np.ndarray) -> np.ndarray:
+    """Reverse complement of an ASCII ``uint8`` array (rows of a 2-D array): A-T,
+    C-G, every other byte (``N``) kept -- ``reverse_complement`` of src/kmer.py:96-103."""
+    return _COMPLEMENT[np.asarray(seq, dtype=np.uint8)][..., ::-1]
+
+
+def both_strands_genome(genome) -> np.ndarray:
+    """``T(g) = g + "N" + reverse_complement(g)`` (an empty genome stays empty): a
+    forward index of these genomes holds, for every k-mer, its own genomes and
+    its reverse complement's -- what a both-strand index (PA_BUILD_BOTH_STRANDS)
+    of the genomes ``g`` computes.  ``genome``: str, bytes or ASCII ``uint8`` array."""
+    if isinstance(genome, str):
+        genome = genome.encode("ascii")
+    g = np.frombuffer(genome, dtype=np.uint8) if isinstance(genome, (bytes, bytearray)) else np.asarray(genome, np.uint8)
+    if g.size == 0:
+        return g.copy()
+    return np.concatenate([g, np.frombuffer(b"N", dtype=np.uint8), reverse_complement(g)])
+
+
 def fasta_text(headers: Sequence[str], genomes: Sequence[np.ndarray], width: int = 0) -> str:
     parts = []
     for h, g in zip(headers, genomes):

@@ -168,6 +168,27 @@ pa_status pa_index_build(int32_t device, const char *genomes, const uint64_t *ge
  * on it.  Kept by pa_index_reduce when given again in its flags. */
 #define PA_BUILD_COMPACT 2u
 #define PA_COMPACT_READS_PER_BASE 3
+/* PA_BUILD_BOTH_STRANDS: a both-strand (reverse-complement aware) index.  The
+ * genome set of a k-mer w becomes S(w) | S(rc(w)), S the forward index's set --
+ * the merge of get_kmer_and_reverse_references (src/kmer.py:331-351), which the
+ * reference's parsed-and-unused --reverse-complement flag (src/main.py:76)
+ * never reached the align path with.  The device holds genome g as the region
+ * T(g) = g + "N" + reverse_complement(g) (N's complement is N, an empty genome
+ * stays empty; windows with an N are not indexed, src/kmer.py:145), made on
+ * the device from the forward text, and every result -- pa_index_lookup,
+ * pa_index_class_genomes, pa_index_extsim_stats, every pa_align* entry, their
+ * counters, first keys and filter counters -- is bit for bit that of a forward
+ * index of the genomes T(g_0) .. T(g_G-1).  In pa_index_info, n_kmers counts the
+ * distinct k-mers over both strands, total_windows is twice the forward value,
+ * and the other fields describe what is held: about twice a forward index's
+ * table, tiles and device_bytes (a genome may hold < 2^31 bases for the tiling).
+ * What speaks in genome coordinates stays forward: pa_index_positions (with or
+ * without PA_POS_REVERSE) and pa_reads_synthesize[_mix] give exactly what a
+ * forward index of the same genomes gives; pa_index_dumpref, the dump of the
+ * forward k-mer database, is PA_EUNSUPPORTED (dump from a forward index).
+ * Strandness is fixed at the build: pa_index_reduce keeps it, and does not
+ * take this bit in its flags (PA_EINVAL). */
+#define PA_BUILD_BOTH_STRANDS 4u
 pa_status pa_index_build_ex(int32_t device, const char *genomes, const uint64_t *genome_off, uint32_t n_genomes,
                             int64_t k, uint32_t flags, void *stream, pa_index **out);
 /* Rebuild an index over some of its own genomes, in place: their 2-bit codes
@@ -200,6 +221,8 @@ pa_status pa_index_prepare(pa_index *idx, void *stream);
 pa_status pa_index_prepare_ex(pa_index *idx, uint64_t expected_reads, void *stream);
 void pa_index_free(pa_index *idx);
 pa_status pa_index_get_info(const pa_index *idx, pa_index_info *out);
+/* *both = 1 for an index built with PA_BUILD_BOTH_STRANDS, else 0. */
+pa_status pa_index_strands(const pa_index *idx, uint32_t *both);
 /* n k-mers of length kmer_len packed back to back; cls_out[i] = class id or -1
  * if absent; size_out[i] = number of genomes containing it (0 if absent). */
 pa_status pa_index_lookup(const pa_index *idx, const char *kmers, uint64_t n, uint32_t kmer_len,
