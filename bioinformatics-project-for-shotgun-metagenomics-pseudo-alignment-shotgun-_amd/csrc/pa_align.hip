@@ -1433,6 +1433,27 @@ pa_status align_detail(pa_index *idx, const pa_reads *r, const DevParams &p, uin
     return rc;
 }
 
+pa_status detail_pass_device(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *d_type, uint32_t *d_qf,
+                             uint32_t *d_hr, uint32_t *d_len, const uint64_t *d_off, uint32_t *d_lists,
+                             hipStream_t st) {
+    if (r->n == 0) return PA_OK;
+    ExactArgs x{};
+    unsigned egrid = 0;
+    PA_TRY(prepare_exact(idx, r, x, egrid));
+    x.a = make_args(idx, r, p, 0);
+    x.use_queue = 0;
+    x.type_out = d_type;
+    x.qf_out = d_qf;
+    x.hr_out = d_hr;
+    x.len_out = d_len;
+    x.detail = d_lists ? 2 : 1;
+    x.list_off = d_off;
+    x.lists = d_lists;
+    launch_exact_nw(idx->nw, x, egrid, st);
+    PA_HIP(hipGetLastError());
+    return PA_OK;
+}
+
 }  // namespace pa
 
 namespace {

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <new>
 #include <string>
@@ -43,6 +44,13 @@ hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// Every build and every reduce gives its index a value no other has had: a
+// pa_coverage holds the one it was made under (pa_coverage_*: PA_EINVAL after).
+uint64_t next_epoch() {
+    static std::atomic<uint64_t> e{0};
+    return ++e;
+}
+
 pa_status to_dev_params(const pa_params *p, uint32_t n_genomes, pa::DevParams *out) {
     PA_CHECK(p != nullptr, PA_EINVAL, "params must not be NULL");
     PA_CHECK(p->m >= 0, PA_EINVAL, "m must be bigger than or equal to 0");
@@ -73,6 +81,7 @@ const char *pa_version(void) { return "libpa 0.2 (gfx950) src=" PA_SOURCE_HASH; 
 namespace {
 struct RuntimeStarter {  // joined at exit, before the HIP runtime's own teardown (it was loaded first)
     std::thread th;
+    bool started = false;
     ~RuntimeStarter() {
         if (th.joinable()) th.join();
     }
@@ -81,7 +90,8 @@ RuntimeStarter g_runtime_starter;
 }  // namespace
 
 pa_status pa_runtime_start(int32_t device) {
-    if (g_runtime_starter.th.joinable()) return PA_OK;
+    if (g_runtime_starter.started) return PA_OK;
+    g_runtime_starter.started = true;
     g_runtime_starter.th = std::thread([device] {
         const auto t0 = std::chrono::steady_clock::now();
         const char *w = std::getenv("PA_RUNTIME_WARM");  // 0: the context only (A/B)
@@ -96,6 +106,11 @@ pa_status pa_runtime_start(int32_t device) {
             fprintf(stderr, "[pa_runtime] HIP runtime started in %.1f ms\n",
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     });
+    return PA_OK;
+}
+
+pa_status pa_runtime_wait(void) {
+    if (g_runtime_starter.th.joinable()) g_runtime_starter.th.join();
     return PA_OK;
 }
 
@@ -152,6 +167,7 @@ pa_status pa_index_build_ex(int32_t device, const char *genomes, const uint64_t 
         delete idx;
         return rc;
     }
+    idx->epoch = next_epoch();
     *out = idx;
     return PA_OK;
 }
@@ -166,8 +182,11 @@ pa_status pa_index_reduce(pa_index *idx, const uint32_t *keep, uint32_t n_keep, 
     PA_CHECK((flags & ~(PA_BUILD_DEFER_TILES | PA_BUILD_COMPACT)) == 0, PA_EINVAL, "unknown build flag bits");
     PA_HIP(hipSetDevice(idx->device));
     idx->compact_table = (flags & PA_BUILD_COMPACT) != 0;
-    PA_TRY(pa::index_reduce(idx, keep, n_keep, as_stream(stream), (flags & PA_BUILD_DEFER_TILES) != 0));
-    return PA_OK;
+    const pa_status rc = pa::index_reduce(idx, keep, n_keep, as_stream(stream), (flags & PA_BUILD_DEFER_TILES) != 0);
+    // (rebuilt or released: the positions view went with the old index, index_release;
+    // a failure that left the index unchanged leaves its view and its pa_coverage objects valid)
+    if (rc == PA_OK || idx->released) idx->epoch = next_epoch();
+    return rc;
 }
 
 pa_status pa_index_prepare(pa_index *idx, void *stream) {
@@ -670,6 +689,89 @@ pa_status pa_align_batch(const pa_index *idx, const uint8_t *seq, const uint8_t 
     pa_result_free(res);
     pa_reads_free(r);
     return rc;
+}
+
+// ---- coverage (csrc/pa_cover.hip) ---------------------------------------------------
+
+pa_status pa_index_prepare_coverage(pa_index *idx, void *stream) {
+    PA_CHECK(idx != nullptr, PA_EINVAL, "NULL argument");
+    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_HIP(hipSetDevice(idx->device));
+    PA_TRY(pa::index_prepare_coverage(idx, as_stream(stream)));
+    PA_HIP(hipStreamSynchronize(as_stream(stream)));
+    return PA_OK;
+}
+
+pa_status pa_coverage_create(const pa_index *idx, pa_coverage **out) {
+    PA_CHECK(idx && out, PA_EINVAL, "NULL argument");
+    *out = nullptr;
+    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_HIP(hipSetDevice(idx->device));
+    return pa::coverage_create(idx, out);
+}
+
+pa_status pa_coverage_reset(pa_coverage *cov, void *stream) {
+    PA_CHECK(cov != nullptr, PA_EINVAL, "NULL argument");
+    PA_HIP(hipSetDevice(cov->device));
+    return pa::coverage_reset(cov, as_stream(stream));
+}
+
+pa_status pa_coverage_add(const pa_index *idx, const pa_reads *reads, const pa_params *params, pa_coverage *acc,
+                          void *stream) {
+    PA_CHECK(idx && reads && acc, PA_EINVAL, "NULL argument");
+    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
+    PA_CHECK(acc->idx == idx && acc->epoch == idx->epoch, PA_EINVAL,
+             "the pa_coverage was made for another index, or for this one before a pa_index_reduce");
+    pa::DevParams dp;
+    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    PA_CHECK(acc->reads_added + reads->n < (1ull << 32), PA_EUNSUPPORTED,
+             "a pa_coverage holds fewer than 2^32 reads (its depths are 32-bit)");
+    PA_HIP(hipSetDevice(idx->device));
+    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    return pa::coverage_place(const_cast<pa_index *>(idx), reads, dp, acc, nullptr, nullptr, nullptr, nullptr, 0,
+                              nullptr, as_stream(stream));
+}
+
+pa_status pa_coverage_summary(const pa_coverage *cov, uint32_t min_coverage, uint64_t *covered_unique,
+                              uint64_t *covered_ambiguous, uint64_t *sum_unique, uint64_t *sum_ambiguous,
+                              void *stream) {
+    PA_CHECK(cov != nullptr, PA_EINVAL, "NULL argument");
+    PA_CHECK(min_coverage >= 1, PA_EINVAL, "min_coverage must be at least 1");
+    PA_HIP(hipSetDevice(cov->device));
+    return pa::coverage_summary(const_cast<pa_coverage *>(cov), min_coverage, covered_unique, covered_ambiguous,
+                                sum_unique, sum_ambiguous, as_stream(stream));
+}
+
+pa_status pa_coverage_depth(const pa_coverage *cov, uint32_t genome, uint64_t first, uint64_t count,
+                            uint32_t *unique_depth, uint32_t *ambiguous_depth, void *stream) {
+    PA_CHECK(cov != nullptr, PA_EINVAL, "NULL argument");
+    PA_CHECK(genome < cov->n_genomes, PA_EINVAL, "genome number out of range");
+    const uint64_t len = cov->h_foff[genome + 1] - cov->h_foff[genome];
+    PA_CHECK(first <= len && count <= len - first, PA_EINVAL, "positions past the end of the genome");
+    PA_HIP(hipSetDevice(cov->device));
+    return pa::coverage_depth(const_cast<pa_coverage *>(cov), genome, first, count, unique_depth, ambiguous_depth,
+                              as_stream(stream));
+}
+
+void pa_coverage_free(pa_coverage *cov) {
+    if (!cov) return;
+    hipSetDevice(cov->device);
+    pa::coverage_free(cov);
+}
+
+pa_status pa_align_placements(const pa_index *idx, const pa_reads *reads, const pa_params *params,
+                              uint8_t *read_type, uint64_t *list_off, uint32_t *lists, int64_t *starts,
+                              uint64_t list_cap, uint64_t *list_total, void *stream) {
+    PA_CHECK(idx && reads && read_type && list_off, PA_EINVAL, "NULL argument");
+    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
+    pa::DevParams dp;
+    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    PA_HIP(hipSetDevice(idx->device));
+    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    return pa::coverage_place(const_cast<pa_index *>(idx), reads, dp, nullptr, read_type, list_off, lists, starts,
+                              list_cap, list_total, as_stream(stream));
 }
 
 pa_status pa_profile_enable(pa_index *idx, int32_t enable) {

@@ -2352,6 +2352,7 @@ void extsim_slots_nw(const pa_index *idx, const uint32_t *d_group, uint32_t n_gr
 namespace pa {
 
 void index_release(pa_index *idx) {
+    index_release_coverage(idx);
     pa::dev_free(idx->table);
     pa::dev_free(idx->class_off);
     pa::dev_free(idx->class_size);

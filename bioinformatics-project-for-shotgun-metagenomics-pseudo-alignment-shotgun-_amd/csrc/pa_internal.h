@@ -138,6 +138,16 @@ struct pa_index {
                                        //   a key (present, or no indexed window at t) -- k_tile_rcp, optional
     uint32_t bloom_lg = 0;
     uint64_t device_bytes = 0;
+    // positions view (pa_cover.hip), optional: made by the first coverage / placement call or by
+    // pa_index_prepare_coverage, released with the index.  cov_first holds, k-mer after k-mer, the
+    // first occurrence (concatenated region position) of the k-mer in each genome of its set, genomes
+    // ascending -- the order of its class record; cov_head[slot] is the k-mer's first entry
+    uint32_t *cov_head = nullptr;      // [cap] (NONE at empty slots)
+    uint32_t *cov_first = nullptr;     // [cov_pairs]
+    uint64_t cov_pairs = 0;            // (k-mer, genome) pairs
+    uint64_t cov_bytes = 0;            // its share of device_bytes
+    int cov_ready = 0;
+    uint64_t epoch = 0;                // a new value at every build and reduce (pa_coverage checks it)
     // align scratch
     pa::Workspace ws;
     uint32_t *queue = nullptr;         // read indices deferred to the exact kernel
@@ -185,6 +195,23 @@ struct pa_idset {  // id hashes of a FASTQ byte range (pa_align_fastq_range)
     std::vector<uint64_t> h;
 };
 
+// Depth accumulator of one index (pa_cover.hip): difference arrays in forward
+// genome coordinates, |g| + 1 entries per genome and category (genome g's at
+// foff[g] + g), the ambiguous category after the unique one.
+struct pa_coverage {
+    int device = 0;
+    const pa_index *idx = nullptr;     // the index it was made for, at
+    uint64_t epoch = 0;                //   this build of it
+    uint32_t n_genomes = 0;
+    std::vector<uint64_t> h_foff;      // [G+1] forward bases before genome g
+    uint64_t *foff = nullptr;          // device copy
+    uint64_t entries = 0;              // per category: forward bases + G
+    uint32_t *diff = nullptr;          // [2 entries]
+    uint32_t *depth = nullptr;         // [2 entries] the scanned accumulator, made on demand
+    int depth_valid = 0;
+    uint64_t reads_added = 0;
+};
+
 struct pa_result {
     int device = 0;
     uint32_t n_genomes = 0;
@@ -228,6 +255,26 @@ pa_status align(pa_index *idx, const pa_reads *r, const DevParams &p, uint64_t b
 pa_status align_detail(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *type, uint32_t *qf,
                        uint32_t *hr, uint64_t *list_off, uint32_t *lists, uint64_t list_cap, uint64_t *list_total,
                        hipStream_t st);
+// The detail pass with everything left on the device (pa_cover.hip): without
+// d_lists the per-read type, filter counts and list length; with d_off (n + 1
+// offsets) and d_lists the lists themselves.
+pa_status detail_pass_device(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *d_type, uint32_t *d_qf,
+                             uint32_t *d_hr, uint32_t *d_len, const uint64_t *d_off, uint32_t *d_lists,
+                             hipStream_t st);
+// coverage (pa_cover.hip)
+pa_status index_prepare_coverage(pa_index *idx, hipStream_t st);
+void index_release_coverage(pa_index *idx);
+pa_status coverage_create(const pa_index *idx, pa_coverage **out);
+pa_status coverage_reset(pa_coverage *cov, hipStream_t st);
+void coverage_free(pa_coverage *cov);
+// classify, place and (acc) accumulate; type / list_off / lists / starts: host outputs, nullable
+pa_status coverage_place(pa_index *idx, const pa_reads *r, const DevParams &p, pa_coverage *acc, uint8_t *type,
+                         uint64_t *list_off, uint32_t *lists, int64_t *starts, uint64_t list_cap,
+                         uint64_t *list_total, hipStream_t st);
+pa_status coverage_summary(pa_coverage *cov, uint32_t min_coverage, uint64_t *cov_u, uint64_t *cov_a, uint64_t *sum_u,
+                           uint64_t *sum_a, hipStream_t st);
+pa_status coverage_depth(pa_coverage *cov, uint32_t genome, uint64_t first, uint64_t count, uint32_t *du,
+                         uint32_t *da, hipStream_t st);
 pa_status reads_measure(pa_reads *r, hipStream_t st);  // q_min / len_min of a batch (at its creation)
 // the filters an align of batch r applies: quality thresholds no read can fail dropped
 pa_status effective_params(const pa_reads *r, const DevParams &p, DevParams &out, hipStream_t st);

@@ -34,6 +34,7 @@ import gzip
 import json
 import os
 import pickle
+import weakref
 import tempfile
 from collections import defaultdict, namedtuple
 from enum import Enum
@@ -602,10 +603,23 @@ def _columnar(container) -> Tuple[List[str], np.ndarray, np.ndarray, np.ndarray]
     return ids, seq, qual, off
 
 
-class PseudoAlignment:
-    """Pseudo-alignment of reads against a KmerReference (src/kmer.py:532-699)."""
+# Depth accumulators of the alignments made with coverage=True.  Device state,
+# kept out of the instances' __dict__: an .aln file holds no coverage, and an
+# alignment loaded from one has none.
+_COVERAGE: "weakref.WeakKeyDictionary[PseudoAlignment, Optional[N.Coverage]]" = weakref.WeakKeyDictionary()
 
-    def __init__(self, kmer_reference: KmerReference) -> None:
+
+class PseudoAlignment:
+    """Pseudo-alignment of reads against a KmerReference (src/kmer.py:532-699).
+
+    ``coverage=True`` (not in the reference, which leaves its EXTCOVERAGE
+    extension out): every batch aligned through the host-parsed path is also
+    placed on the genomes it maps to, and ``get_coverage`` reports the depth
+    and breadth per genome."""
+
+    def __init__(self, kmer_reference: KmerReference, coverage: bool = False) -> None:
+        if coverage:
+            _COVERAGE[self] = None  # (the accumulator is made with the first batch)
         self.kmer_reference: KmerReference = kmer_reference
         self.filtered_quality_reads: int = 0
         self.filtered_quality_kmers: int = 0
@@ -686,7 +700,8 @@ class PseudoAlignment:
         ``prefetch``: the same file already on its way to the device
         (N.FastqPrefetch, started before the index build); consumed here."""
         from data_file import FASTAQFile
-        fresh = not self._batches and not self._host and self._result is None
+        # (a coverage job takes the host-parsed path: the placements need the read columns)
+        fresh = not self._batches and not self._host and self._result is None and self not in _COVERAGE
         err = _check_align_args(self.kmer_reference, m, p, min_read_quality, min_kmer_quality, max_genomes)
         n = None
         if fresh and err is None and os.environ.get("PA_STREAM", "1") != "0":
@@ -760,6 +775,8 @@ class PseudoAlignment:
             reads = N.Reads.upload(seq, qual, off, device=ref.index.device)
             N.align(ref.index, reads, prm, self._next_index, self._result)
             stats, _, _, _ = self._result.fetch()
+            if self in _COVERAGE:
+                self._coverage().add(reads, prm)
             reads.close()
             delta = stats - self._gpu_stats
             self._gpu_stats = stats
@@ -839,6 +856,53 @@ class PseudoAlignment:
         genome_mapping = {name: {"unique_reads": counts[name][0], "ambiguous_reads": counts[name][1]}
                           for name in sorted(first, key=first.get)}
         return {"Statistics": summary, "Summary": genome_mapping}
+
+    def _coverage(self) -> "N.Coverage":
+        cov = _COVERAGE[self]
+        if cov is None:
+            cov = _COVERAGE[self] = N.Coverage(self.kmer_reference.index)
+        return cov
+
+    def get_coverage(self, genomes: Optional[Sequence[str]] = None, min_coverage: int = 1,
+                     full: bool = False) -> Dict[str, Dict[str, Any]]:
+        """``{"Coverage": {identifier: {"covered_bases_unique", "covered_bases_ambiguous",
+        "mean_coverage_unique", "mean_coverage_ambiguous"}}}`` for the genomes
+        named in ``genomes`` (None: all), in FASTA order, genomes no read covers
+        included; covered = positions at least ``min_coverage`` reads deep, mean =
+        summed depth / genome length, rounded to one decimal.  ``full`` adds
+        ``"Details": {identifier: {"unique_cov": [...], "ambiguous_cov": [...]}}``,
+        the depth at every position.  ValueError for an alignment made without
+        ``coverage=True`` (or loaded from a file) and for an unknown identifier."""
+        if self not in _COVERAGE:
+            raise ValueError("this alignment was made without coverage=True")
+        if isinstance(min_coverage, bool) or not isinstance(min_coverage, int) or min_coverage < 1:
+            raise ValueError("min_coverage must be an integer of at least 1")
+        names = [g.identifier for g in self.kmer_reference.genomes]
+        if genomes is not None:
+            known = set(names)
+            unknown = [x for x in genomes if x not in known]
+            if unknown:
+                raise ValueError(f"unknown genome identifier: {unknown[0]}")
+            wanted = set(genomes)
+        cov = self._coverage()
+        cu, ca, su, sa = cov.summary(min_coverage)
+        out: Dict[str, Dict[str, Any]] = {"Coverage": {}}
+        if full:
+            out["Details"] = {}
+        for g, name in enumerate(names):
+            if genomes is not None and name not in wanted:
+                continue
+            n = cov.lengths[g]
+            out["Coverage"][name] = {
+                "covered_bases_unique": int(cu[g]),
+                "covered_bases_ambiguous": int(ca[g]),
+                "mean_coverage_unique": round(int(su[g]) / n, 1) if n else 0.0,
+                "mean_coverage_ambiguous": round(int(sa[g]) / n, 1) if n else 0.0,
+            }
+            if full:
+                du, da = cov.depth(g)
+                out["Details"][name] = {"unique_cov": [int(x) for x in du], "ambiguous_cov": [int(x) for x in da]}
+        return out
 
     def get_reads_by_mapping_type(self, mapping_type: ReadMappingType) -> List[str]:
         return [rid for rid, d in self.reads.items() if d["mapping_type"] == mapping_type]

@@ -4,6 +4,7 @@
     python3 main.py -t dumpalign -g GENOMES.fa -k 31 --reads READS.fq [-m M] [-p P]
                     [--min-read-quality Q] [--min-kmer-quality QK] [--max-genomes MG]
                     [--filter-similar [--similarity-threshold T]]
+                    [--coverage [--genomes a,b,c] [--min-coverage N] [--full-coverage]]
 
 Same tasks (reference | dumpref | align | dumpalign), flags, flag-combination
 checks, default coercions and error exits as src/main.py:61-402:
@@ -39,6 +40,20 @@ _EARLY_PREFETCH = None  # (path, native handle) of a FASTQ prefetch started at e
 _FQ_PLAIN_EXT = ".fq"  # (FASTAQFile.EXTENSIONS without ".fq.gz": the file types the prefetch takes)
 
 
+_COVERAGE_FLAGS = ("--coverage", "--genomes", "--min-coverage", "--full-coverage")
+
+
+def _has_coverage_flag(argv: List[str]) -> bool:
+    """A coverage flag on the command line, in any spelling argparse accepts
+    (`--flag=X`, an unambiguous prefix).  Read off argv before argparse; a
+    prefix shared with another flag counts too, which only costs the early prefetch."""
+    for a in argv:
+        name = a.split("=", 1)[0]
+        if len(name) > 2 and name.startswith("--") and any(f.startswith(name) for f in _COVERAGE_FLAGS):
+            return True
+    return False
+
+
 def _early_reads_path(argv: List[str]) -> Optional[str]:
     """The --reads file of a `-t dumpalign` command line, read off argv before
     argparse and the heavy imports (every spelling argparse accepts: `-t X`,
@@ -66,6 +81,8 @@ def _early_reads_path(argv: List[str]) -> Optional[str]:
         i += 1
     if task != "dumpalign" or not reads or not reads.endswith(_FQ_PLAIN_EXT):
         return None
+    if _has_coverage_flag(argv):  # (a coverage job parses the reads on the host)
+        return None
     if os.environ.get("PA_GPUS", "1") not in ("", "0", "1"):  # (read-sharded over GPUs: no whole-file prefetch)
         return None
     if os.environ.get("PA_STREAM", "1") == "0" or os.environ.get("PA_PREFETCH", "1") == "0":
@@ -86,6 +103,10 @@ if __name__ == "__main__":  # the HIP runtime starts on a native thread while th
         _lib = ctypes.CDLL(os.environ.get("PA_LIBRARY", os.path.join(_here, "libpa.so")))
         _dev = int(os.environ.get("PA_DEVICE", os.environ.get("LOCAL_RANK", "0")))
         _lib.pa_runtime_start(_dev)
+        # (a flag check may end the process at once: no way out leaves before the start is
+        # over, or the runtime's exit handlers would run under the thread still starting it)
+        import atexit
+        atexit.register(_lib.pa_runtime_wait)
         # a plain FASTQ's copy into device memory starts now too (pa_fastq_prefetch_start
         # makes no HIP call on this thread): it overlaps the imports, not only the build
         _r = _early_reads_path(sys.argv[1:])
@@ -155,6 +176,12 @@ def parse_arguments(args: Optional[List[str]] = None) -> argparse.Namespace:
     parser.add_argument("--max-genomes", type=int, default=None)
     parser.add_argument("--filter-similar", action="store_true")
     parser.add_argument("--similarity-threshold", type=float)
+    # EXTCOVERAGE (the course project's extension the reference leaves out): dumpalign with --reads
+    parser.add_argument("--coverage", action="store_true", help="add per-genome read coverage to dumpalign's JSON")
+    parser.add_argument("--genomes", default=None, help="comma-separated genome identifiers to report (default: all)")
+    parser.add_argument("--min-coverage", type=int, default=None,
+                        help="reads a position needs to count as covered (default: 1)")
+    parser.add_argument("--full-coverage", action="store_true", help="also print the depth at every position")
     return parser.parse_args(args)
 
 
@@ -228,7 +255,8 @@ def _prefetch_reads(reads_file: str):
 
 def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: str, m: int, p: int,
                                     min_read_quality, min_kmer_quality, max_genomes,
-                                    prefetch=None, per_read: bool = False) -> PseudoAlignment:
+                                    prefetch=None, per_read: bool = False,
+                                    coverage: bool = False) -> PseudoAlignment:
     # the FASTQ file goes straight to the device (parsed there, aligned in
     # windows); a file outside that subset of the grammar is parsed the exact
     # way (FASTAQFile), which also raises the reference's errors.  per_read
@@ -237,7 +265,9 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
     # would only have to be repeated on the host for them
     FASTAQFile.check_extension(reads_file)
     _stage("reference built")
-    alignment = PseudoAlignment(kmer_reference)
+    # coverage: the reads are parsed on the host and aligned on one device (align_reads_from_file
+    # then takes its exact path: the placements need the read columns)
+    alignment = PseudoAlignment(kmer_reference, coverage=True) if coverage else PseudoAlignment(kmer_reference)
     if per_read:
         alignment.align_reads_from_container(FASTAQFile(reads_file).container, m, p, min_read_quality,
                                              min_kmer_quality, max_genomes)
@@ -268,6 +298,13 @@ def _check_task(args: argparse.Namespace) -> None:
     """Flag combinations (src/main.py:321-334), truthiness-based like the reference."""
     extra = (args.reads or args.alignfile or args.unique_threshold or args.ambiguous_threhold
              or args.min_read_quality or args.min_kmer_quality or args.max_genomes)
+    if not args.coverage and (args.genomes is not None or args.min_coverage is not None or args.full_coverage):
+        sys.exit("Error: --genomes, --min-coverage and --full-coverage need --coverage.")
+    if args.coverage:
+        if args.task != "dumpalign" or not args.reads:
+            sys.exit("Error: --coverage is only allowed for task 'dumpalign' with --reads.")
+        if args.min_coverage is not None and args.min_coverage < 1:
+            sys.exit("Error: --min-coverage must be at least 1.")
     if args.task == "reference":
         if extra:
             sys.exit("Error: For task 'reference', only -g, -k, -r, --filter-similar, and --similarity-threshold "
@@ -319,6 +356,15 @@ def _dumpalign_sharded(args: argparse.Namespace, filt) -> Optional[PseudoAlignme
     return pa
 
 
+def _print_alignment(alignment: PseudoAlignment, args: argparse.Namespace) -> None:
+    """The dumpalign JSON; with --coverage the "Coverage" (and "Details") objects after "Summary"."""
+    out = alignment.get_summary()
+    if args.coverage:
+        genomes = None if args.genomes is None else [x for x in args.genomes.split(",") if x]
+        out.update(alignment.get_coverage(genomes, args.min_coverage or 1, args.full_coverage))
+    _print_json(out)
+
+
 def _run(args: argparse.Namespace) -> None:
     filt = (args.unique_threshold, args.ambiguous_threhold, args.min_read_quality, args.min_kmer_quality,
             args.max_genomes)
@@ -355,21 +401,24 @@ def _run(args: argparse.Namespace) -> None:
     elif args.task == "dumpalign":
         if args.referencefile and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
-            pf = _prefetch_reads(args.reads)
+            pf = None if args.coverage else _prefetch_reads(args.reads)
             ref = _load_reference(args.referencefile)
             _check_strands(args, ref)
-            _print_json(create_alignment_from_reference(ref, args.reads, *filt, prefetch=pf).get_summary())
+            _print_alignment(create_alignment_from_reference(ref, args.reads, *filt, prefetch=pf,
+                                                             coverage=args.coverage), args)
         elif args.genomefile and args.kmer_size and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
             validate_file_readable(args.genomefile, "Genome FASTA")
-            sharded = _dumpalign_sharded(args, filt)
+            # (a coverage job runs on one device: the depth arrays of read shards are not reduced)
+            sharded = None if args.coverage else _dumpalign_sharded(args, filt)
             if sharded is not None:
                 _print_json(sharded.get_summary())
                 return
-            pf = _prefetch_reads(args.reads)
+            pf = None if args.coverage else _prefetch_reads(args.reads)
             ref = create_reference(args.genomefile, args.kmer_size, args.filter_similar, args.similarity_threshold,
                                    reads_file=args.reads, both_strands=args.both_strands)
-            _print_json(create_alignment_from_reference(ref, args.reads, *filt, prefetch=pf).get_summary())
+            _print_alignment(create_alignment_from_reference(ref, args.reads, *filt, prefetch=pf,
+                                                             coverage=args.coverage), args)
         elif args.alignfile:
             validate_file_readable(args.alignfile, "Alignment output")
             try:

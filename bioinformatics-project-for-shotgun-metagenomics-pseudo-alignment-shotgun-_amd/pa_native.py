@@ -37,7 +37,7 @@ PA_NB_READS_PER_KBASE_2W, PA_NB_READS_PER_KBASE_3W = 10000, 18000  # (two- / thr
 
 # every symbol declared in include/pa.h
 EXPORTS = (
-    "pa_last_error", "pa_version", "pa_device_count", "pa_runtime_start",
+    "pa_last_error", "pa_version", "pa_device_count", "pa_runtime_start", "pa_runtime_wait",
     "pa_index_build", "pa_index_build_ex", "pa_index_reduce", "pa_index_prepare", "pa_index_prepare_ex", "pa_index_free", "pa_index_get_info", "pa_index_strands", "pa_index_lookup", "pa_index_class_genomes",
     "pa_index_positions",
     "pa_index_extsim_stats", "pa_index_dumpref",
@@ -49,6 +49,8 @@ EXPORTS = (
     "pa_idsets_disjoint", "pa_idset_free",
     "pa_fastq_prefetch_start", "pa_align_fastq_prefetched", "pa_fastq_prefetch_free",
     "pa_comm_unique_id", "pa_comm_init", "pa_comm_free", "pa_comm_count", "pa_counters_reduce",
+    "pa_index_prepare_coverage", "pa_coverage_create", "pa_coverage_reset", "pa_coverage_add", "pa_coverage_summary",
+    "pa_coverage_depth", "pa_coverage_free", "pa_align_placements",
     "pa_profile_enable", "pa_profile_read", "pa_profile_read_kernels", "pa_mem_trim",
     "pa_parse_text", "pa_parse_file", "pa_seqset_sizes", "pa_seqset_export", "pa_seqset_free", "pa_gz_inflate_file",
 )
@@ -117,6 +119,7 @@ def lib():
         "pa_version": (ctypes.c_char_p, []),
         "pa_device_count": (I32, [ctypes.POINTER(I32)]),
         "pa_runtime_start": (I32, [I32]),
+        "pa_runtime_wait": (I32, []),
         "pa_index_build": (I32, [I32, ctypes.c_char_p, P, U32, I64, P, PP]),
         "pa_index_build_ex": (I32, [I32, ctypes.c_char_p, P, U32, I64, U32, P, PP]),
         "pa_index_reduce": (I32, [P, P, U32, U32, P]),
@@ -164,6 +167,14 @@ def lib():
         "pa_comm_free": (I32, [P]),
         "pa_comm_count": (I32, [P, ctypes.POINTER(I32)]),
         "pa_counters_reduce": (I32, [P, P, P]),
+        "pa_index_prepare_coverage": (I32, [P, P]),
+        "pa_coverage_create": (I32, [P, PP]),
+        "pa_coverage_reset": (I32, [P, P]),
+        "pa_coverage_add": (I32, [P, P, ctypes.POINTER(Params), P, P]),
+        "pa_coverage_summary": (I32, [P, U32, P, P, P, P, P]),
+        "pa_coverage_depth": (I32, [P, U32, U64, U64, P, P, P]),
+        "pa_coverage_free": (None, [P]),
+        "pa_align_placements": (I32, [P, P, ctypes.POINTER(Params), P, P, P, P, U64, ctypes.POINTER(U64), P]),
         "pa_profile_enable": (I32, [P, I32]),
         "pa_profile_read": (I32, [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.POINTER(U64)]),
         "pa_profile_read_kernels": (I32, [P, P, P]),
@@ -419,6 +430,7 @@ class Index:
                   "ms", file=sys.stderr, flush=True)
         self._h = h
         self.n_genomes = len(off) - 1
+        self.genome_lengths = np.diff(np.asarray(off, dtype=np.uint64)).astype(np.int64)  # forward bases
         self.compact = bool(compact)
         self.both_strands = bool(both_strands)
 
@@ -445,6 +457,7 @@ class Index:
             self.close()
         _check(st)
         self.n_genomes = len(sel)
+        self.genome_lengths = self.genome_lengths[sel.astype(np.int64)]
 
     def prepare(self, stream=None, expected_reads: Optional[int] = None) -> None:
         """Make a deferred build's align-side view now (pa_index_prepare), or,
@@ -455,6 +468,12 @@ class Index:
             _check(lib().pa_index_prepare(self._h, _stream(stream)))
         else:
             _check(lib().pa_index_prepare_ex(self._h, max(0, min(int(expected_reads), 2 ** 64 - 1)), _stream(stream)))
+
+    def prepare_coverage(self, stream=None) -> None:
+        """Build the positions view coverage and placements need (the k-mers'
+        first occurrence per genome; pa_index_prepare_coverage) now rather than
+        at the first Coverage.add / align_placements.  A no-op once it exists."""
+        _check(lib().pa_index_prepare_coverage(self._h, _stream(stream)))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -900,3 +919,84 @@ def align_detail(index: Index, reads: Reads, params: Params, stream=None):
                                      _ptr(hr), _ptr(off), _ptr(lists), lists.size, ctypes.byref(total),
                                      _stream(stream)))
     return types[:n], qf[:n], hr[:n], off, lists[:int(total.value)]
+
+
+def align_placements(index: Index, reads: Reads, params: Params, stream=None):
+    """pa_align_placements: (types, list offsets, lists, starts) -- align_detail's
+    mapping types and genomes_mapped_to lists, and for every list entry the
+    read's placement on that genome (int64, region coordinates)."""
+    n = reads.n
+    types = np.zeros(max(n, 1), dtype=np.uint8)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    total = U64(0)
+    _check(lib().pa_align_placements(index.handle, reads.handle, ctypes.byref(params), _ptr(types), _ptr(off), None,
+                                     None, 0, ctypes.byref(total), _stream(stream)))
+    lists = np.zeros(max(int(total.value), 1), dtype=np.uint32)
+    starts = np.zeros(max(int(total.value), 1), dtype=np.int64)
+    if total.value:
+        _check(lib().pa_align_placements(index.handle, reads.handle, ctypes.byref(params), _ptr(types), _ptr(off),
+                                         _ptr(lists), _ptr(starts), lists.size, ctypes.byref(total),
+                                         _stream(stream)))
+    return types[:n], off, lists[:int(total.value)], starts[:int(total.value)]
+
+
+class Coverage:
+    """Per-genome read depth of one index (pa_coverage): ``add`` classifies a
+    batch as align_detail does, places every mapped read on the genomes of its
+    list and accumulates; ``summary`` / ``depth`` read the result in forward
+    genome coordinates.  Valid until the index is reduced or closed."""
+
+    def __init__(self, index: Index):
+        h = P()
+        _check(lib().pa_coverage_create(index.handle, ctypes.byref(h)))
+        self._h = h
+        self._index = index  # (kept alive: the accumulator is checked against it)
+        self.n_genomes = index.n_genomes
+        self.lengths = [int(x) for x in index.genome_lengths]  # forward bases per genome
+
+    @property
+    def handle(self):
+        return self._h
+
+    def add(self, reads: Reads, params: Params, stream=None) -> None:
+        _check(lib().pa_coverage_add(self._index.handle, reads.handle, ctypes.byref(params), self._h,
+                                     _stream(stream)))
+
+    def reset(self, stream=None) -> None:
+        _check(lib().pa_coverage_reset(self._h, _stream(stream)))
+
+    def summary(self, min_coverage: int = 1, stream=None):
+        """(covered_unique, covered_ambiguous, sum_unique, sum_ambiguous), each a
+        uint64 array per genome: positions with depth >= min_coverage, and the
+        summed depth."""
+        if not 0 <= int(min_coverage) < 2 ** 32:
+            raise ValueError("min_coverage must be in 1 .. 2^32 - 1")
+        G = self.n_genomes
+        out = [np.zeros(max(G, 1), dtype=np.uint64) for _ in range(4)]
+        _check(lib().pa_coverage_summary(self._h, int(min_coverage), *[_ptr(a) for a in out], _stream(stream)))
+        return tuple(a[:G] for a in out)
+
+    def depth(self, genome: int, first: int = 0, count: Optional[int] = None, stream=None):
+        """(unique depth, ambiguous depth) of positions [first, first + count) of
+        one genome (count None: to its end), uint32 arrays."""
+        genome, first = int(genome), int(first)
+        if not 0 <= genome < self.n_genomes:
+            raise ValueError("genome number out of range")
+        if first < 0 or (count is not None and int(count) < 0):
+            raise ValueError("positions past the end of the genome")
+        if count is None:
+            count = self.lengths[genome] - first
+            if count < 0:
+                raise ValueError("positions past the end of the genome")
+        count = int(count)
+        u = np.zeros(max(count, 1), dtype=np.uint32)
+        a = np.zeros(max(count, 1), dtype=np.uint32)
+        _check(lib().pa_coverage_depth(self._h, genome, first, count, _ptr(u), _ptr(a), _stream(stream)))
+        return u[:count], a[:count]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().pa_coverage_free(self._h)
+            self._h = None
+
+    __del__ = close

@@ -26,6 +26,10 @@
  *   pa_align_detail          the same, with per-read mapping type and
  *                            genomes_mapped_to (PseudoAlignment.reads)      src/kmer.py:542, 551-561
  *   pa_result_fetch          PseudoAlignment.get_summary inputs             src/kmer.py:622-657
+ *   pa_coverage_* /          the course project's EXTCOVERAGE extension (--coverage, --genomes,
+ *   pa_align_placements      --min-coverage, --full-coverage), which the reference leaves out: it
+ *                            has no coverage code, so the definition is DESIGN.md section 10; the
+ *                            occurrence sets it places reads with are kmers[w][g], src/kmer.py:140-150
  *   pa_align_batch           one-shot host-buffer form of pa_align
  *   pa_align_fastq_file      FASTAQFile + align_reads_from_container as one
  *                            device-parsed stream                          src/data_file.py:134-158,
@@ -317,6 +321,64 @@ pa_status pa_align(const pa_index *idx, const pa_reads *reads, const pa_params *
 pa_status pa_align_detail(const pa_index *idx, const pa_reads *reads, const pa_params *params, uint8_t *read_type,
                           uint32_t *filtered_kmers, uint32_t *redundant_kmers, uint64_t *list_off, uint32_t *lists,
                           uint64_t list_cap, uint64_t *list_total, void *stream);
+/* ---- coverage: where on a genome its reads fall ----------
+ *
+ * Every read is classified as pa_align_detail classifies it with the same
+ * params.  A uniquely or ambiguously mapped read is placed on each distinct
+ * genome g of its list (a p-demoted list holds G* twice: once): every window j
+ * of the read whose k-mer w occurs in g's region -- quality and --max-genomes
+ * filters or not -- votes for the diagonal min(occ(w, g)) - j; the placement
+ * s(read, g) is the diagonal with the most votes, the smallest on a tie.  The
+ * read then covers the region positions [s, s + length) inside the region; on a
+ * both-strand index (region g + N + reverse complement) position q < |g| is the
+ * forward coordinate q, q > |g| is 2|g| - q, the N is dropped, and a read over
+ * both halves counts in both.  depth_unique[g][x] / depth_ambiguous[g][x]
+ * (uint32, |g| entries, forward coordinates) count the covering reads of each
+ * type.  Dropped, unmapped and shorter-than-k reads add nothing.
+ *
+ * The placements need the k-mers' first occurrence per genome: the positions
+ * view of the index, 4 B per table slot + 4 B per (k-mer, genome) pair, built
+ * on the device by pa_index_prepare_coverage or by the first pa_coverage_add /
+ * pa_align_placements, counted in pa_index_info.device_bytes once it exists,
+ * released by pa_index_reduce and pa_index_free.  PA_EUNSUPPORTED for a
+ * reference of 2^32 - 1 or more region positions (a both-strand index holds
+ * 2|g| + 1 per genome); PA_ENOMEM when it does not fit -- the index then stays
+ * usable for everything else.  A coverage job runs on one device. */
+typedef struct pa_coverage pa_coverage;
+/* Build the positions view now (no-op when it exists); returns when done. */
+pa_status pa_index_prepare_coverage(pa_index *idx, void *stream);
+/* A zeroed depth accumulator for this index: 8 B per forward genome base on its
+ * device.  It serves this index until its next pa_index_reduce (PA_EINVAL
+ * after, and for any other index). */
+pa_status pa_coverage_create(const pa_index *idx, pa_coverage **out);
+pa_status pa_coverage_reset(pa_coverage *cov, void *stream);
+/* Classify as pa_align_detail, place, accumulate into `acc` (difference arrays:
+ * two atomics per read and genome, four for a read over both halves of a
+ * both-strand region).  PA_EUNSUPPORTED when the reads added since
+ * the last reset would reach 2^32; PA_EINTERNAL if a listed genome gets no
+ * vote (an invariant: never skipped silently).  Returns when done. */
+pa_status pa_coverage_add(const pa_index *idx, const pa_reads *reads, const pa_params *params, pa_coverage *acc,
+                          void *stream);
+/* Per genome (arrays of n_genomes entries, any may be NULL): positions with
+ * depth >= min_coverage (>= 1, else PA_EINVAL) and the sum of the depths, for
+ * the uniquely and the ambiguously mapped reads. */
+pa_status pa_coverage_summary(const pa_coverage *cov, uint32_t min_coverage, uint64_t *covered_unique,
+                              uint64_t *covered_ambiguous, uint64_t *sum_unique, uint64_t *sum_ambiguous,
+                              void *stream);
+/* Depths of positions [first, first + count) of one genome, forward
+ * coordinates; either array may be NULL.  PA_EINVAL: genome >= n_genomes, or a
+ * range past |g|. */
+pa_status pa_coverage_depth(const pa_coverage *cov, uint32_t genome, uint64_t first, uint64_t count,
+                            uint32_t *unique_depth, uint32_t *ambiguous_depth, void *stream);
+void pa_coverage_free(pa_coverage *cov);
+/* pa_align_detail's read_type, list_off and lists, plus starts[i] = s(read,
+ * lists[i]) for every list entry (region coordinates, may be negative; the two
+ * entries of a p-demoted G* are equal).  lists and starts may both be NULL to
+ * query *list_total first. */
+pa_status pa_align_placements(const pa_index *idx, const pa_reads *reads, const pa_params *params,
+                              uint8_t *read_type, uint64_t *list_off, uint32_t *lists, int64_t *starts,
+                              uint64_t list_cap, uint64_t *list_total, void *stream);
+
 /* upload + pa_align + fetch for host buffers (stats and per-genome arrays accumulate: +=, min) */
 pa_status pa_align_batch(const pa_index *idx, const uint8_t *seq, const uint8_t *qual, const uint64_t *read_off,
                          uint64_t n_reads, uint64_t read_index_base, const pa_params *params, pa_stats *stats,
@@ -397,6 +459,12 @@ pa_status pa_index_dumpref(const pa_index *idx, const uint8_t *keep, const uint3
  * ~0.15 s overlaps its imports and FASTA parse); later calls wait for it as
  * for any runtime start.  Always PA_OK (errors surface at the first real call). */
 pa_status pa_runtime_start(int32_t device);
+/* Wait until that start is over (at once when none was made or it is).  A
+ * process must not exit while the runtime is still starting on the other
+ * thread -- its exit handlers would run under that thread -- so a command-line
+ * run calls this on every way out (atexit), the error exits of its flag checks
+ * included.  Always PA_OK. */
+pa_status pa_runtime_wait(void);
 
 /* ---- multi-GPU reduce (RCCL over xGMI) ------------------------------------------- */
 
