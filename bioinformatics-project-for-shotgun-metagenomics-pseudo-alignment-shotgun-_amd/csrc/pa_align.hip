@@ -51,9 +51,13 @@ constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 // k_align_lane's queue segments (AlignArgs::na_seg): one per wave of its
 // grid, 64 entries per chunk of reads the wave takes; the queues hold the
-// reads of a batch plus one chunk per wave of slack.
+// reads of a batch plus kSegSlackChunks chunks per wave of slack -- the
+// rounding of a wave's share and the chunks a wave holds when it claims
+// (kLaneClaimHeld, pa_lane.h) -- for up to kSegSlackWaves waves, twice the
+// resident set of an MI355X (a larger grid takes the flat queue).
 constexpr uint32_t kSegMaxWaves = 16384;
-constexpr uint64_t kSegSlack = 64ull * kSegMaxWaves;
+constexpr uint32_t kSegSlackWaves = 8192, kSegSlackChunks = 5;
+constexpr uint64_t kSegSlack = 64ull * kSegSlackChunks * kSegSlackWaves;
 constexpr uint32_t kLdsGenomeCap = 2048;  // per-workgroup LDS counters up to this many genomes
 
 enum : uint32_t { F_MRQ = 1, F_MKQ = 2, F_MG = 4 };
@@ -125,6 +129,7 @@ struct AlignArgs {
     uint32_t nseg;                         //   entries s * seg_cap ... and their number to seg_cnt[s]; k_rc_seeds
     uint64_t seg_cap;                      //   takes them (nseg: the grid's waves)
     uint64_t queue_cap;                    // entries of every queue
+    uint32_t *lane_next;                   // k_align_lane: chunks claimed past every wave's first two (zeroed per pass)
     const uint4 *qmask;                    // (quality filters) per read: windows failing --min-kmer-quality
     const uint8_t *qdrop;                  //   and 1 if the read fails --min-read-quality (k_quality_masks)
     // wave kernel input: a list of read indices (null: reads 0 .. n-1)
@@ -309,6 +314,7 @@ __global__ __launch_bounds__(256) void k_quality_masks(const uint8_t *__restrict
 }
 
 #include "pa_lane.h"
+static_assert(kSegSlackChunks >= 1 + kLaneClaimHeld, "the queues' slack covers the chunks a wave holds");
 
 // Plane of the windows whose genome set is larger than mg (--max-genomes,
 // src/kmer.py:425-427), bit i of word j <-> position 64 j + i, from tile_cls
@@ -826,7 +832,7 @@ pa_status launch_lane(const AlignArgs &a0, hipStream_t st, pa_index *prof = null
     const bool mg = (a0.prm.flags & F_MG) != 0;
     const bool nm4 = long_reads && !win_q && nw == 1;
     AlignArgs a = a0;
-    const size_t shm = lane_lds_bytes(a.G, nm4 ? 4 : 2);
+    const size_t shm = lane_lds_bytes(a.G, nm4 ? 4 : 2, lane_sched(win_q, mg, nm4 ? 4 : 2, nw));
     auto kern = nw == 3
                     ? (win_q ? (mg ? k_align_lane<true, true, true, 2, 3> : k_align_lane<true, true, false, 2, 3>)
                        : need_q ? (mg ? k_align_lane<true, false, true, 2, 3> : k_align_lane<true, false, false, 2, 3>)
@@ -847,16 +853,24 @@ pa_status launch_lane(const AlignArgs &a0, hipStream_t st, pa_index *prof = null
     PA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     const uint64_t want = (a.n + kBlock - 1) / kBlock;
     const uint64_t resident = (uint64_t)std::max(1, per_cu) * (uint64_t)cus;
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, resident));
+    unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, resident));
+    // (PA_LANE_GRID=<blocks>: tests -- a small batch then runs many chunks per wave)
+    if (const char *e = std::getenv("PA_LANE_GRID"))
+        grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(grid, std::strtoull(e, nullptr, 10)));
     // the seedless reads for k_rc_seeds in per-wave queue segments: one
     // atomic per wave and chunk on the queue's counter serialised, and cost
     // c2rc (half its reads seedless) 0.27 ms per 10 M reads (PA_NA_SEG=0: the
-    // flat queue, A/B)
+    // flat queue, A/B).  A wave's share of the chunks, plus -- with claimed
+    // chunks (PA_LANE_CLAIM) -- the kLaneClaimHeld chunks it may hold: a wave
+    // stops claiming once its segment could not take those whole, that is with
+    // more than its share of all reads queued, so the waves that still claim
+    // have room for every read left and none is lost; a wave with few
+    // seedless reads takes as many chunks as it gets to
     {
         const char *e = std::getenv("PA_NA_SEG");
         const uint64_t waves = (uint64_t)grid * kWaves, chunks = (a.n + 63) / 64;
         a.nseg = (uint32_t)waves;
-        a.seg_cap = 64 * ((chunks + waves - 1) / waves);
+        a.seg_cap = 64 * ((chunks + waves - 1) / waves + kLaneClaimHeld);
         a.na_seg = a.queue_na && a.queue_na_keys && a.seg_cnt && !nm4 && nw == 1 && waves <= kSegMaxWaves &&
                    waves * a.seg_cap <= a.queue_cap && !(e && e[0] == '0');
     }
@@ -1087,7 +1101,8 @@ pa_status reserve_queues(pa_index *idx, uint64_t n) {
     PA_HIP(pa::dev_malloc(&idx->queue_rc, n * 4));
     PA_HIP(pa::dev_malloc(&idx->queue_rc_anc, n * 8));
     // [0] the lane kernel's reads without a seed, [1] k_rc_seeds' walkable ones, [2] the rest (k_align_lane_na)
-    if (!idx->na_count) PA_HIP(pa::dev_malloc(&idx->na_count, 24));
+    // [3] (32 bits) the lane kernel's claimed chunks
+    if (!idx->na_count) PA_HIP(pa::dev_malloc(&idx->na_count, 32));
     idx->queue_cap = n;
     return PA_OK;
 }
@@ -1324,7 +1339,9 @@ pa_status align(pa_index *idx, const pa_reads *r, const DevParams &p_in, uint64_
             a.queue_na2_count = idx->na_count + 2;
             a.na_min = 32768;  // (PA_NA_MIN: tests)
             if (const char *e = std::getenv("PA_NA_MIN")) a.na_min = std::strtoull(e, nullptr, 10);
-            if (na) PA_HIP(hipMemsetAsync(idx->na_count, 0, 24, st));
+            a.lane_next = (uint32_t *)(idx->na_count + 3);
+            // (the queue counts and the claims in one; without the seedless path only for the claims)
+            if (na || PA_LANE_CLAIM) PA_HIP(hipMemsetAsync(idx->na_count, 0, 32, st));
             // the 250-bp shape when any read is longer than the 150-bp one
             // takes: 176 bases or 128 windows (round 6: reads of 159-176 bases
             // at k = 31 went whole to the wave kernel, 0.15 G reads/s)

@@ -86,14 +86,65 @@ constexpr int kPassEntries = 64 * PA_LANE_PROBES;
 // the same G lines from every CU).  1664: a block's counters and its four
 // waves' LaneWave<2> (27 KB) fit 40 KB, four blocks per CU in 160 KB -- the
 // 4 waves per SIMD of the plain variant.  (Round 4 kept 512 at 12 B each: C5's
-// 1200 kept genomes counted in global memory.)
+// 1200 kept genomes counted in global memory.)  With the next chunk's offsets
+// parked in LDS (PA_LANE_PREOFF: 528 B per wave) the same 40 KB hold 1400.
 #ifndef PA_TWO_WINQ
 #define PA_TWO_WINQ 1  // the two-genome decision in the --min-kmer-quality variants too
 #endif
+// How k_align_lane's waves take their chunks of 64 reads (its loop; DESIGN.md
+// section 4), each =0 the earlier form (A/B):
+//   PA_LANE_CLAIM: past a wave's first two chunks (strided), from a device
+//     counter (a.lane_next), claimed two iterations ahead -- the atomic is
+//     issued with an iteration's chunk loads and read back after the packing,
+//     so nothing waits for it; =0: every chunk by the fixed stride;
+//   PA_LANE_PREOFF: the next chunk's read offsets are loaded with this
+//     iteration's chunk loads and parked in LDS (LaneWave::noff); =0: each
+//     iteration first waits for its own offsets, then loads its chunks.
+#ifndef PA_LANE_CLAIM
+#define PA_LANE_CLAIM 1
+#endif
+#ifndef PA_LANE_PREOFF
+#define PA_LANE_PREOFF 1
+#endif
+//   PA_LANE_RUN: chunks per claim away from the end of the pass (1: always one)
+#ifndef PA_LANE_RUN
+#define PA_LANE_RUN 2
+#endif
+// Chunks a wave holds right after a claim: in work, the next, the claimed run
+// (the bound of its queue segment, launch_lane).
+constexpr uint32_t kLaneClaimHeld = PA_LANE_CLAIM ? 2 + PA_LANE_RUN : 0;
+//   PA_LANE_TOPWAIT: one explicit s_waitcnt vmcnt(0) at the top of every
+//     iteration (kLaneWaitVm0, the gfx9 encoding of gfx950), before the claim
+//     goes out; =0: the compiler's own waits, which then cover the claim (A/B).
+#ifndef PA_LANE_TOPWAIT
+#define PA_LANE_TOPWAIT 1
+#endif
+//   PA_LANE_LATE: the claim and the next chunk's offset loads are issued
+//     behind the iteration's chunk loads (a hook in lane_pack), the claim
+//     last: loads and returning atomics come back in order, so the waits for
+//     the chunks then leave the claim in flight through the packing; =0: ahead
+//     of the chunk loads, whose first wait is then one for the claim too (A/B).
+#ifndef PA_LANE_LATE
+#define PA_LANE_LATE 1
+#endif
+// s_waitcnt immediate, gfx9 encoding: vmcnt [3:0] and [15:14] = 0, expcnt [6:4]
+// = 7 and lgkmcnt [11:8] = 15 (not waited for)
+constexpr int kLaneWaitVm0 = 0x0F70;
+// The instantiations that run that loop: not the 250-bp shape, nor
+// --max-genomes with single-word keys -- they pay for its few registers
+// with scratch at 4 waves per SIMD and keep the fixed stride and the unsplit
+// lane_prep.  launch_lane sizes the LDS by the same test.
+constexpr bool lane_sched(bool win_q, bool mg, int nm, int nw) {
+    return (PA_LANE_CLAIM || PA_LANE_PREOFF) && nm == 2 && (nw > 1 || !mg);
+}
+constexpr size_t kLaneOffsBytes = 66 * 8;  // a wave's parked offsets (65 used), after the block's LaneWaves
 #ifndef PA_LANE_LDS_GENOMES
 #define PA_LANE_LDS_GENOMES 1664
 #endif
-constexpr uint32_t kLaneLdsGenomeCap = PA_LANE_LDS_GENOMES;
+// (with the parked offsets the same 40 KB hold 1400 genomes' counters)
+constexpr uint32_t lane_lds_genome_cap(bool sched) {
+    return sched && PA_LANE_PREOFF ? PA_LANE_LDS_GENOMES - 264 : PA_LANE_LDS_GENOMES;
+}
 
 // Per-wave LDS of the lane kernel.
 template <int NM>
@@ -378,8 +429,286 @@ __device__ __forceinline__ bool lane_fits(const AlignArgs &a, uint32_t len, int6
     return A >= 0 && (uint64_t)A + len <= a.tile_n;
 }
 
+// Phase 1a: qualities and packing (into the lane's LDS row).  o, o1: the
+// read's offsets a.off[r], a.off[r + 1] (the caller's: the kernel fetches a
+// chunk's an iteration ahead).  False: the read is settled or left to another
+// kernel (S.kind); true: packed, S.kind still LANE_HARD.
+template <int NM, bool NEED_Q, bool WIN_Q, class AHEAD>
+__device__ __forceinline__ bool lane_pack(const AlignArgs &a, uint64_t r, uint64_t o, uint64_t o1, uint64_t *row,
+                                          LaneRead<NM> &S, AHEAD &&ahead) {
+    using SH = LaneShape<NM>;
+    static_assert(NM == 2 || !WIN_Q, "the window-quality masks cover 128 windows");
+    constexpr int NWD = SH::NWD;
+    S.kind = LANE_HARD;
+    S.hr = S.nspec = S.nincl = 0;
+#pragma unroll
+    for (int i = 0; i < NM; i++) S.F[i] = 0;
+    S.qf = 0;
+    S.uoff = 0;
+    const int k = a.k;
+    const uint32_t len = (uint32_t)(o1 - o);
+    const uint64_t o0 = o & ~15ull;
+    const uint32_t shift = (uint32_t)(o & 15);
+    S.len = len;
+    if (len > (uint32_t)SH::MAXLEN) return LANE_HARD_WHY(0), false;
+    // ---- qualities: the read's mean test (src/kmer.py:399, 587) and the windows
+    // failing --min-kmer-quality (src/kmer.py:404-408, 420-423), made for every
+    // read up front by k_quality_masks
+    if (NEED_Q) {
+        if (a.qdrop[r]) {
+            S.kind = LANE_DROP;  // dropped, not unmapped (src/kmer.py:587-589)
+            return false;
+        }
+        if (WIN_Q) {
+            const uint4 m = a.qmask[r];
+            S.F[0] = (uint64_t)m.x | ((uint64_t)m.y << 32);
+            S.F[NM - 1] = (uint64_t)m.z | ((uint64_t)m.w << 32);  // (NM == 2 here)
+            S.qf = (uint32_t)(__popcll(S.F[0]) + __popcll(S.F[NM - 1]));
+        }
+    }
+    if (len < (uint32_t)k) {
+        S.kind = LANE_UNMAPPED;  // no windows (src/kmer.py:91-92, 516-517)
+        return false;
+    }
+    const uint32_t W = len - k + 1;
+    S.W = W;
+    if (W > (uint32_t)SH::MAXW) return LANE_HARD_WHY(0), false;
+    // ---- 2-bit pack: staged word q (32 bases from the 16-B aligned start) from
+    // chunks 2q, 2q+1; row word q-1 = the read's bases from 0 on, shifted
+    const uint4 *sp = (const uint4 *)(a.seq + o0);
+    const uint32_t s2 = 2 * shift;
+    uint32_t bad = 0;
+    uint64_t prev = 0;
+    // every chunk load of the read issued before any is used (one round trip;
+    // the 250-bp shape: three, of six chunks each -- its registers);
+    // chunks past the read read as "AAAA" (code 0, valid)
+    constexpr int CG = NM == 2 ? 2 * NWD : 6;  // chunks per round trip
+#pragma unroll
+    for (int g0 = 0; g0 < 2 * NWD; g0 += CG) {
+    uint4 ch[CG];
+#pragma unroll
+    for (int c = 0; c < CG; c++)
+        ch[c] = (g0 + c < 2 * NWD && 16u * (g0 + c) < shift + len)
+                    ? sp[g0 + c]
+                    : make_uint4(0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u);
+    // (the kernel's loads for its next iterations go out behind the chunk
+    // loads: returns come in order, so the waits below leave them in flight)
+    if (g0 == 0) ahead();
+#pragma unroll
+    for (int q = g0 / 2; q < (g0 + CG) / 2 && q < NWD; q++) {
+        uint64_t P = 0;
+        if (32u * q < shift + len) {
+            const uint4 v0 = ch[2 * q - g0], v1 = ch[2 * q + 1 - g0];
+            const uint32_t d[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                const uint32_t cd = swar_codes(d[e]);
+#ifdef PA_PACK_MASKED
+                bad |= swar_bad_bytes(d[e], cd) & in_read_mask(32 * q + 4 * e, shift, len);
+#else
+                bad |= swar_bad_bytes(d[e], cd);  // (bytes of the neighbouring reads too: checked below)
+#endif
+                P |= (uint64_t)swar_pack_byte(cd) << (56 - 8 * e);
+            }
+        }
+        if (q > 0) row[q - 1] = s2 ? ((prev << s2) | (P >> (64 - s2))) : prev;
+        prev = P;
+    }
+    }
+    row[NWD - 1] = prev << s2;  // (staged word NWD would be zero: shift + len <= 32 NWD - 1)
+#ifndef PA_PACK_MASKED
+    // a non-ACGT byte in the staged chunks, most likely outside the read (the
+    // buffer's padding after the last read): only the read's own bytes count
+    // (the chunks loaded again: nothing stays live across the packing)
+    if (bad) {
+        bad = 0;
+#pragma unroll 1
+        for (int c = 0; c < 2 * NWD; c++) {
+            if (16u * c >= shift + len) break;
+            const uint4 v = sp[c];
+            const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+                bad |= swar_bad_bytes(d[e], swar_codes(d[e])) & in_read_mask(16u * c + 4 * e, shift, len);
+        }
+    }
+#endif
+    // (row[NWD], the zero word past the read, is cleared once per kernel:
+    // a store here kept a 64-bit zero live through the whole loop and spilled it)
+    if (bad) return LANE_HARD_WHY(2), false;  // non-ACGT base: the wave kernel poisons its windows
+#if defined(PA_STATS) || defined(PA_DISSECT)
+    if (a.dbg_mode == 13) {  // timing dissection: stop after the packing
+        S.kind = LANE_AMB;
+        return false;
+    }
+#endif
+    return true;
+}
+
+// Phase 1b: seeds -> anchor (a read walked again: the given anchor, cd != ~0).
+template <int NM, int NW = 1>
+__device__ __forceinline__ void lane_seeds(const AlignArgs &a, unsigned long long cd, const uint64_t *row,
+                                           LaneRead<NM> &S) {
+    const int k = a.k;
+    const uint32_t len = S.len, W = S.W;
+    if (cd != ~0ull) {  // walked again: from the specific k-mer found off the first walk
+        S.anc = cd;
+        S.acls = NONE;  // genome from the position
+        S.kind = LANE_WALK;
+        return;
+    }
+    const int sh = 64 - 2 * k;
+    // ---- seeds: NSEED windows spread evenly from the first to the last; a
+    // specific one (its genome is the read's) is preferred as the anchor
+    constexpr int NSEED = PA_LANE_SEEDS;
+    // (seed i's window, recomputed where needed rather than kept in registers)
+    auto sw = [W](int i) { return (uint32_t)(((uint64_t)(W - 1) * (uint32_t)i) / (NSEED - 1)); };
+    uint64_t skey[NW == 1 ? NSEED : 1];  // (single-word keys)
+    Key<NW> skk[NW == 1 ? 1 : NSEED];    // (two- and three-word keys, 31 < k <= 95)
+    if constexpr (NW == 1) {
+#pragma unroll
+        for (int i = 0; i < NSEED; i++) skey[i] = row_bits(row, 2 * sw(i)) >> sh;
+    } else {
+        (void)sh;
+#pragma unroll
+        for (int i = 0; i < NSEED; i++) skk[i] = row_key<NW>(row, sw(i), k);
+    }
+#ifndef PA_LANE_SEED_ROUNDS
+#define PA_LANE_SEED_ROUNDS 2
+#endif
+    // two rounds: the first and the last seed, then -- only if neither is a
+    // specific k-mer -- the middle ones (a random 64-B line per probe is what
+    // bounds this kernel)
+    uint32_t sfound = 0, scls[NSEED], stp32[NSEED];
+    {
+#ifndef PA_LANE_SEED_R1
+#define PA_LANE_SEED_R1 (1u | (1u << (NSEED - 1)))  // the first round's seeds
+#endif
+        constexpr uint32_t all = (1u << NSEED) - 1, outer = PA_LANE_SEED_R1;
+        uint32_t act = PA_LANE_SEED_ROUNDS > 1 ? outer : all;
+#pragma unroll 1
+        for (int round = 0; round < 2 && act; round++) {
+            uint32_t f;
+            if constexpr (NW == 1)
+                lane_probe<NSEED, PA_SEED_SLOTS>(a, skey, act, f, scls, stp32);
+            else
+                lane_probe_k<NSEED, NW == 3 ? 1 : PA_SEED_SLOTS, NW>(a, skk, act, f, scls, stp32);  // (NW 3: registers)
+            sfound |= f;
+            bool spec = false;
+#pragma unroll
+            for (int i = 0; i < NSEED; i++) spec |= bit(f, i) && cls_of(scls[i]) < a.G && stp32[i] != NONE;
+#ifndef PA_LANE_R2_ONLY_UNSEEDED
+#define PA_LANE_R2_ONLY_UNSEEDED 0  // 1 (A/B): the second round only when the first found no seed at all --
+                                    // C4 3.94 -> 1.95, C2 3.71 -> 1.91 G reads/s (round 6, profiles/r06/ab_r2u.txt):
+                                    // a stretch named by a shared outer seed is a family's first member, and the
+                                    // walk on it sends most such reads to the wave kernel
+#endif
+            act = (round == 0 && act != all && !spec && (!PA_LANE_R2_ONLY_UNSEEDED || f == 0)) ? all & ~outer : 0u;
+#if defined(PA_STATS) || defined(PA_DISSECT)
+            if (a.dbg_mode == 14) act = 0;  // timing dissection: one seed round
+#endif
+#ifdef PA_STATS
+            if (act) atomicAdd(&a.dbg[27], 1ull);
+#endif
+        }
+    }
+    uint64_t stp[NSEED];  // first occurrences, concatenated positions (NONE64: none)
+#pragma unroll
+    for (int i = 0; i < NSEED; i++) {
+        stp[i] = bit(sfound, i) && stp32[i] != NONE ? first_pos(scls[i], stp32[i], a.G, a.class_genomes, a.goff, a.tpos_local)
+                                                     : ~0ull;
+        scls[i] = cls_of(scls[i]);  // (the position bit used)
+    }
+    int at = -1;
+#pragma unroll
+    for (int pass = 0; pass < 2; pass++)
+#pragma unroll
+        for (int i = 0; i < NSEED; i++)
+            if (at < 0 && stp[i] != ~0ull && (pass == 1 || scls[i] < a.G)) at = i;
+    if (at < 0) {  // no anchor: no seed k-mer is in the index
+        if (a.queue_na) S.kind = LANE_NOANCHOR;
+        // the reverse complements of the outer seeds -- R' windows 0 and W - 1
+        // of the read's reverse complement R' -- for k_rc_seeds (S.P[0] / S.P[1]:
+        // walk fields, unused by such a read)
+        if constexpr (NW == 1) {
+            S.P[0] = rc_key(skey[NSEED - 1], k);
+            S.P[1] = rc_key(skey[0], k);
+        }
+        return (void)LANE_HARD_WHY(3);
+    }
+    S.anc = stp[0] | ((uint64_t)sw(0) << 40);
+    S.acls = scls[0];
+#pragma unroll
+    for (int i = 1; i < NSEED; i++)
+        if (at == i) {
+            S.anc = stp[i] | ((uint64_t)sw(i) << 40);
+            S.acls = scls[i];
+        }
+    // no specific seed: the first occurrence of a multi-genome seed k-mer may
+    // lie in a sibling of the read's genome (a family member), whose variants
+    // would leave many windows unwalked.  Other found seeds may point to other
+    // stretches: walk the one with the fewest mismatching bases (up to three)
+    if (S.acls >= a.G) {
+        // distinct candidate stretches (selects only: no runtime register indexing)
+        const int64_t e0 = (int64_t)(S.anc & kPosMask) - (int64_t)(S.anc >> 40);
+        int64_t e1 = INT64_MIN, e2 = INT64_MIN;
+        uint64_t t1 = 0, t2 = 0;
+        uint32_t w1 = 0, c1 = 0, w2 = 0, c2 = 0;
+#pragma unroll
+        for (int i = 0; i < NSEED; i++) {
+            const int64_t Ai = (int64_t)stp[i] - sw(i);
+            if (stp[i] == ~0ull || Ai == e0 || Ai == e1 || e2 != INT64_MIN) continue;
+            if (e1 == INT64_MIN) {
+                e1 = Ai;
+                t1 = stp[i], w1 = sw(i), c1 = scls[i];
+            } else {
+                e2 = Ai;
+                t2 = stp[i], w2 = sw(i), c2 = scls[i];
+            }
+        }
+        if (e1 != INT64_MIN) {
+#ifdef PA_STATS
+            atomicAdd(&a.dbg[26], 1ull);
+#endif
+            // the stretches' walk blocks loaded together (one round trip, not one
+            // per stretch), ranked on the read's first kRankWords x 32 bases:
+            // the choice only steers the walk (any stretch gives the exact
+            // result), and the genome words of three whole reads in flight
+            // made the kernel spill.  The 250-bp shape ranks on 160 of its
+            // bases (round 6: c2l250 1.58 -> 1.65 G reads/s vs 96; all 250:
+            // 28 B/lane of scratch, 1.63)
+#ifndef PA_LANE_RANK_WORDS4
+#define PA_LANE_RANK_WORDS4 5
+#endif
+            constexpr int NR = NM == 2 ? PA_LANE_RANK_WORDS : PA_LANE_RANK_WORDS4;  // (the 250-bp shape: its registers)
+            const uint32_t rlen = len < 32u * NR ? len : 32u * NR;
+            const bool f0 = lane_fits(a, len, e0), f1 = lane_fits(a, len, e1), f2 = e2 != INT64_MIN && lane_fits(a, len, e2);
+            uint64_t g0[NR + 1], g1[NR + 1], g2[NR + 1], u3[3];
+            lane_blocks<false, NR>(a, f0 ? (uint64_t)e0 : 0, rlen, g0, u3, u3);
+            lane_blocks<false, NR>(a, f1 ? (uint64_t)e1 : 0, rlen, g1, u3, u3);
+            lane_blocks<false, NR>(a, f2 ? (uint64_t)e2 : 0, rlen, g2, u3, u3);
+            const uint32_t m0 = f0 ? lane_count_mismatches<NR>(row, rlen, (uint64_t)e0, g0) : ~0u;
+            const uint32_t m1 = f1 ? lane_count_mismatches<NR>(row, rlen, (uint64_t)e1, g1) : ~0u;
+            const uint32_t m2 = f2 ? lane_count_mismatches<NR>(row, rlen, (uint64_t)e2, g2) : ~0u;
+            uint32_t bj = 0, best = m0;
+            if (m1 < best) best = m1, bj = 1;
+            if (m2 < best) best = m2, bj = 2;
+            if (bj == 1) {
+                S.anc = t1 | ((uint64_t)w1 << 40), S.acls = c1;
+            } else if (bj == 2) {
+                S.anc = t2 | ((uint64_t)w2 << 40), S.acls = c2;
+            }
+        }
+    }
+    S.kind = LANE_WALK;
+}
+
 // Phase 1: qualities, packing (into the lane's LDS row), seeds -> anchor (a
-// read walked again: the given anchor, cd != ~0).
+// read walked again: the given anchor, cd != ~0).  The unsplit form of
+// lane_pack + lane_seeds above, kept as it was for k_align_lane_na and for the
+// k_align_lane instantiations that keep the fixed stride (lane_sched): the
+// split alone cost the 250-bp shape 12-24 B/lane of scratch.  A change to
+// one goes into the other.
 template <int NM, bool NEED_Q, bool WIN_Q, bool SEEDS = true, int NW = 1>
 __device__ __forceinline__ void lane_prep(const AlignArgs &a, uint64_t r, unsigned long long cd, uint64_t *row,
                                           LaneRead<NM> &S) {
@@ -741,6 +1070,85 @@ __device__ __forceinline__ void lane_walk_150(const AlignArgs &a, const uint64_t
     uint32_t nnb = 0;
     const uint32_t qlast = (len - 1) >> 5, rl = len - 32 * qlast;  // the last word holds rl bases
     const uint64_t tail = rl >= 32 ? ~0ull : ~0ull << (64 - 2 * rl);
+    // the mismatching base e of the read (sub(): its substitution index, made
+    // only where it is used); false: too many mismatches, the read is given up
+    auto mismatch = [&](uint32_t e, auto &&sub) -> bool {
+        const int32_t lo = (int32_t)e - k + 1 < 0 ? 0 : (int32_t)e - k + 1;
+        const int32_t hi = (int32_t)e < (int32_t)W - 1 ? (int32_t)e : (int32_t)W - 1;
+        if (lo > hi) return true;
+        const uint64_t r0 = lo < 64 ? ((~0ull << lo) & (hi >= 63 ? ~0ull : ((2ull << hi) - 1))) : 0ull;
+        const uint64_t r1 =
+            hi >= 64 ? ((lo <= 64 ? ~0ull : (~0ull << (lo - 64))) & (hi >= 127 ? ~0ull : ((2ull << (hi - 64)) - 1)))
+                     : 0ull;
+        if (!((r0 & IX0) | (r1 & IX1))) return true;
+        if (++nmis > 8) {
+            // past the neighbour-bit budget (a sibling's stretch, not a few
+            // sequencing errors): its windows are probed; the walked ones
+            // still hold (a found specific k-mer re-anchors the read)
+            if (nmis > kLaneMaxMis) return false;
+            V0 |= r0;
+            V1 |= r1;
+            U0 |= r0;
+            U1 |= r1;
+            return true;
+        }
+        V0 |= U0 & r0;
+        V1 |= U1 & r1;
+        U0 |= r0;
+        U1 |= r1;
+        if (has_nb) {  // the neighbour word of the genome base at A + e and the read's base there
+            epk |= (uint64_t)e << (8 * nnb);
+            cpk |= sub() << (2 * nnb);
+            nnb++;
+        }
+        return true;
+    };
+#ifndef PA_LANE_ONELOOP
+#define PA_LANE_ONELOOP 1
+#endif
+#if PA_LANE_ONELOOP
+    // one loop over the read's mismatches, in base order: as many turns as the
+    // wave's worst read has mismatches, not the sum over the words of the
+    // wave's worst word.  The mismatch bits of words 2p (even bits) and 2p + 1
+    // (odd bits) in MM[p]
+    constexpr int NP2 = (kLaneWords + 1) / 2;
+    uint64_t MM[NP2];
+#pragma unroll
+    for (int p = 0; p < NP2; p++) MM[p] = 0;
+#pragma unroll
+    for (int i = 0; i < kLaneWords; i++) {
+        if (32 * i >= (int)len) break;
+        const uint64_t gwi = gr ? ((gw[i] << gr) | (gw[i + 1] >> (64 - gr))) : gw[i];
+        uint64_t d = row[i] ^ gwi;
+        if ((uint32_t)i == qlast) d &= tail;
+        const uint64_t m = (d | (d >> 1)) & 0x5555555555555555ull;  // one bit per mismatching base
+        MM[i >> 1] |= (i & 1) ? m << 1 : m;
+    }
+    while (true) {
+        uint64_t mm = 0;
+        uint32_t p = 0;
+#pragma unroll
+        for (int q = NP2 - 1; q >= 0; q--)
+            if (MM[q]) mm = MM[q], p = (uint32_t)q;
+        if (!mm) break;
+        const uint64_t ev = mm & 0x5555555555555555ull;
+        const uint32_t odd = ev ? 0u : 1u;  // (word 2p's before word 2p + 1's)
+        const uint32_t j = __builtin_clzll(odd ? mm >> 1 : ev) >> 1, e = 32 * (2 * p + odd) + j;
+        const uint64_t clr = ~((odd ? 2ull : 1ull) << (62 - 2 * j));
+#pragma unroll
+        for (int q = 0; q < NP2; q++) MM[q] &= p == (uint32_t)q ? clr : ~0ull;
+        const bool ok = mismatch(e, [&]() {
+            const uint32_t o = gr + 2 * e;  // (even: the base's two bits lie in one word)
+            const uint32_t cg = (uint32_t)(word_at(gw, o >> 6) >> (62 - (o & 63))) & 3u;
+            const uint32_t cr = (uint32_t)(row[e >> 5] >> (62 - 2 * (e & 31))) & 3u;
+            return (cr - cg - 1) & 3u;
+        });
+        if (!ok) {
+            S.kind = LANE_HARD;
+            return (void)LANE_HARD_WHY(5);
+        }
+    }
+#else
 #pragma unroll
     for (int i = 0; i < kLaneWords; i++) {
         if (32 * i >= (int)len) break;
@@ -751,40 +1159,17 @@ __device__ __forceinline__ void lane_walk_150(const AlignArgs &a, const uint64_t
         while (m) {
             const uint32_t j = __builtin_clzll(m) >> 1, e = 32 * i + j;
             m &= ~(1ull << (62 - 2 * j));
-            const int32_t lo = (int32_t)e - k + 1 < 0 ? 0 : (int32_t)e - k + 1;
-            const int32_t hi = (int32_t)e < (int32_t)W - 1 ? (int32_t)e : (int32_t)W - 1;
-            if (lo > hi) continue;
-            const uint64_t r0 = lo < 64 ? ((~0ull << lo) & (hi >= 63 ? ~0ull : ((2ull << hi) - 1))) : 0ull;
-            const uint64_t r1 =
-                hi >= 64 ? ((lo <= 64 ? ~0ull : (~0ull << (lo - 64))) & (hi >= 127 ? ~0ull : ((2ull << (hi - 64)) - 1)))
-                         : 0ull;
-            if (!((r0 & IX0) | (r1 & IX1))) continue;
-            if (++nmis > 8) {
-                // past the neighbour-bit budget (a sibling's stretch, not a few
-                // sequencing errors): its windows are probed; the walked ones
-                // still hold (a found specific k-mer re-anchors the read)
-                if (nmis > kLaneMaxMis) {
-                    S.kind = LANE_HARD;
-                    return (void)LANE_HARD_WHY(5);
-                }
-                V0 |= r0;
-                V1 |= r1;
-                U0 |= r0;
-                U1 |= r1;
-                continue;
-            }
-            V0 |= U0 & r0;
-            V1 |= U1 & r1;
-            U0 |= r0;
-            U1 |= r1;
-            if (has_nb) {  // the neighbour word of the genome base at A + e and the read's base there
+            const bool ok = mismatch(e, [&]() {
                 const uint32_t cg = (uint32_t)(gwi >> (62 - 2 * j)) & 3u, cr = (uint32_t)(row[i] >> (62 - 2 * j)) & 3u;
-                epk |= (uint64_t)e << (8 * nnb);
-                cpk |= ((cr - cg - 1) & 3u) << (2 * nnb);
-                nnb++;
+                return (cr - cg - 1) & 3u;
+            });
+            if (!ok) {
+                S.kind = LANE_HARD;
+                return (void)LANE_HARD_WHY(5);
             }
         }
     }
+#endif
     // the neighbour words, four loads in flight at a time (one round trip for
     // up to four mismatches, not one per mismatch)
 #pragma unroll 1
@@ -1396,12 +1781,18 @@ void k_align_lane(AlignArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const uint32_t G = a.G;
     const int lane = lane_id();
-    const bool lds = G <= kLaneLdsGenomeCap;
+    constexpr bool kSched = lane_sched(WIN_Q, MG, NM, NW);
+    const bool lds = G <= lane_lds_genome_cap(kSched);
     const size_t cnt_bytes = lds ? ((size_t)G * 8 + 15) / 16 * 16 : 0;
     uint32_t *first = (uint32_t *)smem;  // the smallest batch-local index of a unique read of g (first_key rank 0)
     uint32_t *uniq = first + (lds ? G : 0);
     // (the wave's index read from lane 0: the LDS base is then a scalar, not a VGPR held all kernel long)
     LW_t &LW = ((LW_t *)(smem + cnt_bytes))[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
+    // a.off of the wave's next chunk, lane l's read from [l] to [l + 1] (PA_LANE_PREOFF; after the LaneWaves)
+    uint64_t *noff = nullptr;
+    if constexpr (kSched && PA_LANE_PREOFF)
+        noff = (uint64_t *)(smem + cnt_bytes + kWaves * sizeof(LW_t) +
+                            kLaneOffsBytes * (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
     if (lds) {
         for (uint32_t i = threadIdx.x; i < G; i += kBlock) {
             first[i] = ~0u;
@@ -1422,14 +1813,39 @@ void k_align_lane(AlignArgs a) {
     // specific k-mer off it is walked again from that k-mer, but later, with 63
     // others (a list per wave), so that the 3 % of such reads do not hold whole
     // waves for a second walk.  Every decision below is wave-uniform.
+    // The grid is the resident set, so a fixed stride leaves the waves that
+    // finish their share early (XCD and HBM distance, divergent chunks) idle
+    // to the end of the launch: past its first two chunks a wave claims them
+    // from a.lane_next (PA_LANE_CLAIM).  `chunk` is the one to work on, `chunk1`
+    // the one after it, known an iteration ahead so that its offsets can be
+    // fetched early (PA_LANE_PREOFF); a claim is the one after that.
+    // (Not in every instantiation: lane_sched.)
+    constexpr bool CLAIM = PA_LANE_CLAIM && kSched, PREOFF = PA_LANE_PREOFF && kSched;
     const uint64_t n_chunks = (a.n + 63) / 64, wave_stride = (uint64_t)gridDim.x * kWaves;
     uint64_t chunk = (uint64_t)blockIdx.x * kWaves + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint64_t chunk1 = chunk + wave_stride;
+    // a.off[min(64 c + lane + 1, n)] (and, in lane 0, a.off[64 c]) of chunk c
+    auto chunk_offs = [&](uint64_t c, uint64_t &o0, uint64_t &o1) {
+        const uint64_t i = c * 64 + (uint32_t)lane;
+        o1 = a.off[i + 1 < a.n ? i + 1 : a.n];
+        if (lane == 0) o0 = a.off[i];  // (c < n_chunks: 64 c < n)
+    };
+    if constexpr (PREOFF) {
+        if (chunk < n_chunks) {  // the first chunk's offsets (no iteration before it)
+            uint64_t o0 = 0, o1;
+            chunk_offs(chunk, o0, o1);
+            noff[lane + 1] = o1;
+            if (lane == 0) noff[0] = o0;
+        }
+    }
     // this wave's segment of the seedless reads' queue (a.na_seg): entries
     // seg_base ... seg_base + seg_na (scalar)
     const uint32_t wave_id = (uint32_t)chunk;
     const uint64_t seg_base = (uint64_t)wave_id * a.seg_cap;
     uint32_t seg_na = 0;
     uint32_t n_again = 0;  // entries in LW.again_r / again_a
+    uint64_t res = 0;      // the rest of a claimed run: chunks res ... res + nres - 1 (scalar)
+    uint32_t nres = 0;
     while (true) {
         uint32_t r = ~0u;  // (a batch holds < 2^32 reads: pa::align)
         unsigned long long cd = ~0ull;
@@ -1444,10 +1860,53 @@ void k_align_lane(AlignArgs a) {
             again_batch = true;
         } else if (chunk < n_chunks) {
             r = chunk * 64 + lane < a.n ? (uint32_t)(chunk * 64 + lane) : ~0u;
-            chunk += wave_stride;
+            if constexpr (!CLAIM && !PREOFF) chunk += wave_stride;
         } else {
             break;
         }
+        // a fresh chunk: the claim of the chunk after chunk1 and the loads of
+        // chunk1's offsets go out right behind this chunk's loads (lane_pack) and
+        // are taken up after the packing, and the few registers
+        // (cl, no0, no1) are free again before the seeds.  A wave claims only
+        // while its queue segment takes every chunk it then holds whole (64
+        // kLaneClaimHeld entries; launch_lane sizes the segments so that the
+        // waves still claiming can take all that is left)
+        const bool fresh = !again_batch;
+        uint32_t cl = 0;
+        uint64_t no0 = 0, no1 = 0;
+        bool claimed = false;
+        // (whatever the last iteration left in flight -- its queue stores, little else --
+        // is waited for before the claim goes out, not after: the compiler's waits for
+        // registers it may still see pending are else waits for the claim itself)
+        if constexpr ((CLAIM || PREOFF) && PA_LANE_TOPWAIT) __builtin_amdgcn_s_waitcnt(kLaneWaitVm0);
+        // A claim is for a run of PA_LANE_RUN consecutive chunks (the rest of a
+        // run waits in res / nres; no claim while it lasts), single chunks near
+        // the end of the pass, where the balance is made: 4096 waves' atomics
+        // on one address are the claim's cost
+        uint32_t run = 1;
+        if constexpr (CLAIM) {
+            claimed = fresh && nres == 0 && chunk1 < n_chunks &&
+                      (!(NM == 2 && a.na_seg) || seg_na + 64 * kLaneClaimHeld <= a.seg_cap);
+            if (PA_LANE_RUN > 1 && chunk1 + 4 * wave_stride < n_chunks) run = PA_LANE_RUN;
+        }
+        // (per lane: lane_pack calls it once its chunk loads are out -- PA_LANE_LATE --
+        // and a lane that left lane_pack earlier, or has no read, calls it after)
+        bool ahead_done = !fresh;
+        auto ahead = [&]() {
+            if (ahead_done) return;
+            ahead_done = true;
+            if (PREOFF && chunk1 < n_chunks) chunk_offs(chunk1, no0, no1);
+            if constexpr (CLAIM) {
+                if (claimed && lane == 0) {
+                    // (the address with an opaque zero index: for a uniform one the compiler
+                    // combines the wave's lanes into one atomic and waits for it on the spot)
+                    uint32_t z = 0;
+                    asm volatile("" : "+v"(z));
+                    cl = atomicAdd(a.lane_next + z, run);
+                }
+            }
+        };
+        if constexpr (!PA_LANE_LATE) ahead();
         LaneRead<NM> S;
         S.kind = LANE_UNMAPPED + 100;  // (past the end: counted nowhere)
         wave_sync();  // the previous read's rows (and the taken list entries) are done with
@@ -1458,7 +1917,53 @@ void k_align_lane(AlignArgs a) {
             asm volatile("" : "+v"(l));
             return LW.R[l];
         };
-        if (r != ~0u) lane_prep<NM, NEED_Q, WIN_Q, true, NW>(a, r, cd, my_row(), S);
+        if constexpr (!CLAIM && !PREOFF) {
+            if (r != ~0u) lane_prep<NM, NEED_Q, WIN_Q, true, NW>(a, r, cd, my_row(), S);
+        } else {
+            bool packed = false;
+            if (r != ~0u) {
+                // (the LDS values through an opaque copy: the compiler otherwise joins
+                // the two sources into one flat load of a selected address, and every
+                // wait after a flat load is a wait for all memory operations)
+                uint64_t o = 0, o1 = 0;
+                if constexpr (PREOFF) {
+                    o = noff[lane], o1 = noff[lane + 1];
+                    asm volatile("" : "+v"(o), "+v"(o1));
+                }
+                if (!PREOFF || !fresh) {  // (a read walked again: loaded)
+                    o = a.off[r], o1 = a.off[r + 1];
+                    // (waited for here, inside the branch: a wait where the paths join would
+                    // be one for the fresh path's claim and offsets too)
+                    if constexpr (PREOFF) asm volatile("" : "+v"(o), "+v"(o1));
+                }
+                packed = lane_pack<NM, NEED_Q, WIN_Q>(a, r, o, o1, my_row(), S, ahead);
+            }
+            ahead();
+            if (fresh) {
+                if constexpr (PREOFF) {
+                    wave_sync();  // (every lane has read this chunk's)
+                    if (chunk1 < n_chunks) {
+                        noff[lane + 1] = no1;
+                        if (lane == 0) noff[0] = no0;
+                    }
+                }
+                chunk = chunk1;
+                if constexpr (CLAIM) {
+                    if (nres) {
+                        chunk1 = res++;
+                        nres--;
+                    } else if (claimed) {
+                        chunk1 = 2 * wave_stride + (uint32_t)__builtin_amdgcn_readfirstlane(cl);
+                        res = chunk1 + 1;
+                        nres = run - 1;
+                    } else {
+                        chunk1 = ~0ull;
+                    }
+                } else
+                    chunk1 += wave_stride;
+            }
+            if (packed) lane_seeds<NM, NW>(a, cd, my_row(), S);
+        }
 #if defined(PA_STATS) || defined(PA_DISSECT)
         if (a.dbg_mode == 10 && S.kind == LANE_WALK) S.kind = LANE_AMB;  // timing dissection: stop after the seeds
 #endif
@@ -1652,8 +2157,9 @@ void k_align_lane(AlignArgs a) {
     }
 }
 
-constexpr size_t lane_lds_bytes(uint32_t G, int NM = 2) {
-    return (G <= kLaneLdsGenomeCap ? ((size_t)G * 8 + 15) / 16 * 16 : 0) +
+constexpr size_t lane_lds_bytes(uint32_t G, int NM = 2, bool sched = false) {
+    return (G <= lane_lds_genome_cap(sched) ? ((size_t)G * 8 + 15) / 16 * 16 : 0) +
+           (sched && PA_LANE_PREOFF ? kWaves * kLaneOffsBytes : 0) +
            (size_t)kWaves * (NM == 4 ? sizeof(LaneWave<4>) : sizeof(LaneWave<2>));
 }
 
