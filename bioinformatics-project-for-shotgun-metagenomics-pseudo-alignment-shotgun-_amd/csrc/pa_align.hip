@@ -1221,7 +1221,7 @@ pa_status align(pa_index *idx, const pa_reads *r, const DevParams &p_in, uint64_
     a.dbg = (unsigned long long *)idx->counters + 4;
     PA_HIP(hipMemsetAsync(idx->counters, 0, 8, st));
 #ifdef PA_STATS
-    PA_HIP(hipMemsetAsync(a.dbg, 0, 224, st));
+    PA_HIP(hipMemsetAsync(a.dbg, 0, 36 * 8, st));
 #endif
     ExactArgs x{};
     unsigned egrid = 0;
@@ -1374,8 +1374,8 @@ pa_status align(pa_index *idx, const pa_reads *r, const DevParams &p_in, uint64_
         PA_HIP(hipGetLastError());
     }
 #ifdef PA_STATS
-    unsigned long long d[32];
-    PA_HIP(hipMemcpyAsync(d, idx->counters, 256, hipMemcpyDeviceToHost, st));
+    unsigned long long d[40];
+    PA_HIP(hipMemcpyAsync(d, idx->counters, sizeof d, hipMemcpyDeviceToHost, st));
     PA_HIP(hipStreamSynchronize(st));
     fprintf(stderr, "[pa_stats] reads %llu lane-hard %llu exact %llu | wave kernel: windows %llu probed %llu walk %llu anchors %llu\n",
             (unsigned long long)r->n, d[3], d[0], d[4], d[5], d[6], d[7]);
@@ -1383,6 +1383,7 @@ pa_status align(pa_index *idx, const pa_reads *r, const DevParams &p_in, uint64_
             d[8], d[9], d[10], d[11], d[12], d[13], d[14], d[15], d[16]);
     fprintf(stderr, "[pa_stats] lane: cooperative probes %llu re-anchors %llu neighbour words %llu | pending: invalid %llu "
             "2+ mismatches %llu neighbour present %llu\n", d[18], d[19], d[20], d[21], d[22], d[23]);
+    fprintf(stderr, "[pa_stats] lane: single-probe re-anchors %llu second walks given up unprobed %llu\n", d[32], d[33]);
     fprintf(stderr, "[pa_stats] lane found: shared-neighbour+specific %llu second-walk specific %llu probed-shared+specific %llu"
             " | unique by bound %llu, by off-walk counts %llu | probes past the Bloom filter %llu\n", d[24], d[25], d[26], d[27], d[28],
             d[29]);

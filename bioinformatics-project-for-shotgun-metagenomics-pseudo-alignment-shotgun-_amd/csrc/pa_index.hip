@@ -2545,8 +2545,8 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
     else
         PA_HIP(pa::dev_malloc(&idx->codes, std::max<uint64_t>(total, 1)));
     PA_HIP(pa::dev_malloc(&idx->goff, (n + 1) * 8));
-    PA_HIP(pa::dev_malloc(&idx->counters, 32 * 8));
-    PA_HIP(hipMemsetAsync(idx->counters, 0, 32 * 8, st));
+    PA_HIP(pa::dev_malloc(&idx->counters, 40 * 8));
+    PA_HIP(hipMemsetAsync(idx->counters, 0, 40 * 8, st));
     PA_HIP(hipMemcpyAsync(idx->goff, idx->h_goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
     if (both) {
         PA_HIP(pa::dev_malloc(&idx->fwd_len, std::max<uint64_t>(n, 1) * 8));

@@ -164,7 +164,7 @@ struct pa_index {
     uint32_t *seg_cnt = nullptr;       // [kSegMaxWaves] the lane kernel's per-wave queue segments (pa_align.hip)
     uint64_t queue_cap = 0;            // entries of every queue (the reads of a batch + kSegSlack)
     uint64_t *counters = nullptr;      // [0] queue length, [1] deferred total, [2] error flags, [3] hard reads,
-                                       // [4..31] PA_STATS counters
+                                       // [4..39] PA_STATS counters
     // profiling
     bool profile = false;
     std::vector<hipEvent_t> ev_start, ev_stop;

@@ -127,6 +127,23 @@ constexpr uint32_t kLaneClaimHeld = PA_LANE_CLAIM ? 2 + PA_LANE_RUN : 0;
 #ifndef PA_LANE_LATE
 #define PA_LANE_LATE 1
 #endif
+//   PA_LANE_SURE: a read whose walk already shows that it will be walked
+//     again (lane_walk_150's last step: present specific neighbours against
+//     too few walked specific k-mers) probes one of those neighbours for its
+//     anchor, not every unwalked window, and on its second walk none at all;
+//     =0: every unwalked window of such a read is probed both times (A/B).
+#ifndef PA_LANE_SURE
+#define PA_LANE_SURE 1
+#endif
+// LaneRead::uoff of such a read (a count of windows is below 2^9)
+constexpr uint32_t kLaneSure = 1u << 31;
+// The instantiations with that rule: single-word keys (the neighbour words of
+// two- and three-word keys have no specific half); of the 250-bp shape not
+// --max-genomes, which pays for it with 4 B/lane more scratch (DESIGN.md
+// section 6).
+constexpr bool lane_sure(bool win_q, bool mg, int nm, int nw) {
+    return PA_LANE_SURE && nw == 1 && (nm == 2 || !mg);
+}
 // s_waitcnt immediate, gfx9 encoding: vmcnt [3:0] and [15:14] = 0, expcnt [6:4]
 // = 7 and lgkmcnt [11:8] = 15 (not waited for)
 constexpr int kLaneWaitVm0 = 0x0F70;
@@ -343,7 +360,8 @@ struct LaneRead {
     uint64_t P[NM];                    // unwalked windows (bit w of word w / 64)
     uint64_t F[NM];                    // windows failing --min-kmer-quality (never looked up)
     uint32_t qf;                       // their number (src/kmer.py:420-423)
-    uint32_t uoff;                     // walk windows whose k-mer is off the walk, present and multi-genome (neighbour bits)
+    uint32_t uoff;                     // walk windows whose k-mer is off the walk, present and multi-genome (neighbour bits);
+                                       // kLaneSure: P is one present specific neighbour, the read is walked again
 };
 
 // 64 bits of an LDS row of MSB-first packed words starting at bit o.
@@ -1023,7 +1041,10 @@ __device__ __forceinline__ void shifted_planes(const uint64_t (&p)[NM + 1], uint
 // others are left in S.P for the cooperative probes.  The 150-bp shape (NM =
 // 2) in named words: the NM-general form (lane_walk_long) needs ~10 more
 // VGPRs here, and the kernel then spills at 4 waves per SIMD.
-template <bool WIN_Q, bool MG, int NW = 1>
+// SURE (PA_LANE_SURE; single-word keys with both halves of the neighbour
+// words): 1: the read that is walked again whatever its probes return keeps
+// one window to probe (the last step); 2: only reported, for lane_walk_halves.
+template <bool WIN_Q, bool MG, int NW = 1, int SURE = lane_sure(WIN_Q, MG, 2, NW)>
 __device__ __forceinline__ void lane_walk_150(const AlignArgs &a, const uint64_t *row, LaneRead<2> &S) {
     const int k = a.k;
     uint32_t W = S.W, len = S.len;
@@ -1289,6 +1310,17 @@ __device__ __forceinline__ void lane_walk_150(const AlignArgs &a, const uint64_t
     const uint64_t P0 = (live0 & ~valid0) | (valid0 & U0 & (V0 | NQ0));
     const uint64_t P1 = (live1 & ~valid1) | (valid1 & U1 & (V1 | NQ1));
     S.uoff = (uint32_t)(__popcll(valid0 & U0 & ~V0 & NP0 & ~NQ0 & ~NB0) + __popcll(valid1 & U1 & ~V1 & NP1 & ~NQ1 & ~NB1));
+    // windows with one mismatch whose k-mer the neighbour bits show present and
+    // specific (and, under --max-genomes, included): each is certain to be
+    // found off the walk.  Their number, and the lowest one (bits 8..)
+    uint32_t sure = 0;
+    if constexpr (SURE != 0 && NW == 1) {
+        if (has_nb && a.nb_spec && (!has_mg || mgk)) {
+            const uint64_t C0 = valid0 & U0 & ~V0 & NQ0, C1 = valid1 & U1 & ~V1 & NQ1;
+            sure = (uint32_t)(__popcll(C0) + __popcll(C1)) |
+                   ((C0 ? (uint32_t)__builtin_ctzll(C0) : 64u + (uint32_t)__builtin_ctzll(C1 | (1ull << 63))) << 8);
+        }
+    }
     const uint32_t hr_off = (uint32_t)(__popcll(valid0 & U0 & ~V0 & NB0) + __popcll(valid1 & U1 & ~V1 & NB1));
     const uint64_t walked0 = valid0 & ~U0, walked1 = valid1 & ~U1;
 #ifdef PA_STATS
@@ -1330,6 +1362,24 @@ __device__ __forceinline__ void lane_walk_150(const AlignArgs &a, const uint64_t
     S.hr = hr + hr_off;  // windows, repeats included (quirk 4)
     S.P[0] = P0;
     S.P[1] = P1;
+    // With cs > 0 such windows the probes find nsoff >= cs specific k-mers off
+    // the walk, and both ways to settle the read need nspec >= nsoff + max(m, 1)
+    // (k_align_lane: the bound's X >= cs, the two-genome decision's c = nsoff):
+    // with nspec < cs + max(m, 1) the read is walked again from one of them
+    // (or, on its second walk, given up) whatever the other windows hold, so
+    // only that one is probed
+    if constexpr (SURE == 2) {
+        S.uoff |= sure << 8;
+    } else if constexpr (SURE == 1 && NW == 1) {
+        const uint32_t cs = sure & 255u;
+        if (cs && nspec < cs + (uint32_t)(a.prm.m > 0 ? a.prm.m : 1)) {
+            const uint32_t w = sure >> 8;
+            S.P[0] = w < 64 ? 1ull << w : 0ull;
+            S.P[1] = w < 64 ? 0ull : 1ull << (w - 64);
+            S.uoff = kLaneSure;
+            return;
+        }
+    }
     // a read with very many unwalked windows is left to the wave kernel
     if ((uint32_t)(__popcll(P0) + __popcll(P1)) > a.lane_maxpend) {
         S.kind = LANE_HARD;
@@ -1355,6 +1405,7 @@ __device__ __forceinline__ void lane_walk_halves(const AlignArgs &a, const uint6
     const uint32_t len = S.len, W = S.W;
     S.nspec = S.nincl = S.hr = S.uoff = 0;
     S.P[2] = S.P[3] = 0;
+    uint32_t cs = 0, sw = 0;  // windows sure to be found off the walk (lane_walk_150), and the lowest
     // (one copy of the walk in a loop, not two inlined ones: the copies' loop
     // invariants were hoisted side by side and spilled)
 #pragma unroll 1
@@ -1373,16 +1424,26 @@ __device__ __forceinline__ void lane_walk_halves(const AlignArgs &a, const uint6
             H.anc = (uint64_t)(A + 128);  // (window 0 of the second half at A + 128; A >= 0: the first half checked it)
             H.acls = S.g;                 // (the first half's genome: a genome id < G)
         }
-        lane_walk_150<false, MG, 1>(a, row + 4 * h, H);
+        lane_walk_150<false, MG, 1, lane_sure(false, MG, 4, 1) ? 2 : 0>(a, row + 4 * h, H);
         if (h == 0) S.g = H.g;
         S.kind = H.kind;
-        S.nspec += H.nspec, S.nincl += H.nincl, S.hr += H.hr, S.uoff += H.uoff;
+        S.nspec += H.nspec, S.nincl += H.nincl, S.hr += H.hr, S.uoff += H.uoff & 255u;
+        if (H.kind == LANE_WALK && (H.uoff & 0xFF00u)) {  // the half's sure windows: their number, the read's lowest
+            if (!cs) sw = 128 * h + ((H.uoff >> 16) & 255u);
+            cs += (H.uoff >> 8) & 255u;
+        }
         if (h == 0) {
             S.P[0] = H.P[0], S.P[1] = H.P[1];
         } else {
             S.P[2] = H.P[0], S.P[3] = H.P[1];
         }
         if (S.kind != LANE_WALK || W <= 128) break;
+    }
+    // lane_walk_150's last step on the counts of both halves
+    if (S.kind == LANE_WALK && cs && S.nspec < cs + (uint32_t)(a.prm.m > 0 ? a.prm.m : 1)) {
+#pragma unroll
+        for (uint32_t q = 0; q < 4; q++) S.P[q] = (sw >> 6) == q ? 1ull << (sw & 63) : 0ull;
+        S.uoff = kLaneSure;
     }
 }
 
@@ -1781,7 +1842,7 @@ void k_align_lane(AlignArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const uint32_t G = a.G;
     const int lane = lane_id();
-    constexpr bool kSched = lane_sched(WIN_Q, MG, NM, NW);
+    constexpr bool kSched = lane_sched(WIN_Q, MG, NM, NW), kSure = lane_sure(WIN_Q, MG, NM, NW);
     const bool lds = G <= lane_lds_genome_cap(kSched);
     const size_t cnt_bytes = lds ? ((size_t)G * 8 + 15) / 16 * 16 : 0;
     uint32_t *first = (uint32_t *)smem;  // the smallest batch-local index of a unique read of g (first_key rank 0)
@@ -1992,7 +2053,19 @@ void k_align_lane(AlignArgs a) {
             // Under --max-genomes the filtered_hr_kmers count needs the set size
             // of every window found off the walk: only when every one is known
             // from the bits (a.mg_nb, nothing left to probe).
-            if (S.kind == LANE_WALK && S.nspec > 0 && (!MG || (a.mg_nb && !lane_any(S.P)))) {
+            // (A read marked kLaneSure cannot meet it -- X >= cs -- and its S.P
+            // is no longer the X of the bound; on its second walk it is given
+            // up here, as its probes would end.)
+            const bool sure = kSure && S.kind == LANE_WALK && (S.uoff & kLaneSure);
+            if (sure && attempt == 1) {
+                S.kind = LANE_HARD;
+                LANE_HARD_WHY(7);
+                LANE_HARD_WHY(17);
+#ifdef PA_STATS
+                atomicAdd(&a.dbg[29], 1ull);
+#endif
+            }
+            if (S.kind == LANE_WALK && !sure && S.nspec > 0 && (!MG || (a.mg_nb && !lane_any(S.P)))) {
                 const int64_t X = (int64_t)(lane_popc(S.P) + S.uoff);
                 const int64_t ns = (int64_t)S.nspec;
                 if (ns >= X + (a.prm.m > 0 ? a.prm.m : 1) && (a.prm.p < 0 || X - ns <= a.prm.p)) {
@@ -2010,7 +2083,23 @@ void k_align_lane(AlignArgs a) {
                 LANE_HARD_WHY(16);
             }
             lane_probe_wave<NM, NW, PA_TWO_WINQ || !WIN_Q>(a, LW, S, S.P, true);
-            if (S.kind == LANE_WALK) {
+            if (kSure && S.kind == LANE_WALK && (S.uoff & kLaneSure)) {  // (made again: not kept through the probes)
+                // the one window probed: its specific k-mer is the new anchor (not
+                // found -- the neighbour bits say it is -- : the wave kernel)
+                if (LW.cand[lane] != ~0ull) {
+                    S.kind = LANE_AGAIN;
+#ifdef PA_STATS
+                    atomicAdd(&a.dbg[15], 1ull);
+                    atomicAdd(&a.dbg[28], 1ull);
+#endif
+                } else {
+                    S.kind = LANE_HARD;
+                    LANE_HARD_WHY(7);
+                }
+#if defined(PA_STATS) || defined(PA_DISSECT)
+                if (a.dbg_mode == 12) S.kind = LANE_AMB;  // timing dissection: no second walk
+#endif
+            } else if (S.kind == LANE_WALK) {
                 const uint32_t fl = LW.flags[lane];
                 const uint32_t nsoff = fl >> 16;  // specific k-mers off the walk (windows)
                 // Specific k-mers of one other genome h off the walk, fewer than
