@@ -137,6 +137,10 @@ struct AlignArgs {
     const unsigned long long *rlist_count;
     unsigned long long *dbg;  // PA_STATS builds: [0] windows [1] probed [2] walk-resolved [3] anchors (wave
                               // kernel), [4..11] lane kernel: reads left to the wave kernel, by reason
+    // the assign pass (the lane kernels' AS instantiations, lane_assign): per read of the batch, written
+    // for the reads a lane kernel settles
+    uint8_t *as_type;
+    uint32_t *as_len, *as_g, *as_qf, *as_hr;
 };
 
 __device__ __forceinline__ uint64_t first_key(uint64_t read, uint32_t rank) { return (read << 20) | rank; }
@@ -825,6 +829,8 @@ struct KernelTimer {
 // nw: key words (2: 31 < k <= 63, 3: 63 < k <= 95 -- the 150-bp shape, no
 // reverse-strand path: reads without a seed go to the wave kernel).
 constexpr uint64_t kRcnbMinReads = 32768;  // seedless reads in a pass that make the reverse-complement bits worth it
+// AS: the assign pass's instantiations (lane_assign; a.as_* set).
+template <bool AS>
 pa_status launch_lane(const AlignArgs &a0, hipStream_t st, pa_index *prof = nullptr, bool long_reads = false,
                       int nw = 1) {
     const bool need_q = (a0.prm.flags & (F_MRQ | F_MKQ)) != 0;
@@ -834,18 +840,18 @@ pa_status launch_lane(const AlignArgs &a0, hipStream_t st, pa_index *prof = null
     AlignArgs a = a0;
     const size_t shm = lane_lds_bytes(a.G, nm4 ? 4 : 2, lane_sched(win_q, mg, nm4 ? 4 : 2, nw));
     auto kern = nw == 3
-                    ? (win_q ? (mg ? k_align_lane<true, true, true, 2, 3> : k_align_lane<true, true, false, 2, 3>)
-                       : need_q ? (mg ? k_align_lane<true, false, true, 2, 3> : k_align_lane<true, false, false, 2, 3>)
-                                : (mg ? k_align_lane<false, false, true, 2, 3> : k_align_lane<false, false, false, 2, 3>))
+                    ? (win_q ? (mg ? k_align_lane<true, true, true, 2, 3, AS> : k_align_lane<true, true, false, 2, 3, AS>)
+                       : need_q ? (mg ? k_align_lane<true, false, true, 2, 3, AS> : k_align_lane<true, false, false, 2, 3, AS>)
+                                : (mg ? k_align_lane<false, false, true, 2, 3, AS> : k_align_lane<false, false, false, 2, 3, AS>))
               : nw == 2
-                    ? (win_q ? (mg ? k_align_lane<true, true, true, 2, 2> : k_align_lane<true, true, false, 2, 2>)
-                       : need_q ? (mg ? k_align_lane<true, false, true, 2, 2> : k_align_lane<true, false, false, 2, 2>)
-                                : (mg ? k_align_lane<false, false, true, 2, 2> : k_align_lane<false, false, false, 2, 2>))
-              : nm4 ? (need_q ? (mg ? k_align_lane<true, false, true, 4> : k_align_lane<true, false, false, 4>)
-                              : (mg ? k_align_lane<false, false, true, 4> : k_align_lane<false, false, false, 4>))
-              : win_q ? (mg ? k_align_lane<true, true, true> : k_align_lane<true, true, false>)
-              : need_q ? (mg ? k_align_lane<true, false, true> : k_align_lane<true, false, false>)
-                       : (mg ? k_align_lane<false, false, true> : k_align_lane<false, false, false>);
+                    ? (win_q ? (mg ? k_align_lane<true, true, true, 2, 2, AS> : k_align_lane<true, true, false, 2, 2, AS>)
+                       : need_q ? (mg ? k_align_lane<true, false, true, 2, 2, AS> : k_align_lane<true, false, false, 2, 2, AS>)
+                                : (mg ? k_align_lane<false, false, true, 2, 2, AS> : k_align_lane<false, false, false, 2, 2, AS>))
+              : nm4 ? (need_q ? (mg ? k_align_lane<true, false, true, 4, 1, AS> : k_align_lane<true, false, false, 4, 1, AS>)
+                              : (mg ? k_align_lane<false, false, true, 4, 1, AS> : k_align_lane<false, false, false, 4, 1, AS>))
+              : win_q ? (mg ? k_align_lane<true, true, true, 2, 1, AS> : k_align_lane<true, true, false, 2, 1, AS>)
+              : need_q ? (mg ? k_align_lane<true, false, true, 2, 1, AS> : k_align_lane<true, false, false, 2, 1, AS>)
+                       : (mg ? k_align_lane<false, false, true, 2, 1, AS> : k_align_lane<false, false, false, 2, 1, AS>);
     if (shm > 64 * 1024) PA_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     int per_cu = 0, dev = 0, cus = 256;
     PA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, shm));
@@ -906,9 +912,9 @@ pa_status launch_lane(const AlignArgs &a0, hipStream_t st, pa_index *prof = null
                 hipLaunchKernelGGL(k_rc_seeds, dim3(sgrid), dim3(kBlock), 0, st, b);
                 PA_HIP(hipGetLastError());
             }
-            auto rc = win_q ? (mg ? k_align_lane_rc<true, true, true> : k_align_lane_rc<true, true, false>)
-                    : need_q ? (mg ? k_align_lane_rc<true, false, true> : k_align_lane_rc<true, false, false>)
-                             : (mg ? k_align_lane_rc<false, false, true> : k_align_lane_rc<false, false, false>);
+            auto rc = win_q ? (mg ? k_align_lane_rc<true, true, true, AS> : k_align_lane_rc<true, true, false, AS>)
+                    : need_q ? (mg ? k_align_lane_rc<true, false, true, AS> : k_align_lane_rc<true, false, false, AS>)
+                             : (mg ? k_align_lane_rc<false, false, true, AS> : k_align_lane_rc<false, false, false, AS>);
             int rc_cu = 0;
             PA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&rc_cu, rc, kBlock, 0));
             const unsigned rgrid = (unsigned)std::max<uint64_t>(
@@ -919,15 +925,15 @@ pa_status launch_lane(const AlignArgs &a0, hipStream_t st, pa_index *prof = null
             b.queue_na = a.queue_na2;
             b.queue_na_count = a.queue_na2_count;
         }
-        auto na = nw == 3 ? (win_q ? (mg ? k_align_lane_naw<true, true, true, 3> : k_align_lane_naw<true, true, false, 3>)
-                             : need_q ? (mg ? k_align_lane_naw<true, false, true, 3> : k_align_lane_naw<true, false, false, 3>)
-                                      : (mg ? k_align_lane_naw<false, false, true, 3> : k_align_lane_naw<false, false, false, 3>))
-                : nw == 2 ? (win_q ? (mg ? k_align_lane_naw<true, true, true, 2> : k_align_lane_naw<true, true, false, 2>)
-                             : need_q ? (mg ? k_align_lane_naw<true, false, true, 2> : k_align_lane_naw<true, false, false, 2>)
-                                      : (mg ? k_align_lane_naw<false, false, true, 2> : k_align_lane_naw<false, false, false, 2>))
-                : win_q ? (mg ? k_align_lane_na<true, true, true> : k_align_lane_na<true, true, false>)
-                : need_q ? (mg ? k_align_lane_na<true, false, true> : k_align_lane_na<true, false, false>)
-                         : (mg ? k_align_lane_na<false, false, true> : k_align_lane_na<false, false, false>);
+        auto na = nw == 3 ? (win_q ? (mg ? k_align_lane_naw<true, true, true, 3, AS> : k_align_lane_naw<true, true, false, 3, AS>)
+                             : need_q ? (mg ? k_align_lane_naw<true, false, true, 3, AS> : k_align_lane_naw<true, false, false, 3, AS>)
+                                      : (mg ? k_align_lane_naw<false, false, true, 3, AS> : k_align_lane_naw<false, false, false, 3, AS>))
+                : nw == 2 ? (win_q ? (mg ? k_align_lane_naw<true, true, true, 2, AS> : k_align_lane_naw<true, true, false, 2, AS>)
+                             : need_q ? (mg ? k_align_lane_naw<true, false, true, 2, AS> : k_align_lane_naw<true, false, false, 2, AS>)
+                                      : (mg ? k_align_lane_naw<false, false, true, 2, AS> : k_align_lane_naw<false, false, false, 2, AS>))
+                : win_q ? (mg ? k_align_lane_na<true, true, true, AS> : k_align_lane_na<true, true, false, AS>)
+                : need_q ? (mg ? k_align_lane_na<true, false, true, AS> : k_align_lane_na<true, false, false, AS>)
+                         : (mg ? k_align_lane_na<false, false, true, AS> : k_align_lane_na<false, false, false, AS>);
         int na_cu = 0;
         PA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&na_cu, na, kBlock, 0));
         const unsigned ngrid = (unsigned)std::max<uint64_t>(
@@ -1198,11 +1204,18 @@ pa_status effective_params(const pa_reads *r, const DevParams &p, DevParams &out
     return PA_OK;
 }
 
-pa_status align(pa_index *idx, const pa_reads *r, const DevParams &p_in, uint64_t base, pa_result *acc,
-                hipStream_t st) {
+// One pass over a batch.  as == nullptr: the counter pass into acc (pa_align).
+// as: the assign pass's first half (assign_classify) -- the lane kernels write
+// the reads they settle into as's arrays and their counters into as->scratch,
+// the wave kernel is not launched, and the exact kernel in detail mode takes
+// what the lane chain queued (queue_hard; *queued = true) or, without a lane
+// path, every read.
+static pa_status align_pass(pa_index *idx, const pa_reads *r, const DevParams &p_in, uint64_t base, pa_result *acc,
+                            const AssignBufs *as, bool *queued, hipStream_t st) {
     if (r->n == 0) return PA_OK;
     if (r->n >= 0xFFFFFFFFull) {  // (read indices of a batch are 32-bit in the queues and lane kernels)
-        set_error("pa_align: a batch holds at most 2^32 - 2 reads (split it; read_index_base keeps the order)");
+        set_error(std::string(as ? "pa_align_reads" : "pa_align") +
+                  ": a batch holds at most 2^32 - 2 reads (split it; read_index_base keeps the order)");
         return PA_EUNSUPPORTED;
     }
     PA_TRY(index_note_reads(idx, r->n, st));  // (the neighbour bits, once enough reads came)
@@ -1211,10 +1224,17 @@ pa_status align(pa_index *idx, const pa_reads *r, const DevParams &p_in, uint64_
     PA_TRY(effective_params(r, p_in, p, st));
     AlignArgs a = make_args(idx, r, p, base);
     const uint32_t G = idx->n_genomes;
-    a.stats = (unsigned long long *)acc->sum_block;
-    a.uniq = (unsigned long long *)acc->sum_block + 6;
+    a.stats = (unsigned long long *)(as ? as->scratch : acc->sum_block);
+    a.uniq = a.stats + 6;
     a.amb = a.uniq + G;
-    a.first = (unsigned long long *)acc->min_block;
+    a.first = as ? a.amb + G : (unsigned long long *)acc->min_block;
+    if (as) {
+        a.as_type = as->type;
+        a.as_len = as->len;
+        a.as_g = as->g;
+        a.as_qf = as->qf;
+        a.as_hr = as->hr;
+    }
     a.queue = idx->queue;
     a.qcount = (unsigned long long *)idx->counters;
     a.deferred_total = (unsigned long long *)idx->counters + 1;
@@ -1227,12 +1247,20 @@ pa_status align(pa_index *idx, const pa_reads *r, const DevParams &p_in, uint64_
     unsigned egrid = 0;
     PA_TRY(prepare_exact(idx, r, x, egrid));
     x.a = a;
-    x.detail = 0;
+    x.detail = as ? 1 : 0;
+    if (as) {
+        x.type_out = as->type;
+        x.qf_out = as->qf;
+        x.hr_out = as->hr;
+        x.len_out = as->len;
+    }
     const bool fast_ok = idx->k > 0 && idx->nw <= 4 && idx->n_kmers > 0;  // (k <= 127: the wave kernel's keys)
     // the lane kernel first (single-word keys on a tiled index); PA_NO_LANE=1 skips it
     const char *no_lane = std::getenv("PA_NO_LANE");
-    const bool lane_ok = fast_ok && idx->nw <= 3 && a.tile_n > 0 && a.tile_lw && !(no_lane && no_lane[0] == '1');
-    if (fast_ok) {
+    const bool lane_ok = fast_ok && idx->nw <= 3 && a.tile_n > 0 && a.tile_lw && !(no_lane && no_lane[0] == '1') &&
+                         (!as || as->lane);
+    if (queued) *queued = as && lane_ok;
+    if (as ? lane_ok : fast_ok) {
         const uint32_t wmax = r->max_len >= idx->k ? (uint32_t)(r->max_len - idx->k + 1) : 0;
         const int wpl = wmax <= 64 ? 1 : wmax <= 128 ? 2 : 4;  // longer reads are deferred by WPL=4
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1347,11 +1375,16 @@ pa_status align(pa_index *idx, const pa_reads *r, const DevParams &p_in, uint64_
             // at k = 31 went whole to the wave kernel, 0.15 G reads/s)
             const bool long_reads = r->max_len > (uint32_t)kLaneMaxLen ||
                                     (r->max_len >= idx->k && r->max_len - idx->k + 1 > (uint32_t)kLaneMaxW);
-            PA_TRY(launch_lane(a, st, idx, long_reads, idx->nw));
+            PA_TRY(as ? launch_lane<true>(a, st, idx, long_reads, idx->nw)
+                      : launch_lane<false>(a, st, idx, long_reads, idx->nw));
             a.rlist = idx->queue_hard;
             a.rlist_count = a.queue_hard_count;
         }
-        {
+        if (as) {  // the lane chain's remainder is the exact kernel's queue
+            a.queue = idx->queue_hard;
+            a.qcount = a.queue_hard_count;
+            a.deferred_total = nullptr;
+        } else {
             KernelTimer kt(idx, st, PA_PROF_WAVE);
             PA_TRY(idx->nw == 1   ? launch_fast_wpl<1>(a, wpl, st)
                    : idx->nw == 2 ? launch_fast_wpl<2>(a, wpl, st)
@@ -1389,6 +1422,43 @@ pa_status align(pa_index *idx, const pa_reads *r, const DevParams &p_in, uint64_
             d[29]);
     fprintf(stderr, "[pa_stats] lane seeds: anchor ranked among stretches %llu, second seed round %llu\n", d[30], d[31]);
 #endif
+    return PA_OK;
+}
+
+pa_status align(pa_index *idx, const pa_reads *r, const DevParams &p, uint64_t base, pa_result *acc,
+                hipStream_t st) {
+    return align_pass(idx, r, p, base, acc, nullptr, nullptr, st);
+}
+
+pa_status assign_classify(pa_index *idx, const pa_reads *r, const DevParams &p, const AssignBufs &as, bool *queued,
+                          hipStream_t st) {
+    return align_pass(idx, r, p, 0, nullptr, &as, queued, st);
+}
+
+// The assign pass's second half: the lists of the reads the exact kernel
+// classified -- the queue assign_classify left (queued), or every read.
+pa_status assign_lists(pa_index *idx, const pa_reads *r, const DevParams &p_in, const AssignBufs &as, bool queued,
+                       const uint64_t *d_off, uint32_t *d_lists, hipStream_t st) {
+    if (r->n == 0) return PA_OK;
+    DevParams p;
+    PA_TRY(effective_params(r, p_in, p, st));
+    ExactArgs x{};
+    unsigned egrid = 0;
+    PA_TRY(prepare_exact(idx, r, x, egrid));
+    x.a = make_args(idx, r, p, 0);
+    x.a.queue = idx->queue_hard;
+    x.a.qcount = (unsigned long long *)idx->counters + 3;
+    x.use_queue = queued ? 1 : 0;
+    x.type_out = as.type;
+    x.qf_out = as.qf;
+    x.hr_out = as.hr;
+    x.len_out = as.len;
+    x.detail = 2;
+    x.list_off = d_off;
+    x.lists = d_lists;
+    KernelTimer kt(idx, st, PA_PROF_EXACT);
+    launch_exact_nw(idx->nw, x, egrid, st);
+    PA_HIP(hipGetLastError());
     return PA_OK;
 }
 

@@ -650,6 +650,20 @@ pa_status pa_align_detail(const pa_index *idx, const pa_reads *reads, const pa_p
                             list_off, lists, list_cap, list_total, as_stream(stream));
 }
 
+pa_status pa_align_reads(const pa_index *idx, const pa_reads *reads, const pa_params *params, uint8_t *read_type,
+                         uint32_t *filtered_kmers, uint32_t *redundant_kmers, uint64_t *list_off, uint32_t *lists,
+                         uint64_t list_cap, uint64_t *list_total, void *stream) {
+    PA_CHECK(idx && reads && read_type && list_off && list_total, PA_EINVAL, "NULL argument");
+    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
+    pa::DevParams dp;
+    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    PA_HIP(hipSetDevice(idx->device));
+    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    return pa::align_reads(const_cast<pa_index *>(idx), reads, dp, read_type, filtered_kmers, redundant_kmers,
+                           list_off, lists, list_cap, list_total, as_stream(stream));
+}
+
 pa_status pa_align_batch(const pa_index *idx, const uint8_t *seq, const uint8_t *qual, const uint64_t *read_off,
                          uint64_t n_reads, uint64_t read_index_base, const pa_params *params, pa_stats *stats,
                          uint64_t *unique_reads, uint64_t *ambiguous_reads, uint64_t *first_key, void *stream) {

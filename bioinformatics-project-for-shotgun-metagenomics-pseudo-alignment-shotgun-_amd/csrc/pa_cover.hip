@@ -449,11 +449,6 @@ void launch_place(const PlaceArgs &a, unsigned grid, hipStream_t st) {
     hipLaunchKernelGGL(k_place<NW>, dim3(grid), dim3(kBlock), 0, st, a);
 }
 
-__global__ void k_widen_len(const uint32_t *__restrict__ len, uint64_t n, uint64_t *out) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= n) out[i] = i < n ? len[i] : 0;
-}
-
 // ---- depth and summaries ---------------------------------------------------------
 
 // One block per (genome, category): positions with depth >= minc, and the depths' sum.
@@ -582,48 +577,29 @@ pa_status coverage_place(pa_index *idx, const pa_reads *r, const DevParams &p, p
     if (list_total) *list_total = 0;
     PA_TRY(index_prepare_coverage(idx, st));
     if (n == 0) return PA_OK;
-    uint8_t *d_type = nullptr;
-    uint32_t *d_qf = nullptr, *d_hr = nullptr, *d_len = nullptr, *d_lists = nullptr;
-    uint64_t *d_len64 = nullptr, *d_off = nullptr;
     int64_t *d_starts = nullptr, *d_ws = nullptr;
     unsigned long long *d_err = nullptr;
-    void *tmp = nullptr;
+    AssignDev as;
     auto cleanup = [&] {
         (void)hipStreamSynchronize(st);
-        pa::dev_free(d_type); pa::dev_free(d_qf); pa::dev_free(d_hr); pa::dev_free(d_len); pa::dev_free(d_lists);
-        pa::dev_free(d_len64); pa::dev_free(d_off); pa::dev_free(d_starts); pa::dev_free(d_ws); pa::dev_free(d_err);
-        pa::dev_free(tmp);
+        assign_free(as);
+        pa::dev_free(d_starts); pa::dev_free(d_ws); pa::dev_free(d_err);
     };
-    C_HIP(pa::dev_malloc(&d_type, n));
-    C_HIP(pa::dev_malloc(&d_qf, n * 4));
-    C_HIP(pa::dev_malloc(&d_hr, n * 4));
-    C_HIP(pa::dev_malloc(&d_len, n * 4));
-    C_HIP(pa::dev_malloc(&d_len64, (n + 1) * 8));
-    C_HIP(pa::dev_malloc(&d_off, (n + 1) * 8));
+    const bool want_lists = lists || starts;
+    // classification, list offsets and lists: the assign pass, left on the device
+    // (no lists for the *list_total query, or when the caller's capacity is short)
+    pa_status rc = assign_pass_device(idx, r, p, acc ? ~0ull : (want_lists ? list_cap : 0), as, st);
+    if (rc != PA_OK) return rc;
+    uint8_t *d_type = as.type;
+    uint64_t *d_off = as.off;
+    uint32_t *d_lists = as.lists;
+    const uint64_t total = as.total;
     C_HIP(pa::dev_malloc(&d_err, 16));
     C_HIP(hipMemsetAsync(d_err, 0, 16, st));
-    pa_status rc = detail_pass_device(idx, r, p, d_type, d_qf, d_hr, d_len, nullptr, nullptr, st);
-    if (rc != PA_OK) {
-        cleanup();
-        return rc;
-    }
-    // list offsets: a device scan of the list lengths
-    hipLaunchKernelGGL(k_widen_len, dim3((unsigned)((n + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_len, n,
-                       d_len64);
-    C_HIP(hipGetLastError());
-    size_t tmp_bytes = 0;
-    C_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_len64, d_off, (uint64_t)0, (size_t)(n + 1),
-                                  rocprim::plus<uint64_t>(), st));
-    C_HIP(pa::dev_malloc(&tmp, std::max<size_t>(tmp_bytes, 16)));
-    C_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, d_len64, d_off, (uint64_t)0, (size_t)(n + 1),
-                                  rocprim::plus<uint64_t>(), st));
-    uint64_t total = 0;
-    C_HIP(hipMemcpyAsync(&total, d_off + n, 8, hipMemcpyDeviceToHost, st));
     if (type) C_HIP(hipMemcpyAsync(type, d_type, n, hipMemcpyDeviceToHost, st));
     if (list_off) C_HIP(hipMemcpyAsync(list_off, d_off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
     C_HIP(hipStreamSynchronize(st));
     if (list_total) *list_total = total;
-    const bool want_lists = lists || starts;
     if (!acc && !want_lists) {  // (the query for *list_total)
         cleanup();
         return PA_OK;
@@ -637,12 +613,6 @@ pa_status coverage_place(pa_index *idx, const pa_reads *r, const DevParams &p, p
         cleanup();
         if (acc) acc->reads_added += n;
         return PA_OK;
-    }
-    C_HIP(pa::dev_malloc(&d_lists, total * 4));
-    rc = detail_pass_device(idx, r, p, d_type, d_qf, d_hr, d_len, d_off, d_lists, st);
-    if (rc != PA_OK) {
-        cleanup();
-        return rc;
     }
     if (starts) C_HIP(pa::dev_malloc(&d_starts, total * 8));
     const uint32_t wmax = r->max_len >= (uint64_t)idx->k ? (uint32_t)(r->max_len - idx->k + 1) : 1;

@@ -261,6 +261,41 @@ pa_status align_detail(pa_index *idx, const pa_reads *r, const DevParams &p, uin
 pa_status detail_pass_device(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *d_type, uint32_t *d_qf,
                              uint32_t *d_hr, uint32_t *d_len, const uint64_t *d_off, uint32_t *d_lists,
                              hipStream_t st);
+// The assign pass (pa_assign.hip): pa_align_detail's per-read outputs, made by
+// the lane kernels for the reads they settle (one store per read at their
+// commit) and by the exact kernel, in detail mode over the lane chain's queue,
+// for the rest.  Device arrays per read of the batch:
+struct AssignBufs {
+    uint8_t *type;      // PA_*; kAssignUnset until a kernel settles the read
+    uint32_t *qf, *hr;  // filtered_kmers, redundant_kmers
+    uint32_t *len;      // list length
+    uint32_t *g;        // a lane-settled unique read's genome (kAssignNoGenome: none, or the exact kernel's read)
+    void *scratch;      // (6 + 3 G) * 8 bytes: the lane kernels' counters go here, never to a caller's result
+    bool lane;          // false: every read to the exact kernel (PA_ASSIGN=0)
+};
+constexpr uint8_t kAssignUnset = 0xFF;
+constexpr uint32_t kAssignNoGenome = 0xFFFFFFFFu;
+// the two halves in pa_align.hip (the kernels' file): types, counts and list lengths; then the exact kernel's lists
+pa_status assign_classify(pa_index *idx, const pa_reads *r, const DevParams &p, const AssignBufs &as, bool *queued,
+                          hipStream_t st);
+pa_status assign_lists(pa_index *idx, const pa_reads *r, const DevParams &p, const AssignBufs &as, bool queued,
+                       const uint64_t *d_off, uint32_t *d_lists, hipStream_t st);
+// The whole pass with everything left on the device (detail_pass_device's
+// sibling): type, qf, hr, len [n], off [n + 1] and total always; lists [total]
+// when total <= list_cap (else null: the caller reports PA_EINVAL or only
+// wanted the total).  Every read covered, or PA_EINTERNAL.  Free with assign_free.
+struct AssignDev {
+    uint8_t *type = nullptr;
+    uint32_t *qf = nullptr, *hr = nullptr, *len = nullptr, *lists = nullptr;
+    uint64_t *off = nullptr;
+    uint64_t total = 0;
+    void *block = nullptr;  // (the per-read arrays' allocation)
+};
+pa_status assign_pass_device(pa_index *idx, const pa_reads *r, const DevParams &p, uint64_t list_cap, AssignDev &out,
+                             hipStream_t st);
+void assign_free(AssignDev &d);
+pa_status align_reads(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *type, uint32_t *qf, uint32_t *hr,
+                      uint64_t *list_off, uint32_t *lists, uint64_t list_cap, uint64_t *list_total, hipStream_t st);
 // coverage (pa_cover.hip)
 pa_status index_prepare_coverage(pa_index *idx, hipStream_t st);
 void index_release_coverage(pa_index *idx);

@@ -1832,7 +1832,25 @@ __device__ __forceinline__ void lane_probe_wave(const AlignArgs &a, LaneWave<NM>
 #ifndef PA_LANE_WAVES_W
 #define PA_LANE_WAVES_W 3  // two- and three-word keys (~168 VGPRs; at 4 they spill 84-180 B/lane)
 #endif
-template <bool NEED_Q, bool WIN_Q, bool MG, int NM = 2, int NW = 1>
+// The assign pass (pa_assign.hip; AS instantiations of the lane kernels): a
+// settled read's per-read result, written where the read is committed -- by
+// the one kernel that settles it, once (a read handed on is written by the
+// kernel that takes it, a read walked again at its second commit).  The list
+// of a lane-settled read is [g] (UNIQUE) or empty; plain stores by the read's
+// own lane, no atomics.
+__device__ __forceinline__ void lane_assign(const AlignArgs &a, uint32_t r, int kind, uint32_t g, uint32_t qf,
+                                            uint32_t hr) {
+    a.as_type[r] = kind == LANE_UNIQUE ? (uint8_t)PA_UNIQUELY_MAPPED
+                 : kind == LANE_AMB    ? (uint8_t)PA_AMBIGUOUSLY_MAPPED
+                 : kind == LANE_DROP   ? (uint8_t)PA_DROPPED
+                                       : (uint8_t)PA_UNMAPPED;
+    a.as_len[r] = kind == LANE_UNIQUE ? 1u : 0u;
+    if (kind == LANE_UNIQUE) a.as_g[r] = g;
+    a.as_qf[r] = qf;
+    a.as_hr[r] = hr;
+}
+
+template <bool NEED_Q, bool WIN_Q, bool MG, int NM = 2, int NW = 1, bool AS = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(
     NM == 4 ? PA_LANE_WAVES_LONG
             : (NW >= 2 ? PA_LANE_WAVES_W : (WIN_Q ? PA_LANE_WAVES_Q : (MG ? PA_LANE_WAVES_MG : PA_LANE_WAVES))))))
@@ -2169,6 +2187,10 @@ void k_align_lane(AlignArgs a) {
             }
         }
         if (S.kind == LANE_WALK) S.kind = LANE_HARD;  // (a second re-anchoring is not attempted)
+        if constexpr (AS) {  // (a lane without a read holds none of these kinds)
+            if (S.kind == LANE_UNIQUE || S.kind == LANE_AMB || S.kind == LANE_UNMAPPED || S.kind == LANE_DROP)
+                lane_assign(a, r, S.kind, S.g, WIN_Q ? S.qf : 0u, MG ? S.hr : 0u);
+        }
         const bool hard = S.kind == LANE_HARD;
         const uint64_t hb = __ballot(hard);
         if (hb) {  // one queue allocation per wave
@@ -2601,7 +2623,7 @@ __device__ __forceinline__ void na_probe_rest(const AlignArgs &a, const uint64_t
 #ifndef PA_NA_WAVES
 #define PA_NA_WAVES 4  // (c2mix: 1.31 vs 1.26 G reads/s at 3, 28 B/lane of scratch)
 #endif
-template <bool NEED_Q, bool WIN_Q, bool MG>
+template <bool NEED_Q, bool WIN_Q, bool MG, bool AS = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PA_NA_WAVES))) void k_align_lane_na(AlignArgs a) {
     __shared__ uint64_t rows[kBlock][kLaneWords + 1];
     __shared__ uint4 hcarry[4][kBlock];  // per lane: the last Bloom group's last sixteen 15-mer orders
@@ -2670,6 +2692,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PA_NA_WA
             if (!spec) {
                 hr_sum += hr;
                 qf_sum += S.qf;
+                if constexpr (AS) lane_assign(a, r, S.kind, 0u, WIN_Q ? S.qf : 0u, MG ? hr : 0u);
             }
         }
         const bool hard = S.kind == LANE_HARD;
@@ -2702,7 +2725,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PA_NA_WA
 // bloom_word2 / bloom_word3), then the table for the few it lets through;
 // nothing found: UNMAPPED, only multi-genome k-mers: AMBIGUOUS with an empty
 // list, a specific one: the wave kernel (src/kmer.py:410-461).
-template <bool NEED_Q, bool WIN_Q, bool MG, int NW>
+template <bool NEED_Q, bool WIN_Q, bool MG, int NW, bool AS = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PA_NA_WAVES))) void k_align_lane_naw(AlignArgs a) {
     static_assert(NW == 2 || NW == 3, "multi-word keys");
     __shared__ uint64_t rows[kBlock][kLaneWords + 1];
@@ -2792,6 +2815,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PA_NA_WA
             if (!spec) {
                 hr_sum += hr;
                 qf_sum += S.qf;
+                if constexpr (AS) lane_assign(a, r, S.kind, 0u, WIN_Q ? S.qf : 0u, MG ? hr : 0u);
             }
         }
         const bool hard = S.kind == LANE_HARD;
@@ -2943,7 +2967,7 @@ __global__ __launch_bounds__(kBlock) void k_rc_seeds(AlignArgs a) {
 // probes its read's remaining windows (na_probe_rest) and settles it as
 // k_align_lane_na does.
 constexpr int kRcGroups = kLaneMaxW / 8;  // Bloom groups of 8 windows per read
-template <bool NEED_Q, bool WIN_Q, bool MG>
+template <bool NEED_Q, bool WIN_Q, bool MG, bool AS = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PA_NA_WAVES))) void k_align_lane_rc(AlignArgs a) {
     __shared__ uint64_t rows[kBlock][kLaneWords + 1];
     __shared__ uint32_t glist[kWaves][64 * kRcGroups];      // (lane << 16) | (group << 8) | windows of the group
@@ -3025,6 +3049,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PA_NA_WA
             if (!spec) {
                 hr_sum += hr;
                 qf_sum += S.qf;
+                if constexpr (AS) lane_assign(a, r, S.kind, 0u, WIN_Q ? S.qf : 0u, MG ? hr : 0u);
             }
         }
         const bool hard = S.kind == LANE_HARD;

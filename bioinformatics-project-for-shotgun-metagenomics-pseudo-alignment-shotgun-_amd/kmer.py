@@ -10,7 +10,8 @@ attributes, return values and exceptions.  What changes is where the work runs:
   HBM and classifies all of them in one kernel pass (``pa_align``,
   src/kmer.py:482-620); only per-genome counters and filter statistics come
   back.  ``PseudoAlignment.reads`` (per-read mapping types and genome lists)
-  is materialised on first access by the per-read kernel (``pa_align_detail``).
+  is materialised on first access by the assign pass (``pa_align_reads``: the
+  lane kernels write the reads they settle, the per-read kernel the rest).
 * ``KmerReference.kmers`` -- positions included -- is an introspection view
   built on the host on first access; nothing on the align path reads it.
   ``KmerReference.get_summary`` (dumpref) is made on the device instead
@@ -50,6 +51,20 @@ IGNORE_AMBIGUOUS_THRESHOLD = 0
 M_THRESHOLD = 0
 _NO_KEY = int(N.NO_FIRST_KEY)
 _DROPPED = 0  # PA_DROPPED
+
+# --assignments: one line per read, read id <TAB> mapping <TAB> genome identifiers joined by ","
+ASSIGNMENTS_HEADER = "#read\tmapping\tgenomes\n"
+_ASSIGNMENT_WORDS = {0: "filtered", 1: "unmapped", 2: "unique", 3: "ambiguous"}  # PA_DROPPED .. PA_AMBIGUOUSLY_MAPPED
+
+
+def assignment_line(read_id: str, mapping_type: int, genomes: Sequence[str]) -> str:
+    """A line of the assignments file.  ``mapping_type``: a PA_* code (a
+    ReadMappingType's value, or 0 for a read dropped by --min-read-quality);
+    ``genomes``: genomes_mapped_to in list order (a p-demoted list repeats its
+    first genome), written only for unique and ambiguous reads."""
+    word = _ASSIGNMENT_WORDS[int(mapping_type)]
+    listed = ",".join(genomes) if int(mapping_type) >= 2 else ""
+    return f"{read_id}\t{word}\t{listed}\n"
 
 
 class NotValidatingUniqueMapping(Exception):
@@ -805,7 +820,7 @@ class PseudoAlignment:
             if b.entries is None:
                 b.load()
                 reads = N.Reads.upload(b.seq, b.qual, b.off, device=ref.index.device)
-                types, _, _, loff, lists = N.align_detail(ref.index, reads, b.params)
+                types, _, _, loff, lists = N.align_reads(ref.index, reads, b.params)
                 reads.close()
                 names = [g.identifier for g in ref.genomes]
                 ent = []
@@ -819,6 +834,34 @@ class PseudoAlignment:
             items.extend(b.entries)
         items.sort(key=lambda x: x[0])
         return {rid: e for _, rid, e in items}
+
+    def write_assignments(self, fh) -> None:
+        """Read -> genome as text: the header ``#read<TAB>mapping<TAB>genomes``, then one
+        line per read in the order the reads were added (assignment_line).
+        Reads dropped by --min-read-quality are written as ``filtered``, so a
+        FASTQ file gives as many lines as it has records.  Written batch by
+        batch from the device's per-read arrays; the ``reads`` dict is not built."""
+        ref = self.kmer_reference
+        names = [g.identifier for g in ref.genomes]
+        fh.write(ASSIGNMENTS_HEADER)
+        parts: List[Tuple[int, Any]] = [(b.base, b) for b in self._batches] + [(i, (rid, e)) for i, rid, e in self._host]
+        parts.sort(key=lambda x: x[0])
+        for _, part in parts:
+            if isinstance(part, tuple):  # a read of add_read()
+                rid, e = part
+                fh.write(assignment_line(rid, int(e["mapping_type"].value), e["genomes_mapped_to"]))
+                continue
+            b = part
+            b.load()
+            if b.all_dropped:
+                fh.writelines(assignment_line(rid, _DROPPED, ()) for rid in b.ids)
+                continue
+            reads = N.Reads.upload(b.seq, b.qual, b.off, device=ref.index.device)
+            types, _, _, loff, lists = N.align_reads(ref.index, reads, b.params)
+            reads.close()
+            loff = loff.astype(np.int64)
+            fh.writelines(assignment_line(rid, int(types[i]), [names[int(g)] for g in lists[loff[i]:loff[i + 1]]])
+                          for i, rid in enumerate(b.ids))
 
     def get_summary(self) -> Dict[str, Dict[str, Union[int, Dict[str, int]]]]:
         stats = self._gpu_stats.astype(np.int64)

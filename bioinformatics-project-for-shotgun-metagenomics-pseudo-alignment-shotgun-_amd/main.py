@@ -5,6 +5,7 @@
                     [--min-read-quality Q] [--min-kmer-quality QK] [--max-genomes MG]
                     [--filter-similar [--similarity-threshold T]]
                     [--coverage [--genomes a,b,c] [--min-coverage N] [--full-coverage]]
+                    [--assignments FILE]
 
 Same tasks (reference | dumpref | align | dumpalign), flags, flag-combination
 checks, default coercions and error exits as src/main.py:61-402:
@@ -54,6 +55,17 @@ def _has_coverage_flag(argv: List[str]) -> bool:
     return False
 
 
+def _has_assignments_flag(argv: List[str]) -> bool:
+    """--assignments on the command line, in any spelling argparse accepts
+    (`--assignments X`, `--assignments=X`, an unambiguous prefix; a prefix
+    shared with another flag counts too, which only costs the early prefetch)."""
+    for a in argv:
+        name = a.split("=", 1)[0]
+        if len(name) > 2 and name.startswith("--") and "--assignments".startswith(name):
+            return True
+    return False
+
+
 def _early_reads_path(argv: List[str]) -> Optional[str]:
     """The --reads file of a `-t dumpalign` command line, read off argv before
     argparse and the heavy imports (every spelling argparse accepts: `-t X`,
@@ -82,6 +94,8 @@ def _early_reads_path(argv: List[str]) -> Optional[str]:
     if task != "dumpalign" or not reads or not reads.endswith(_FQ_PLAIN_EXT):
         return None
     if _has_coverage_flag(argv):  # (a coverage job parses the reads on the host)
+        return None
+    if _has_assignments_flag(argv):  # (so does a job that writes every read's assignment)
         return None
     if os.environ.get("PA_GPUS", "1") not in ("", "0", "1"):  # (read-sharded over GPUs: no whole-file prefetch)
         return None
@@ -182,6 +196,9 @@ def parse_arguments(args: Optional[List[str]] = None) -> argparse.Namespace:
     parser.add_argument("--min-coverage", type=int, default=None,
                         help="reads a position needs to count as covered (default: 1)")
     parser.add_argument("--full-coverage", action="store_true", help="also print the depth at every position")
+    # not in the reference: read -> genome as text, dumpalign with --reads
+    parser.add_argument("--assignments", default=None, metavar="FILE",
+                        help="write one line per read (id, mapping, genomes) to FILE")
     return parser.parse_args(args)
 
 
@@ -256,7 +273,7 @@ def _prefetch_reads(reads_file: str):
 def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: str, m: int, p: int,
                                     min_read_quality, min_kmer_quality, max_genomes,
                                     prefetch=None, per_read: bool = False,
-                                    coverage: bool = False) -> PseudoAlignment:
+                                    coverage: bool = False, assignments: bool = False) -> PseudoAlignment:
     # the FASTQ file goes straight to the device (parsed there, aligned in
     # windows); a file outside that subset of the grammar is parsed the exact
     # way (FASTAQFile), which also raises the reference's errors.  per_read
@@ -268,7 +285,8 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
     # coverage: the reads are parsed on the host and aligned on one device (align_reads_from_file
     # then takes its exact path: the placements need the read columns)
     alignment = PseudoAlignment(kmer_reference, coverage=True) if coverage else PseudoAlignment(kmer_reference)
-    if per_read:
+    # assignments: the host parse too -- every read's line needs its id and the read columns
+    if per_read or assignments:
         alignment.align_reads_from_container(FASTAQFile(reads_file).container, m, p, min_read_quality,
                                              min_kmer_quality, max_genomes)
     else:
@@ -305,6 +323,10 @@ def _check_task(args: argparse.Namespace) -> None:
             sys.exit("Error: --coverage is only allowed for task 'dumpalign' with --reads.")
         if args.min_coverage is not None and args.min_coverage < 1:
             sys.exit("Error: --min-coverage must be at least 1.")
+    if args.assignments is not None:
+        if args.task != "dumpalign" or not args.reads:
+            sys.exit("Error: --assignments is only allowed for task 'dumpalign' with --reads.")
+        validate_file_writable(args.assignments, "Assignments output")
     if args.task == "reference":
         if extra:
             sys.exit("Error: For task 'reference', only -g, -k, -r, --filter-similar, and --similarity-threshold "
@@ -363,6 +385,9 @@ def _print_alignment(alignment: PseudoAlignment, args: argparse.Namespace) -> No
         genomes = None if args.genomes is None else [x for x in args.genomes.split(",") if x]
         out.update(alignment.get_coverage(genomes, args.min_coverage or 1, args.full_coverage))
     _print_json(out)
+    if args.assignments is not None:
+        with open(args.assignments, "w") as fh:
+            alignment.write_assignments(fh)
 
 
 def _run(args: argparse.Namespace) -> None:
@@ -401,24 +426,29 @@ def _run(args: argparse.Namespace) -> None:
     elif args.task == "dumpalign":
         if args.referencefile and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
-            pf = None if args.coverage else _prefetch_reads(args.reads)
+            host_parsed = args.coverage or args.assignments is not None
+            pf = None if host_parsed else _prefetch_reads(args.reads)
             ref = _load_reference(args.referencefile)
             _check_strands(args, ref)
             _print_alignment(create_alignment_from_reference(ref, args.reads, *filt, prefetch=pf,
-                                                             coverage=args.coverage), args)
+                                                             coverage=args.coverage,
+                                                             assignments=args.assignments is not None), args)
         elif args.genomefile and args.kmer_size and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
             validate_file_readable(args.genomefile, "Genome FASTA")
-            # (a coverage job runs on one device: the depth arrays of read shards are not reduced)
-            sharded = None if args.coverage else _dumpalign_sharded(args, filt)
+            # (a coverage job runs on one device: the depth arrays of read shards are not reduced;
+            # an assignments job too: its lines come from one host-parsed batch)
+            host_parsed = args.coverage or args.assignments is not None
+            sharded = None if host_parsed else _dumpalign_sharded(args, filt)
             if sharded is not None:
                 _print_json(sharded.get_summary())
                 return
-            pf = None if args.coverage else _prefetch_reads(args.reads)
+            pf = None if host_parsed else _prefetch_reads(args.reads)
             ref = create_reference(args.genomefile, args.kmer_size, args.filter_similar, args.similarity_threshold,
                                    reads_file=args.reads, both_strands=args.both_strands)
             _print_alignment(create_alignment_from_reference(ref, args.reads, *filt, prefetch=pf,
-                                                             coverage=args.coverage), args)
+                                                             coverage=args.coverage,
+                                                             assignments=args.assignments is not None), args)
         elif args.alignfile:
             validate_file_readable(args.alignfile, "Alignment output")
             try:

@@ -45,7 +45,7 @@ EXPORTS = (
     "pa_reads_download", "pa_reads_free",
     "pa_result_create", "pa_result_reset", "pa_result_fetch", "pa_result_device_view", "pa_result_copy_out",
     "pa_result_copy_in", "pa_result_load", "pa_result_free",
-    "pa_align", "pa_align_detail", "pa_align_batch", "pa_align_fastq_file", "pa_align_fastq_range",
+    "pa_align", "pa_align_detail", "pa_align_reads", "pa_align_batch", "pa_align_fastq_file", "pa_align_fastq_range",
     "pa_idsets_disjoint", "pa_idset_free",
     "pa_fastq_prefetch_start", "pa_align_fastq_prefetched", "pa_fastq_prefetch_free",
     "pa_comm_unique_id", "pa_comm_init", "pa_comm_free", "pa_comm_count", "pa_counters_reduce",
@@ -170,6 +170,7 @@ def lib():
         "pa_index_prepare_coverage": (I32, [P, P]),
         "pa_coverage_create": (I32, [P, PP]),
         "pa_coverage_reset": (I32, [P, P]),
+        "pa_align_reads": (I32, [P, P, ctypes.POINTER(Params), P, P, P, P, P, U64, ctypes.POINTER(U64), P]),
         "pa_coverage_add": (I32, [P, P, ctypes.POINTER(Params), P, P]),
         "pa_coverage_summary": (I32, [P, U32, P, P, P, P, P]),
         "pa_coverage_depth": (I32, [P, U32, U64, U64, P, P, P]),
@@ -919,6 +920,39 @@ def align_detail(index: Index, reads: Reads, params: Params, stream=None):
                                      _ptr(hr), _ptr(off), _ptr(lists), lists.size, ctypes.byref(total),
                                      _stream(stream)))
     return types[:n], qf[:n], hr[:n], off, lists[:int(total.value)]
+
+
+def align_reads_call(index: Index, reads: Reads, params: Params, list_cap: int, counters: bool = True,
+                     stream=None):
+    """One pa_align_reads call with room for `list_cap` list entries (0: no
+    list buffer): (status, types, qf, hr, list offsets, lists, list_total).
+    qf and hr are None without `counters`.  PA_EINVAL with list_total >
+    list_cap is the protocol's overflow: everything but the lists is valid."""
+    n = reads.n
+    types = np.zeros(max(n, 1), dtype=np.uint8)
+    qf = np.zeros(max(n, 1), dtype=np.uint32) if counters else None
+    hr = np.zeros(max(n, 1), dtype=np.uint32) if counters else None
+    off = np.zeros(n + 1, dtype=np.uint64)
+    lists = np.zeros(max(int(list_cap), 1), dtype=np.uint32) if list_cap else None
+    total = U64(0)
+    st = lib().pa_align_reads(index.handle, reads.handle, ctypes.byref(params), _ptr(types), _ptr(qf), _ptr(hr),
+                              _ptr(off), _ptr(lists), int(list_cap), ctypes.byref(total), _stream(stream))
+    return (st, types[:n], None if qf is None else qf[:n], None if hr is None else hr[:n], off, lists,
+            int(total.value))
+
+
+def align_reads(index: Index, reads: Reads, params: Params, stream=None):
+    """pa_align_reads: what align_detail returns, from the assign pass (the lane
+    kernels write the reads they settle, the exact kernel the rest).  The first
+    call has room for one list entry per read; a batch with longer lists is run
+    once more with the capacity the first call reported."""
+    st, types, qf, hr, off, lists, total = align_reads_call(index, reads, params, reads.n, True, stream)
+    if st == PA_EINVAL and total > reads.n:
+        st, types, qf, hr, off, lists, total = align_reads_call(index, reads, params, total, True, stream)
+    _check(st)
+    if lists is None:
+        lists = np.zeros(0, dtype=np.uint32)
+    return types, qf, hr, off, lists[:total]
 
 
 def align_placements(index: Index, reads: Reads, params: Params, stream=None):

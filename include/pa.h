@@ -25,6 +25,10 @@
  *                            Read.pseudo_align (counters only)              src/kmer.py:482-620
  *   pa_align_detail          the same, with per-read mapping type and
  *                            genomes_mapped_to (PseudoAlignment.reads)      src/kmer.py:542, 551-561
+ *   pa_align_reads           the same per-read results for a whole batch at
+ *                            about the counter pass's cost: the lane kernels
+ *                            write the reads they settle, the exact kernel the
+ *                            rest (PseudoAlignment.reads, --assignments)    src/kmer.py:542, 551-561
  *   pa_result_fetch          PseudoAlignment.get_summary inputs             src/kmer.py:622-657
  *   pa_coverage_* /          the course project's EXTCOVERAGE extension (--coverage, --genomes,
  *   pa_align_placements      --min-coverage, --full-coverage), which the reference leaves out: it
@@ -321,6 +325,20 @@ pa_status pa_align(const pa_index *idx, const pa_reads *reads, const pa_params *
 pa_status pa_align_detail(const pa_index *idx, const pa_reads *reads, const pa_params *params, uint8_t *read_type,
                           uint32_t *filtered_kmers, uint32_t *redundant_kmers, uint64_t *list_off, uint32_t *lists,
                           uint64_t list_cap, uint64_t *list_total, void *stream);
+/* pa_align_detail's outputs, made by the lane kernels for the reads they settle and by
+ * the exact kernel for the rest.  Bit for bit pa_align_detail's values.
+ * The pass runs once per call.  If list_cap < *list_total the call returns
+ * PA_EINVAL with *list_total, read_type, list_off and the two counters valid:
+ * the caller retries with the capacity it now knows (lists == NULL behaves as
+ * list_cap == 0).  filtered_kmers and redundant_kmers may be NULL.  At most
+ * 2^32 - 2 reads per batch (PA_EUNSUPPORTED), as pa_align; PA_EINTERNAL if a
+ * read was settled by no kernel (an invariant: never skipped silently).
+ * PA_ASSIGN=0 in the environment sends every read to the exact kernel, which is
+ * pa_align_detail's pass (A/B runs, a fallback).  DESIGN.md section 11. */
+pa_status pa_align_reads(const pa_index *idx, const pa_reads *reads, const pa_params *params,
+                         uint8_t *read_type, uint32_t *filtered_kmers /*nullable*/,
+                         uint32_t *redundant_kmers /*nullable*/, uint64_t *list_off,
+                         uint32_t *lists, uint64_t list_cap, uint64_t *list_total, void *stream);
 /* ---- coverage: where on a genome its reads fall ----------
  *
  * Every read is classified as pa_align_detail classifies it with the same

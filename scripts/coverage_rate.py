@@ -4,6 +4,7 @@ genomes, k = 31, synthesized 150-bp reads, 0.5 % substitutions).
 
     python scripts/coverage_rate.py --mode detail   [--reads N] [--runs R] > parent.json
     python scripts/coverage_rate.py --mode coverage [--reads N] [--runs R] [--baseline-json parent.json]
+    python scripts/coverage_rate.py --mode assign   [--reads N] [--runs R] [--read-err E --rc-rate X --foreign-rate Y]
 
 --mode detail times one pa_align_detail call with its lists (the pass a
 coverage add rides on); run it with PA_LIBRARY=<the parent commit's libpa.so>
@@ -17,6 +18,14 @@ align_detail_parent_s, so the record is one line of one command.  Every figure
 is the median of --runs timed calls after one warm-up call; all calls return
 when the device is done, so wall time is device time plus the call's own host
 work.  One JSON line on stdout.
+
+--mode assign times one pa_align_reads call (the assign pass, DESIGN.md section
+11: types, counters, offsets and lists of every read in one call with room for
+one list entry per read) next to pa_align_detail on the same library, and adds
+the kernels' own times over profiled_calls such calls (pa_profile_read_kernels)
+and the counter pass (pa_align + fetch) on the same batch.  --mode coverage rides the assign pass since
+pa_coverage_add classifies through it (PA_ASSIGN=0: the exact pass, as before).
+--read-err / --rc-rate / --foreign-rate give bench.py's c2mix reads (0.015, 0.2, 0.2).
 """
 
 import argparse
@@ -66,26 +75,70 @@ def time_detail(index, reads, prm, runs):
     return med, ts, int(total.value)
 
 
+def time_assign(index, reads, prm, runs):
+    """(median, runs, list entries) of one pa_align_reads call with its lists
+    (room for one entry per read; a longer total is learnt by a first call)."""
+    n = reads.n
+    types = np.zeros(n, dtype=np.uint8)
+    qf = np.zeros(n, dtype=np.uint32)
+    hr = np.zeros(n, dtype=np.uint32)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    total = N.U64(0)
+    lists = np.zeros(max(n, 1), dtype=np.uint32)
+
+    def call():
+        return N.lib().pa_align_reads(index.handle, reads.handle, ctypes.byref(prm), N._ptr(types), N._ptr(qf),
+                                      N._ptr(hr), N._ptr(off), N._ptr(lists), lists.size, ctypes.byref(total), None)
+    st = call()
+    if st == N.PA_EINVAL and total.value > lists.size:
+        lists = np.zeros(int(total.value), dtype=np.uint32)
+        st = call()
+    N._check(st)
+    med, ts = timed(lambda: N._check(call()), runs)
+    return med, ts, int(total.value)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("detail", "coverage"), required=True)
+    ap.add_argument("--mode", choices=("detail", "coverage", "assign"), required=True)
     ap.add_argument("--reads", type=int, default=10_000_000)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--genomes", type=int, default=50)
     ap.add_argument("--genome-len", type=int, default=2_000_000)
+    ap.add_argument("--read-err", type=float, default=0.005)
+    ap.add_argument("--rc-rate", type=float, default=0.0)
+    ap.add_argument("--foreign-rate", type=float, default=0.0)
     ap.add_argument("--baseline-json", default=None, help="the line of a --mode detail run on the parent's library")
     args = ap.parse_args()
     genomes = synth.family_genomes(args.genomes, args.genome_len, seed=1, family_size=5, sub_rate=0.01,
                                    conserved_len=5000, n_rate=1e-4, n_run=10)
     index = N.Index(genomes, 31)
     index.prepare()
-    reads = N.Reads.synthesize(index, args.reads, 150, first_read=0, seed=2, sub_rate=0.005)
+    reads = N.Reads.synthesize(index, args.reads, 150, first_read=0, seed=2, sub_rate=args.read_err,
+                               rc_rate=args.rc_rate, foreign_rate=args.foreign_rate)
     prm = N.Params.make()
     out = {"workload": f"C2 index ({args.genomes} x {args.genome_len} bp, k=31), {args.reads} x 150 bp reads",
+           "read_mix": {"err": args.read_err, "reverse_complement": args.rc_rate, "foreign": args.foreign_rate},
            "mode": args.mode, "runs": args.runs, "library": N.lib().pa_version().decode()}
     if args.mode == "detail":
         med, ts, entries = time_detail(index, reads, prm, args.runs)
         out.update(align_detail_s=med, align_detail_runs_s=ts, list_entries=entries)
+    elif args.mode == "assign":
+        med, ts, entries = time_assign(index, reads, prm, args.runs)
+        out.update(align_reads_s=med, align_reads_runs_s=ts, list_entries=entries,
+                   assign_reads_per_s=args.reads / med)
+        index.profile_enable(True)
+        index.profile_read_kernels()
+        time_assign(index, reads, prm, 1)  # (three calls: the first, the warm-up and one timed)
+        out["profiled_calls"] = 3
+        out["kernels_ms_launches"] = index.profile_read_kernels()
+        index.profile_enable(False)
+        res = N.Result(index)
+        N.align(index, reads, prm, 0, res)
+        out["counter_pass_s"], _ = timed(lambda: (N.align(index, reads, prm, 0, res), res.fetch()), args.runs)
+        dmed, dts, dentries = time_detail(index, reads, prm, args.runs)
+        assert dentries == entries
+        out.update(align_detail_s=dmed, align_detail_runs_s=dts, ratio_detail_over_assign=dmed / med)
     else:
         med, ts, entries = time_detail(index, reads, prm, args.runs)
         out.update(align_detail_branch_s=med, align_detail_branch_runs_s=ts, list_entries=entries)
