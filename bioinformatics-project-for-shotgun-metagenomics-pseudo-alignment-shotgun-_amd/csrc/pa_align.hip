@@ -38,6 +38,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "pa_device.h"
@@ -786,20 +787,79 @@ size_t fast_lds_bytes(uint32_t G, int wpl, bool need_q) {
     return cnt + kWaves * wl;
 }
 
-template <int NW, int WPL, bool DENSE>
-pa_status launch_fast(const AlignArgs &a, size_t shm, hipStream_t st) {
-    auto kern = k_align_fast<NW, WPL, DENSE>;
+// The environment switches of the align passes (tests and A/B runs), all read
+// here and nowhere else: a pass makes one Switches at its top, on every call --
+// tests flip them between two calls of one process, so nothing is kept.
+const char *env(const char *name) { return std::getenv(name); }
+bool env_is(const char *name, char c) { const char *e = env(name); return e && e[0] == c; }
+uint64_t env_u64(const char *name, uint64_t unset) { const char *e = env(name); return e ? std::strtoull(e, nullptr, 10) : unset; }
+int env_int(const char *name, int unset) { const char *e = env(name); return e ? std::atoi(e) : unset; }
+int env_01(const char *name) { const char *e = env(name); return e ? e[0] == '1' : -1; }  // -1: unset
+
+struct Switches {
+    bool no_qelide = env("PA_NO_QELIDE");            // set: quality thresholds no read can fail stay in the pass
+    bool no_lane = env_is("PA_NO_LANE", '1');        // 1: skip the lane kernels
+    uint64_t lane_grid = env_u64("PA_LANE_GRID", ~0ull);  // <blocks>: tests -- a small batch then runs many chunks per wave
+    uint32_t lane_maxpend = (uint32_t)env_int("PA_LANE_MAXPEND", 96);  // more unwalked windows than this -> wave kernel
+    // 1 / else: seedless reads probe all their windows (k_align_lane_na) / go to the wave kernel; unset (-1): by the Bloom filter
+    int lane_noanchor = env_01("PA_LANE_NOANCHOR");
+    uint64_t na_min = env_u64("PA_NA_MIN", 32768);   // fewer seedless reads than this go on to the wave kernel (tests)
+    bool na_seg = !env_is("PA_NA_SEG", '0');         // 0: the flat queue of seedless reads, not per-wave segments (A/B)
+    bool na_rcwalk = !env_is("PA_NA_RCWALK", '0');   // 0: without the reverse-complement plane (no reverse-strand walk)
+    bool na_rcnb = !env_is("PA_NA_RCNB", '0');       // 0: without the reverse-complement neighbour bits
+    bool mm_bits = !env_is("PA_MM_BITS", '0');       // 0: without the minimizer presence bitmap
+    bool no_nbbig = env("PA_NO_NBBIG");              // set: --max-genomes >= 2 without the neighbour bits' set-size half
+    bool no_nbm = env("PA_NO_NBM");                  // set: ... without that half interleaved with the neighbour words
+    bool no_mgnb = env("PA_NO_MGNB");                // set: the neighbour bits do not settle a neighbour's set vs mg
+    int walk_rounds = env_int("PA_WALK_ROUNDS", 1);  // the wave kernel's walk rounds
+    int dbg_mode = env_int("PA_DBG_MODE", 0);        // PA_STATS / PA_DISSECT builds: stop each read after phase N
+};
+
+// Runtime choices as compile-time constants: each helper calls a generic
+// lambda with std::integral_constants, every call returning the same type; a
+// combination no helper lists is not instantiated.
+template <int N> using int_c = std::integral_constant<int, N>;
+
+// f(N) for the first N of the list that equals n, else for the last one
+template <int N0, int... Ns, class F>
+auto with_int(int n, F &&f) {
+    if constexpr (sizeof...(Ns) == 0) return f(int_c<N0>{});
+    else return n == N0 ? f(int_c<N0>{}) : with_int<Ns...>(n, f);
+}
+
+// f(NEED_Q, WIN_Q, MG) for the six filter sets of a pass (window quality implies read quality)
+template <class F>
+auto with_filters(uint32_t flags, F &&f) {
+    const auto with_mg = [&](auto need_q, auto win_q) {
+        return (flags & F_MG) ? f(need_q, win_q, std::true_type{}) : f(need_q, win_q, std::false_type{});
+    };
+    if (flags & F_MKQ) return with_mg(std::true_type{}, std::true_type{});
+    if (flags & F_MRQ) return with_mg(std::true_type{}, std::false_type{});
+    return with_mg(std::false_type{}, std::false_type{});
+}
+
+// f(NM, NW) for key widths 3, 2, 1; the 250-bp shape (NM = 4) only for single-word keys without window quality
+template <bool WIN_Q, class F>
+auto with_shape(int nw, bool nm4, F &&f) {
+    return with_int<3, 2, 1>(nw, [&](auto w) {
+        if constexpr (!WIN_Q && w() == 1)
+            if (nm4) return f(int_c<4>{}, w);
+        return f(int_c<2>{}, w);
+    });
+}
+
+// The grid of a persistent kernel: the blocks of `kern` (`block` threads, shm
+// bytes of dynamic LDS) resident on the device at once, at most `want`, at
+// least one.
+using AlignKernel = void (*)(AlignArgs);
+pa_status resident_grid(AlignKernel kern, int block, size_t shm, uint64_t want, unsigned &grid) {
     if (shm > 64 * 1024) PA_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    int per_cu = 0;
-    PA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, shm));
-    int dev = 0, cus = 256;
+    int per_cu = 0, dev = 0, cus = 256;
+    PA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, block, shm));
     PA_HIP(hipGetDevice(&dev));
     PA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    uint64_t want = (a.n + kWaves - 1) / kWaves;
-    uint64_t resident = (uint64_t)std::max(1, per_cu) * (uint64_t)cus;
-    unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, resident));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), shm, st, a);
-    PA_HIP(hipGetLastError());
+    const uint64_t resident = (uint64_t)std::max(1, per_cu) * (uint64_t)cus;
+    grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, resident));
     return PA_OK;
 }
 
@@ -822,6 +882,30 @@ struct KernelTimer {
     }
 };
 
+// One kernel of a pass on `grid` workgroups, timed as profile slot `slot`.
+pa_status launch_timed(pa_index *prof, int slot, AlignKernel kern, unsigned grid, size_t shm, hipStream_t st,
+                       const AlignArgs &a) {
+    KernelTimer kt(prof, st, slot);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), shm, st, a);
+    PA_HIP(hipGetLastError());
+    return PA_OK;
+}
+
+// The wave kernel for keys of nw words and wpl windows per lane (1, 2, else 4), a wave per read.
+pa_status launch_wave(const AlignArgs &a, pa_index *prof, int nw, int wpl, hipStream_t st) {
+    const size_t shm = fast_lds_bytes(a.G, wpl, (a.prm.flags & (F_MRQ | F_MKQ)) != 0);
+    const bool dense = a.G <= 64;  // membership masks exist (k_class_masks)
+    const AlignKernel kern = with_int<1, 2, 3, 4>(nw, [&](auto w) {
+        constexpr int NW = w();
+        return with_int<1, 2, 4>(wpl, [&](auto l) -> AlignKernel {
+            return dense ? k_align_fast<NW, l(), true> : k_align_fast<NW, l(), false>;
+        });
+    });
+    unsigned grid = 0;
+    PA_TRY(resident_grid(kern, kBlock, shm, (a.n + kWaves - 1) / kWaves, grid));
+    return launch_timed(prof, PA_PROF_WAVE, kern, grid, shm, st, a);
+}
+
 // long_reads: the batch holds reads longer than the 150-bp shape takes (176
 // bases): the 250-bp shape (NM = 4, <= 272 bases, <= 256 windows) walks them,
 // unless --min-kmer-quality is set (its window masks cover 128 windows: such
@@ -829,40 +913,29 @@ struct KernelTimer {
 // nw: key words (2: 31 < k <= 63, 3: 63 < k <= 95 -- the 150-bp shape, no
 // reverse-strand path: reads without a seed go to the wave kernel).
 constexpr uint64_t kRcnbMinReads = 32768;  // seedless reads in a pass that make the reverse-complement bits worth it
+struct LaneKernels { AlignKernel lane, rc, na; };
 // AS: the assign pass's instantiations (lane_assign; a.as_* set).
 template <bool AS>
-pa_status launch_lane(const AlignArgs &a0, hipStream_t st, pa_index *prof = nullptr, bool long_reads = false,
-                      int nw = 1) {
-    const bool need_q = (a0.prm.flags & (F_MRQ | F_MKQ)) != 0;
+pa_status launch_lane(const AlignArgs &a0, const Switches &sw, hipStream_t st, pa_index *prof, bool long_reads, int nw) {
     const bool win_q = (a0.prm.flags & F_MKQ) != 0;
     const bool mg = (a0.prm.flags & F_MG) != 0;
     const bool nm4 = long_reads && !win_q && nw == 1;
     AlignArgs a = a0;
     const size_t shm = lane_lds_bytes(a.G, nm4 ? 4 : 2, lane_sched(win_q, mg, nm4 ? 4 : 2, nw));
-    auto kern = nw == 3
-                    ? (win_q ? (mg ? k_align_lane<true, true, true, 2, 3, AS> : k_align_lane<true, true, false, 2, 3, AS>)
-                       : need_q ? (mg ? k_align_lane<true, false, true, 2, 3, AS> : k_align_lane<true, false, false, 2, 3, AS>)
-                                : (mg ? k_align_lane<false, false, true, 2, 3, AS> : k_align_lane<false, false, false, 2, 3, AS>))
-              : nw == 2
-                    ? (win_q ? (mg ? k_align_lane<true, true, true, 2, 2, AS> : k_align_lane<true, true, false, 2, 2, AS>)
-                       : need_q ? (mg ? k_align_lane<true, false, true, 2, 2, AS> : k_align_lane<true, false, false, 2, 2, AS>)
-                                : (mg ? k_align_lane<false, false, true, 2, 2, AS> : k_align_lane<false, false, false, 2, 2, AS>))
-              : nm4 ? (need_q ? (mg ? k_align_lane<true, false, true, 4, 1, AS> : k_align_lane<true, false, false, 4, 1, AS>)
-                              : (mg ? k_align_lane<false, false, true, 4, 1, AS> : k_align_lane<false, false, false, 4, 1, AS>))
-              : win_q ? (mg ? k_align_lane<true, true, true, 2, 1, AS> : k_align_lane<true, true, false, 2, 1, AS>)
-              : need_q ? (mg ? k_align_lane<true, false, true, 2, 1, AS> : k_align_lane<true, false, false, 2, 1, AS>)
-                       : (mg ? k_align_lane<false, false, true, 2, 1, AS> : k_align_lane<false, false, false, 2, 1, AS>);
-    if (shm > 64 * 1024) PA_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    int per_cu = 0, dev = 0, cus = 256;
-    PA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, shm));
-    PA_HIP(hipGetDevice(&dev));
-    PA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const LaneKernels kern = with_filters(a.prm.flags, [&](auto nq, auto wq, auto g) {
+        constexpr bool NEED_Q = nq(), WIN_Q = wq(), MG = g();
+        return LaneKernels{
+            with_shape<WIN_Q>(nw, nm4, [](auto nm, auto w) -> AlignKernel { return k_align_lane<NEED_Q, WIN_Q, MG, nm(), w(), AS>; }),
+            k_align_lane_rc<NEED_Q, WIN_Q, MG, AS>,
+            with_int<3, 2, 1>(nw, [](auto w) -> AlignKernel {
+                if constexpr (w() == 1) return k_align_lane_na<NEED_Q, WIN_Q, MG, AS>;
+                else return k_align_lane_naw<NEED_Q, WIN_Q, MG, w(), AS>;
+            })};
+    });
     const uint64_t want = (a.n + kBlock - 1) / kBlock;
-    const uint64_t resident = (uint64_t)std::max(1, per_cu) * (uint64_t)cus;
-    unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, resident));
-    // (PA_LANE_GRID=<blocks>: tests -- a small batch then runs many chunks per wave)
-    if (const char *e = std::getenv("PA_LANE_GRID"))
-        grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(grid, std::strtoull(e, nullptr, 10)));
+    unsigned grid = 0;
+    PA_TRY(resident_grid(kern.lane, kBlock, shm, want, grid));
+    grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(grid, sw.lane_grid));
     // the seedless reads for k_rc_seeds in per-wave queue segments: one
     // atomic per wave and chunk on the queue's counter serialised, and cost
     // c2rc (half its reads seedless) 0.27 ms per 10 M reads (PA_NA_SEG=0: the
@@ -872,111 +945,56 @@ pa_status launch_lane(const AlignArgs &a0, hipStream_t st, pa_index *prof = null
     // more than its share of all reads queued, so the waves that still claim
     // have room for every read left and none is lost; a wave with few
     // seedless reads takes as many chunks as it gets to
-    {
-        const char *e = std::getenv("PA_NA_SEG");
-        const uint64_t waves = (uint64_t)grid * kWaves, chunks = (a.n + 63) / 64;
-        a.nseg = (uint32_t)waves;
-        a.seg_cap = 64 * ((chunks + waves - 1) / waves + kLaneClaimHeld);
-        a.na_seg = a.queue_na && a.queue_na_keys && a.seg_cnt && !nm4 && nw == 1 && waves <= kSegMaxWaves &&
-                   waves * a.seg_cap <= a.queue_cap && !(e && e[0] == '0');
-    }
-    {
-        KernelTimer kt(prof, st, PA_PROF_LANE);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), shm, st, a);
-        PA_HIP(hipGetLastError());
-    }
-    if (a.queue_na) {  // the reads without a seed in the index (count on the device)
-        AlignArgs b = a;
-        // the reverse-complement neighbour bits, left out by the build
-        // (build_nb), are made by the first pass that queues enough seedless
-        // reads; passes that queue too few look twice, then stop looking (the
-        // reverse-strand walk runs without them, exactly, only slower)
-        if (prof && prof->rcnb_pending && a.queue_na_keys) {
-            unsigned long long c = 0;
-            PA_HIP(hipMemcpyAsync(&c, a.queue_na_count, 8, hipMemcpyDeviceToHost, st));
-            PA_HIP(hipStreamSynchronize(st));
-            if (c >= std::max<uint64_t>(kRcnbMinReads, a.n / 64)) {
-                PA_TRY(pa::index_build_rcnb(prof, st));
-                const char *e = std::getenv("PA_NA_RCNB");
-                if (!(e && e[0] == '0')) b.tile_rcnb = prof->tile_rcnb;
-            } else if (++prof->rcnb_checks >= 2) {
-                prof->rcnb_pending = 0;
-            }
+    const uint64_t waves = (uint64_t)grid * kWaves, chunks = (a.n + 63) / 64;
+    a.nseg = (uint32_t)waves;
+    a.seg_cap = 64 * ((chunks + waves - 1) / waves + kLaneClaimHeld);
+    a.na_seg = a.queue_na && a.queue_na_keys && a.seg_cnt && !nm4 && nw == 1 && waves <= kSegMaxWaves &&
+               waves * a.seg_cap <= a.queue_cap && sw.na_seg;
+    PA_TRY(launch_timed(prof, PA_PROF_LANE, kern.lane, grid, shm, st, a));
+    if (!a.queue_na) return PA_OK;
+    AlignArgs b = a;  // for the reads without a seed in the index (count on the device)
+    // the reverse-complement neighbour bits, left out by the build
+    // (build_nb), are made by the first pass that queues enough seedless
+    // reads; passes that queue too few look twice, then stop looking (the
+    // reverse-strand walk runs without them, exactly, only slower)
+    if (prof && prof->rcnb_pending && a.queue_na_keys) {
+        unsigned long long c = 0;
+        PA_HIP(hipMemcpyAsync(&c, a.queue_na_count, 8, hipMemcpyDeviceToHost, st));
+        PA_HIP(hipStreamSynchronize(st));
+        if (c >= std::max<uint64_t>(kRcnbMinReads, a.n / 64)) {
+            PA_TRY(pa::index_build_rcnb(prof, st));
+            if (sw.na_rcnb) b.tile_rcnb = prof->tile_rcnb;
+        } else if (++prof->rcnb_checks >= 2) {
+            prof->rcnb_pending = 0;
         }
-        if (a.queue_na_keys) {  // reverse-complement seeds, the reverse-strand walk; the rest on to k_align_lane_na
-            {
-                KernelTimer kt(prof, st, PA_PROF_RC_SEEDS);
-                const unsigned sgrid = a.na_seg ? (a.nseg + kSegGroup - 1) / kSegGroup  // (a group of segments per block)
-                                                : (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(
-                                                      (a.n + kBlock * 4 - 1) / (kBlock * 4), 8192));
-                hipLaunchKernelGGL(k_rc_seeds, dim3(sgrid), dim3(kBlock), 0, st, b);
-                PA_HIP(hipGetLastError());
-            }
-            auto rc = win_q ? (mg ? k_align_lane_rc<true, true, true, AS> : k_align_lane_rc<true, true, false, AS>)
-                    : need_q ? (mg ? k_align_lane_rc<true, false, true, AS> : k_align_lane_rc<true, false, false, AS>)
-                             : (mg ? k_align_lane_rc<false, false, true, AS> : k_align_lane_rc<false, false, false, AS>);
-            int rc_cu = 0;
-            PA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&rc_cu, rc, kBlock, 0));
-            const unsigned rgrid = (unsigned)std::max<uint64_t>(
-                1, std::min<uint64_t>(want, (uint64_t)std::max(1, rc_cu) * (uint64_t)cus));
-            KernelTimer kt(prof, st, PA_PROF_LANE_RC);
-            hipLaunchKernelGGL(rc, dim3(rgrid), dim3(kBlock), 0, st, b);
-            PA_HIP(hipGetLastError());
-            b.queue_na = a.queue_na2;
-            b.queue_na_count = a.queue_na2_count;
-        }
-        auto na = nw == 3 ? (win_q ? (mg ? k_align_lane_naw<true, true, true, 3, AS> : k_align_lane_naw<true, true, false, 3, AS>)
-                             : need_q ? (mg ? k_align_lane_naw<true, false, true, 3, AS> : k_align_lane_naw<true, false, false, 3, AS>)
-                                      : (mg ? k_align_lane_naw<false, false, true, 3, AS> : k_align_lane_naw<false, false, false, 3, AS>))
-                : nw == 2 ? (win_q ? (mg ? k_align_lane_naw<true, true, true, 2, AS> : k_align_lane_naw<true, true, false, 2, AS>)
-                             : need_q ? (mg ? k_align_lane_naw<true, false, true, 2, AS> : k_align_lane_naw<true, false, false, 2, AS>)
-                                      : (mg ? k_align_lane_naw<false, false, true, 2, AS> : k_align_lane_naw<false, false, false, 2, AS>))
-                : win_q ? (mg ? k_align_lane_na<true, true, true, AS> : k_align_lane_na<true, true, false, AS>)
-                : need_q ? (mg ? k_align_lane_na<true, false, true, AS> : k_align_lane_na<true, false, false, AS>)
-                         : (mg ? k_align_lane_na<false, false, true, AS> : k_align_lane_na<false, false, false, AS>);
-        int na_cu = 0;
-        PA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&na_cu, na, kBlock, 0));
-        const unsigned ngrid = (unsigned)std::max<uint64_t>(
-            1, std::min<uint64_t>(want, (uint64_t)std::max(1, na_cu) * (uint64_t)cus));
-        KernelTimer kt(prof, st, PA_PROF_LANE_NA);
-        hipLaunchKernelGGL(na, dim3(ngrid), dim3(kBlock), 0, st, b);
-        PA_HIP(hipGetLastError());
     }
+    if (a.queue_na_keys) {  // reverse-complement seeds, the reverse-strand walk; the rest on to k_align_lane_na
+        const unsigned sgrid = a.na_seg ? (a.nseg + kSegGroup - 1) / kSegGroup  // (a group of segments per block)
+                                        : (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(
+                                              (a.n + kBlock * 4 - 1) / (kBlock * 4), 8192));
+        PA_TRY(launch_timed(prof, PA_PROF_RC_SEEDS, k_rc_seeds, sgrid, 0, st, b));
+        PA_TRY(resident_grid(kern.rc, kBlock, 0, want, grid));
+        PA_TRY(launch_timed(prof, PA_PROF_LANE_RC, kern.rc, grid, 0, st, b));
+        b.queue_na = a.queue_na2;
+        b.queue_na_count = a.queue_na2_count;
+    }
+    PA_TRY(resident_grid(kern.na, kBlock, 0, want, grid));
+    return launch_timed(prof, PA_PROF_LANE_NA, kern.na, grid, 0, st, b);
+}
+
+// The exact kernel for keys of nw words, timed (prof: the index, or null) as PA_PROF_EXACT.
+pa_status launch_exact(pa_index *prof, int nw, const ExactArgs &x, unsigned grid, hipStream_t st) {
+    KernelTimer kt(prof, st, PA_PROF_EXACT);
+    with_int<1, 2, 3, 4, 5, 6, 7, 8>(nw, [&](auto w) {
+        hipLaunchKernelGGL(k_align_exact<w()>, dim3(grid), dim3(kBlock), 0, st, x);
+    });
+    PA_HIP(hipGetLastError());
     return PA_OK;
-}
-
-template <int NW>
-pa_status launch_fast_wpl(const AlignArgs &a, int wpl, hipStream_t st) {
-    size_t shm = fast_lds_bytes(a.G, wpl, (a.prm.flags & (F_MRQ | F_MKQ)) != 0);
-    const bool dense = a.G <= 64;  // membership masks exist (k_class_masks)
-    switch (wpl) {
-        case 1: return dense ? launch_fast<NW, 1, true>(a, shm, st) : launch_fast<NW, 1, false>(a, shm, st);
-        case 2: return dense ? launch_fast<NW, 2, true>(a, shm, st) : launch_fast<NW, 2, false>(a, shm, st);
-        default: return dense ? launch_fast<NW, 4, true>(a, shm, st) : launch_fast<NW, 4, false>(a, shm, st);
-    }
-}
-
-template <int NW>
-void launch_exact(const ExactArgs &x, unsigned grid, hipStream_t st) {
-    hipLaunchKernelGGL(k_align_exact<NW>, dim3(grid), dim3(kBlock), 0, st, x);
-}
-
-void launch_exact_nw(int nw, const ExactArgs &x, unsigned grid, hipStream_t st) {
-    switch (nw) {
-        case 1: launch_exact<1>(x, grid, st); break;
-        case 2: launch_exact<2>(x, grid, st); break;
-        case 3: launch_exact<3>(x, grid, st); break;
-        case 4: launch_exact<4>(x, grid, st); break;
-        case 5: launch_exact<5>(x, grid, st); break;
-        case 6: launch_exact<6>(x, grid, st); break;
-        case 7: launch_exact<7>(x, grid, st); break;
-        default: launch_exact<8>(x, grid, st); break;
-    }
 }
 
 constexpr unsigned kExactGrid = 512;
 
-AlignArgs make_args(const pa_index *idx, const pa_reads *r, const pa::DevParams &p, uint64_t base) {
+AlignArgs make_args(const pa_index *idx, const pa_reads *r, const pa::DevParams &p, uint64_t base, const Switches &sw) {
     AlignArgs a{};
     a.table = idx->table;
     a.cap = idx->cap;
@@ -998,22 +1016,17 @@ AlignArgs make_args(const pa_index *idx, const pa_reads *r, const pa::DevParams 
     a.gblk = idx->tile_gblk;
     a.bloom = idx->tile_cls ? idx->bloom : nullptr;
     a.bloom_lg = idx->bloom_lg;
-    a.tile_rcp = idx->tile_cls ? idx->tile_rcp : nullptr;
-    a.mm_bits = idx->tile_cls ? idx->mm_bits : nullptr;
+    a.tile_rcp = idx->tile_cls && sw.na_rcwalk ? idx->tile_rcp : nullptr;
+    a.mm_bits = idx->tile_cls && sw.mm_bits ? idx->mm_bits : nullptr;
     a.mm_lg = idx->mm_lg;
-    if (const char *e = std::getenv("PA_MM_BITS")) if (e[0] == '0') a.mm_bits = nullptr;
-    a.tile_rcnb = idx->tile_cls ? idx->tile_rcnb : nullptr;
-    if (const char *e = std::getenv("PA_NA_RCNB")) if (e[0] == '0') a.tile_rcnb = nullptr;
-    if (const char *e = std::getenv("PA_NA_RCWALK")) if (e[0] == '0') a.tile_rcp = nullptr;
+    a.tile_rcnb = idx->tile_cls && sw.na_rcnb ? idx->tile_rcnb : nullptr;
     a.tile_n = idx->tile_cls ? idx->tile_n : 0;
-    a.walk_rounds = 1;
+    a.walk_rounds = sw.walk_rounds;
     a.tpos_local = idx->tpos_local;
-    a.lane_maxpend = 96;
-    if (const char *e = std::getenv("PA_LANE_MAXPEND")) a.lane_maxpend = (uint32_t)std::atoi(e);
-    a.lane_noanchor = a.bloom != nullptr;  // (without the filter every window costs a table line)
-    if (const char *e = std::getenv("PA_LANE_NOANCHOR")) a.lane_noanchor = e[0] == '1';
-    if (const char *e = std::getenv("PA_WALK_ROUNDS")) a.walk_rounds = std::atoi(e);
-    if (const char *e = std::getenv("PA_DBG_MODE")) a.dbg_mode = std::atoi(e);
+    a.lane_maxpend = sw.lane_maxpend;
+    // (without the Bloom filter every window of a seedless read costs a table line)
+    a.lane_noanchor = sw.lane_noanchor < 0 ? a.bloom != nullptr : sw.lane_noanchor;
+    a.dbg_mode = sw.dbg_mode;
     a.seq = r->seq;
     a.qual = r->qual;
     a.off = r->off;
@@ -1023,7 +1036,14 @@ AlignArgs make_args(const pa_index *idx, const pa_reads *r, const pa::DevParams 
     return a;
 }
 
-pa_status prepare_exact(pa_index *idx, const pa_reads *r, ExactArgs &x, unsigned &grid) {
+// The exact kernel's arguments over batch r: its workspace and grid, the
+// pass's AlignArgs, and where the per-read detail goes -- out null: counters
+// only (detail 0); else types, filter counts and list lengths (1) and, with
+// out->lists, the lists at out->list_off (2).
+struct DetailOut { uint8_t *type; uint32_t *qf, *hr, *len; const uint64_t *list_off; uint32_t *lists; };
+
+pa_status exact_args(pa_index *idx, const pa_reads *r, const AlignArgs &a, const DetailOut *out, ExactArgs &x,
+                     unsigned &grid) {
     const uint32_t wcap = std::max<uint32_t>(1, r->max_len);
     uint32_t dh = 64;
     while (dh < 2 * wcap) dh <<= 1;
@@ -1031,10 +1051,17 @@ pa_status prepare_exact(pa_index *idx, const pa_reads *r, ExactArgs &x, unsigned
     grid = kExactGrid;
     while (grid > 16 && (uint64_t)grid * stride > (1ull << 31)) grid >>= 1;
     PA_TRY(pa::ensure_workspace(idx, (size_t)grid * stride));
+    x = ExactArgs{};
+    x.a = a;
     x.ws = (unsigned char *)idx->ws.ptr;
     x.ws_stride = stride;
     x.wcap = wcap;
     x.dh = dh;
+    if (out) {
+        x.detail = out->lists ? 2 : 1;
+        x.type_out = out->type, x.qf_out = out->qf, x.hr_out = out->hr, x.len_out = out->len;
+        x.list_off = out->list_off, x.lists = out->lists;
+    }
     return PA_OK;
 }
 
@@ -1195,14 +1222,147 @@ pa_status reads_measure(pa_reads *r, hipStream_t st) {
 // --min-read-quality / --min-kmer-quality <= that byte nothing is filtered
 // (src/kmer.py:420, 587: strict <) -- e.g. C3's literal 20 / 25 against
 // FASTQ qualities >= '!' (33), quirk 5.  Reads of length 0 keep the read test.
-pa_status effective_params(const pa_reads *r, const DevParams &p, DevParams &out, hipStream_t st) {
+static pa_status effective_params(const pa_reads *r, const DevParams &p, DevParams &out, hipStream_t st,
+                                  const Switches &sw) {
     out = p;
-    if (!(p.flags & (F_MRQ | F_MKQ)) || !r->qual || r->n == 0 || std::getenv("PA_NO_QELIDE")) return PA_OK;
+    if (!(p.flags & (F_MRQ | F_MKQ)) || !r->qual || r->n == 0 || sw.no_qelide) return PA_OK;
     if (r->q_min < 0) PA_TRY(reads_measure(const_cast<pa_reads *>(r), st));  // (not measured at creation)
     if ((p.flags & F_MRQ) && r->len_min > 0 && p.mrq <= r->q_min) out.flags &= ~F_MRQ;
     if ((p.flags & F_MKQ) && p.mkq <= r->q_min) out.flags &= ~F_MKQ;
     return PA_OK;
 }
+
+pa_status effective_params(const pa_reads *r, const DevParams &p, DevParams &out, hipStream_t st) {
+    return effective_params(r, p, out, st, Switches{});
+}
+
+// ---- the steps of a pass (align_pass, below) --------------------------------
+
+// A cached plane of the index of `bytes` (+ 64 of padding), made only when it
+// fits with 8 GB to spare; counted in device_bytes (pa_index_get_info reports
+// the real footprint).
+template <class T>
+static bool alloc_when_it_fits(pa_index *idx, T **p, uint64_t bytes) {
+    size_t free_b = 0, total_b = 0;
+    const bool ok = pa::dev_mem_info(&free_b, &total_b) == hipSuccess && bytes + (8ull << 30) < free_b &&
+                    pa::dev_malloc(p, bytes + 64) == hipSuccess;
+    if (ok)
+        idx->device_bytes += bytes + 64;
+    else
+        *p = nullptr;
+    (void)hipGetLastError();
+    return ok;
+}
+
+// The lane kernels' planes for --max-genomes, cached in the index per mg value:
+// tile_big ("set size > mg", mg >= 2), tile_nbbig (the neighbour bits' set-size
+// half) and tile_nbm (that half interleaved with the neighbour words).
+static pa_status mg_planes(pa_index *idx, AlignArgs &a, const Switches &sw, hipStream_t st) {
+    if ((a.prm.flags & F_MG) && a.prm.mg >= 2) {
+        const uint64_t n_words = a.tile_n / 64 + 8;  // (padded: the 250-bp walk reads five words from any position)
+        if (!idx->tile_big) PA_HIP(pa::dev_malloc(&idx->tile_big, n_words * 8));
+        if (idx->tile_big_mg != a.prm.mg) {
+            hipLaunchKernelGGL(k_tile_big, dim3((unsigned)std::min<uint64_t>((n_words + 3) / 4, 1u << 20)),
+                               dim3(256), 0, st, idx->tile_cls, a.tile_n, a.G, idx->class_genomes,
+                               (int32_t)a.prm.mg, idx->tile_big, n_words);
+            PA_HIP(hipGetLastError());
+            idx->tile_big_mg = a.prm.mg;
+        }
+        a.tile_big = idx->tile_big;
+        // the neighbour bits' set-size half for this mg (12 B per base;
+        // only with the 24-B neighbour bits, and when it fits)
+        if (idx->tile_nb && idx->nb_spec && !idx->tile_nb1 && !sw.no_nbbig) {
+            const uint64_t nw = 3 * a.tile_n;
+            const unsigned grid = (unsigned)std::min<uint64_t>((nw + 255) / 256, 1u << 20);
+            if (!idx->tile_nbbig && alloc_when_it_fits(idx, &idx->tile_nbbig, nw * 4)) idx->tile_nbbig_mg = -1;
+            if (idx->tile_nbbig && idx->tile_nbbig_mg != a.prm.mg) {
+                hipLaunchKernelGGL(k_nb_big, dim3(grid), dim3(256), 0, st, idx->tile_pk, (const uint64_t *)idx->tile_nb,
+                                   nw, (int)idx->k, (const Slot<1> *)idx->table, idx->home, a.G, idx->class_genomes,
+                                   (int32_t)a.prm.mg, idx->tile_nbbig);
+                PA_HIP(hipGetLastError());
+                idx->tile_nbbig_mg = a.prm.mg;
+            }
+            a.tile_nbbig = idx->tile_nbbig;
+            if (a.tile_nbbig) a.nbbig_ld = a.tile_nbbig, a.nbbig_mask = ~0ull;
+            // interleaved with the neighbour words (48 B per base, when it fits)
+            if (idx->tile_nbbig && !sw.no_nbm) {
+                if (!idx->tile_nbm && alloc_when_it_fits(idx, &idx->tile_nbm, nw * 16)) idx->tile_nbm_mg = -1;
+                if (idx->tile_nbm && idx->tile_nbm_mg != a.prm.mg) {
+                    hipLaunchKernelGGL(k_nb_merge, dim3(grid), dim3(256), 0, st, (const uint64_t *)idx->tile_nb,
+                                       idx->tile_nbbig, nw, idx->tile_nbm);
+                    PA_HIP(hipGetLastError());
+                    idx->tile_nbm_mg = a.prm.mg;
+                }
+                a.tile_nbm = idx->tile_nbm;
+            }
+        }
+    }
+    // every present neighbour's set size vs mg known from the bits
+    a.mg_nb = (a.prm.flags & F_MG) && a.tile_nb && a.nb_spec && (a.prm.mg < 2 || a.tile_nbbig) && !sw.no_mgnb;
+    return PA_OK;
+}
+
+// The quality filters of every read, up front (k_quality_masks), when the pass has any.
+static pa_status quality_prepass(pa_index *idx, const pa_reads *r, AlignArgs &a, hipStream_t st) {
+    if (!(a.prm.flags & (F_MRQ | F_MKQ))) return PA_OK;
+    if (idx->k > 95) {  // (k_quality_masks realigns by k >> 2 <= 23: the lane path implies k <= 95)
+        set_error("internal: quality pre-pass for k > 95");
+        return PA_EINTERNAL;
+    }
+    PA_TRY(ensure_qmask(idx, r->n));
+    KernelTimer kt(idx, st, PA_PROF_QUALITY);
+    hipLaunchKernelGGL(idx->k > 63 ? k_quality_masks<true> : k_quality_masks<false>,
+                       dim3((unsigned)std::min<uint64_t>((r->n + 255) / 256, 65536)), dim3(256), 0, st, r->qual, r->off,
+                       r->n, (int)idx->k, (int64_t)a.prm.mrq, (int64_t)a.prm.mkq, a.prm.flags & (F_MRQ | F_MKQ),
+                       idx->qmask, idx->qdrop);
+    PA_HIP(hipGetLastError());
+    a.qmask = idx->qmask;
+    a.qdrop = idx->qdrop;
+    return PA_OK;
+}
+
+// The queues of the reads without a seed in the index (k_align_lane_na, with
+// a Bloom filter; two- and three-word keys: k_align_lane_naw), of their
+// reverse-complement seeds (k_rc_seeds -> k_align_lane_rc: with the
+// reverse-complement plane) and the lane kernel's claim counter, zeroed.
+static pa_status seedless_queues(pa_index *idx, AlignArgs &a, const Switches &sw, hipStream_t st) {
+    const bool na = a.lane_noanchor && idx->nw <= 3;
+    a.queue_na = na ? idx->queue_na : nullptr;
+    a.queue_na_count = idx->na_count;
+    a.queue_na_keys = na && a.tile_rcp && a.bloom ? idx->queue_na_keys : nullptr;
+    a.queue_rc = idx->queue_rc;
+    a.queue_rc_anc = idx->queue_rc_anc;
+    a.queue_rc_count = idx->na_count + 1;
+    a.seg_cnt = idx->seg_cnt;
+    a.queue_cap = idx->queue_cap;
+    a.queue_na2 = idx->queue_na2;
+    a.queue_na2_count = idx->na_count + 2;
+    a.na_min = sw.na_min;
+    a.lane_next = (uint32_t *)(idx->na_count + 3);
+    // (the queue counts and the claims in one; without the seedless path only for the claims)
+    if (na || PA_LANE_CLAIM) PA_HIP(hipMemsetAsync(idx->na_count, 0, 32, st));
+    return PA_OK;
+}
+
+#ifdef PA_STATS
+static pa_status print_stats(pa_index *idx, const pa_reads *r, hipStream_t st) {
+    unsigned long long d[40];
+    PA_HIP(hipMemcpyAsync(d, idx->counters, sizeof d, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
+    fprintf(stderr, "[pa_stats] reads %llu lane-hard %llu exact %llu | wave kernel: windows %llu probed %llu walk %llu anchors %llu\n",
+            (unsigned long long)r->n, d[3], d[0], d[4], d[5], d[6], d[7]);
+    fprintf(stderr, "[pa_stats] lane hard reasons: long %llu mkq %llu bad %llu no-anchor %llu range %llu mismatches %llu rep %llu found %llu pending %llu\n",
+            d[8], d[9], d[10], d[11], d[12], d[13], d[14], d[15], d[16]);
+    fprintf(stderr, "[pa_stats] lane: cooperative probes %llu re-anchors %llu neighbour words %llu | pending: invalid %llu "
+            "2+ mismatches %llu neighbour present %llu\n", d[18], d[19], d[20], d[21], d[22], d[23]);
+    fprintf(stderr, "[pa_stats] lane: single-probe re-anchors %llu second walks given up unprobed %llu\n", d[32], d[33]);
+    fprintf(stderr, "[pa_stats] lane found: shared-neighbour+specific %llu second-walk specific %llu probed-shared+specific %llu"
+            " | unique by bound %llu, by off-walk counts %llu | probes past the Bloom filter %llu\n", d[24], d[25], d[26], d[27], d[28],
+            d[29]);
+    fprintf(stderr, "[pa_stats] lane seeds: anchor ranked among stretches %llu, second seed round %llu\n", d[30], d[31]);
+    return PA_OK;
+}
+#endif
 
 // One pass over a batch.  as == nullptr: the counter pass into acc (pa_align).
 // as: the assign pass's first half (assign_classify) -- the lane kernels write
@@ -1218,23 +1378,18 @@ static pa_status align_pass(pa_index *idx, const pa_reads *r, const DevParams &p
                   ": a batch holds at most 2^32 - 2 reads (split it; read_index_base keeps the order)");
         return PA_EUNSUPPORTED;
     }
+    const Switches sw;
     PA_TRY(index_note_reads(idx, r->n, st));  // (the neighbour bits, once enough reads came)
     PA_TRY(reserve_queues(idx, r->n));
     DevParams p;
-    PA_TRY(effective_params(r, p_in, p, st));
-    AlignArgs a = make_args(idx, r, p, base);
+    PA_TRY(effective_params(r, p_in, p, st, sw));
+    AlignArgs a = make_args(idx, r, p, base, sw);
     const uint32_t G = idx->n_genomes;
     a.stats = (unsigned long long *)(as ? as->scratch : acc->sum_block);
     a.uniq = a.stats + 6;
     a.amb = a.uniq + G;
     a.first = as ? a.amb + G : (unsigned long long *)acc->min_block;
-    if (as) {
-        a.as_type = as->type;
-        a.as_len = as->len;
-        a.as_g = as->g;
-        a.as_qf = as->qf;
-        a.as_hr = as->hr;
-    }
+    if (as) a.as_type = as->type, a.as_len = as->len, a.as_g = as->g, a.as_qf = as->qf, a.as_hr = as->hr;
     a.queue = idx->queue;
     a.qcount = (unsigned long long *)idx->counters;
     a.deferred_total = (unsigned long long *)idx->counters + 1;
@@ -1243,140 +1398,36 @@ static pa_status align_pass(pa_index *idx, const pa_reads *r, const DevParams &p
 #ifdef PA_STATS
     PA_HIP(hipMemsetAsync(a.dbg, 0, 36 * 8, st));
 #endif
-    ExactArgs x{};
+    const DetailOut out{as ? as->type : nullptr, as ? as->qf : nullptr, as ? as->hr : nullptr, as ? as->len : nullptr,
+                        nullptr, nullptr};
+    ExactArgs x;
     unsigned egrid = 0;
-    PA_TRY(prepare_exact(idx, r, x, egrid));
-    x.a = a;
-    x.detail = as ? 1 : 0;
-    if (as) {
-        x.type_out = as->type;
-        x.qf_out = as->qf;
-        x.hr_out = as->hr;
-        x.len_out = as->len;
-    }
+    PA_TRY(exact_args(idx, r, a, as ? &out : nullptr, x, egrid));
     const bool fast_ok = idx->k > 0 && idx->nw <= 4 && idx->n_kmers > 0;  // (k <= 127: the wave kernel's keys)
-    // the lane kernel first (single-word keys on a tiled index); PA_NO_LANE=1 skips it
-    const char *no_lane = std::getenv("PA_NO_LANE");
-    const bool lane_ok = fast_ok && idx->nw <= 3 && a.tile_n > 0 && a.tile_lw && !(no_lane && no_lane[0] == '1') &&
-                         (!as || as->lane);
+    // the lane kernels first (keys of up to three words on a tiled index)
+    const bool lane_ok = fast_ok && idx->nw <= 3 && a.tile_n > 0 && a.tile_lw && !sw.no_lane && (!as || as->lane);
     if (queued) *queued = as && lane_ok;
     if (as ? lane_ok : fast_ok) {
-        const uint32_t wmax = r->max_len >= idx->k ? (uint32_t)(r->max_len - idx->k + 1) : 0;
-        const int wpl = wmax <= 64 ? 1 : wmax <= 128 ? 2 : 4;  // longer reads are deferred by WPL=4
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (idx->profile) {
             PA_HIP(hipEventCreate(&e0));
             PA_HIP(hipEventCreate(&e1));
             PA_HIP(hipEventRecord(e0, st));
         }
-        if (lane_ok) {
-            if ((a.prm.flags & F_MG) && a.prm.mg >= 2) {
-                const uint64_t n_words = a.tile_n / 64 + 8;  // (padded: the 250-bp walk reads five words from any position)
-                if (!idx->tile_big) PA_HIP(pa::dev_malloc(&idx->tile_big, n_words * 8));
-                if (idx->tile_big_mg != a.prm.mg) {
-                    hipLaunchKernelGGL(k_tile_big, dim3((unsigned)std::min<uint64_t>((n_words + 3) / 4, 1u << 20)),
-                                       dim3(256), 0, st, idx->tile_cls, a.tile_n, a.G, idx->class_genomes,
-                                       (int32_t)a.prm.mg, idx->tile_big, n_words);
-                    PA_HIP(hipGetLastError());
-                    idx->tile_big_mg = a.prm.mg;
-                }
-                a.tile_big = idx->tile_big;
-                // the neighbour bits' set-size half for this mg (12 B per base;
-                // only with the 24-B neighbour bits, and when it fits)
-                if (idx->tile_nb && idx->nb_spec && !idx->tile_nb1 && !std::getenv("PA_NO_NBBIG")) {
-                    const uint64_t nw = 3 * a.tile_n;
-                    if (!idx->tile_nbbig) {
-                        size_t free_b = 0, total_b = 0;
-                        if (pa::dev_mem_info(&free_b, &total_b) == hipSuccess && nw * 4 + (8ull << 30) < free_b &&
-                            pa::dev_malloc(&idx->tile_nbbig, nw * 4 + 64) == hipSuccess) {
-                            idx->tile_nbbig_mg = -1;
-                            idx->device_bytes += nw * 4 + 64;  // (pa_index_get_info reports the real footprint)
-                        } else
-                            idx->tile_nbbig = nullptr;
-                        (void)hipGetLastError();
-                    }
-                    if (idx->tile_nbbig && idx->tile_nbbig_mg != a.prm.mg) {
-                        hipLaunchKernelGGL(k_nb_big, dim3((unsigned)std::min<uint64_t>((nw + 255) / 256, 1u << 20)),
-                                           dim3(256), 0, st, idx->tile_pk, (const uint64_t *)idx->tile_nb, nw, (int)idx->k,
-                                           (const Slot<1> *)idx->table, idx->home, a.G, idx->class_genomes,
-                                           (int32_t)a.prm.mg, idx->tile_nbbig);
-                        PA_HIP(hipGetLastError());
-                        idx->tile_nbbig_mg = a.prm.mg;
-                    }
-                    a.tile_nbbig = idx->tile_nbbig;
-                    if (a.tile_nbbig) a.nbbig_ld = a.tile_nbbig, a.nbbig_mask = ~0ull;
-                    // interleaved with the neighbour words (48 B per base, when it fits; PA_NO_NBM=1: none)
-                    if (idx->tile_nbbig && !std::getenv("PA_NO_NBM")) {
-                        if (!idx->tile_nbm) {
-                            size_t free_b = 0, total_b = 0;
-                            if (pa::dev_mem_info(&free_b, &total_b) == hipSuccess && nw * 16 + (8ull << 30) < free_b &&
-                                pa::dev_malloc(&idx->tile_nbm, nw * 16 + 64) == hipSuccess) {
-                                idx->tile_nbm_mg = -1;
-                                idx->device_bytes += nw * 16 + 64;
-                            } else
-                                idx->tile_nbm = nullptr;
-                            (void)hipGetLastError();
-                        }
-                        if (idx->tile_nbm && idx->tile_nbm_mg != a.prm.mg) {
-                            hipLaunchKernelGGL(k_nb_merge, dim3((unsigned)std::min<uint64_t>((nw + 255) / 256, 1u << 20)),
-                                               dim3(256), 0, st, (const uint64_t *)idx->tile_nb, idx->tile_nbbig, nw,
-                                               idx->tile_nbm);
-                            PA_HIP(hipGetLastError());
-                            idx->tile_nbm_mg = a.prm.mg;
-                        }
-                        a.tile_nbm = idx->tile_nbm;
-                    }
-                }
-            }
-            // every present neighbour's set size vs mg known from the bits
-            a.mg_nb = (a.prm.flags & F_MG) && a.tile_nb && a.nb_spec && (a.prm.mg < 2 || a.tile_nbbig) &&
-                      !std::getenv("PA_NO_MGNB");
+        if (lane_ok) {  // the lane chain; what it leaves is in queue_hard
+            PA_TRY(mg_planes(idx, a, sw, st));
             a.queue_hard = idx->queue_hard;
             a.queue_hard_count = (unsigned long long *)idx->counters + 3;
             PA_HIP(hipMemsetAsync(idx->counters + 3, 0, 8, st));
-            if (a.prm.flags & (F_MRQ | F_MKQ)) {  // the quality filters of every read, up front
-                if (idx->k > 95) {  // (k_quality_masks realigns by k >> 2 <= 23: lane_ok implies k <= 95)
-                    set_error("internal: quality pre-pass for k > 95");
-                    return PA_EINTERNAL;
-                }
-                PA_TRY(ensure_qmask(idx, r->n));
-                KernelTimer kt(idx, st, PA_PROF_QUALITY);
-                hipLaunchKernelGGL(idx->k > 63 ? k_quality_masks<true> : k_quality_masks<false>, dim3((unsigned)std::min<uint64_t>((r->n + 255) / 256, 65536)),
-                                   dim3(256), 0, st, r->qual, r->off, r->n, (int)idx->k, (int64_t)a.prm.mrq,
-                                   (int64_t)a.prm.mkq, a.prm.flags & (F_MRQ | F_MKQ), idx->qmask, idx->qdrop);
-                PA_HIP(hipGetLastError());
-                a.qmask = idx->qmask;
-                a.qdrop = idx->qdrop;
-            }
-            // reads without a seed in the index: k_align_lane_na (with a Bloom filter; PA_LANE_NOANCHOR=0/1)
-            bool na = a.bloom != nullptr;
-            if (const char *e = std::getenv("PA_LANE_NOANCHOR")) na = e[0] == '1';
-            if (idx->nw > 3) na = false;  // (two- and three-word keys: k_align_lane_naw)
-            a.queue_na = na ? idx->queue_na : nullptr;
-            a.queue_na_count = idx->na_count;
-            // their reverse-complement seeds (k_rc_seeds -> k_align_lane_rc):
-            // with the reverse-complement plane (PA_NA_RCWALK=0: none)
-            const bool rcw = na && a.tile_rcp && a.bloom;
-            a.queue_na_keys = rcw ? idx->queue_na_keys : nullptr;
-            a.queue_rc = idx->queue_rc;
-            a.queue_rc_anc = idx->queue_rc_anc;
-            a.queue_rc_count = idx->na_count + 1;
-            a.seg_cnt = idx->seg_cnt;
-            a.queue_cap = idx->queue_cap;
-            a.queue_na2 = idx->queue_na2;
-            a.queue_na2_count = idx->na_count + 2;
-            a.na_min = 32768;  // (PA_NA_MIN: tests)
-            if (const char *e = std::getenv("PA_NA_MIN")) a.na_min = std::strtoull(e, nullptr, 10);
-            a.lane_next = (uint32_t *)(idx->na_count + 3);
-            // (the queue counts and the claims in one; without the seedless path only for the claims)
-            if (na || PA_LANE_CLAIM) PA_HIP(hipMemsetAsync(idx->na_count, 0, 32, st));
+            PA_TRY(quality_prepass(idx, r, a, st));
+            PA_TRY(seedless_queues(idx, a, sw, st));
             // the 250-bp shape when any read is longer than the 150-bp one
             // takes: 176 bases or 128 windows (round 6: reads of 159-176 bases
             // at k = 31 went whole to the wave kernel, 0.15 G reads/s)
             const bool long_reads = r->max_len > (uint32_t)kLaneMaxLen ||
                                     (r->max_len >= idx->k && r->max_len - idx->k + 1 > (uint32_t)kLaneMaxW);
-            PA_TRY(as ? launch_lane<true>(a, st, idx, long_reads, idx->nw)
-                      : launch_lane<false>(a, st, idx, long_reads, idx->nw));
+            PA_TRY(as ? launch_lane<true>(a, sw, st, idx, long_reads, idx->nw)
+                      : launch_lane<false>(a, sw, st, idx, long_reads, idx->nw));
             a.rlist = idx->queue_hard;
             a.rlist_count = a.queue_hard_count;
         }
@@ -1384,12 +1435,10 @@ static pa_status align_pass(pa_index *idx, const pa_reads *r, const DevParams &p
             a.queue = idx->queue_hard;
             a.qcount = a.queue_hard_count;
             a.deferred_total = nullptr;
-        } else {
-            KernelTimer kt(idx, st, PA_PROF_WAVE);
-            PA_TRY(idx->nw == 1   ? launch_fast_wpl<1>(a, wpl, st)
-                   : idx->nw == 2 ? launch_fast_wpl<2>(a, wpl, st)
-                   : idx->nw == 3 ? launch_fast_wpl<3>(a, wpl, st)
-                                  : launch_fast_wpl<4>(a, wpl, st));
+        } else {  // the wave kernel: the remainder, or every read; what it defers is in queue
+            const uint32_t wmax = r->max_len >= idx->k ? (uint32_t)(r->max_len - idx->k + 1) : 0;
+            const int wpl = wmax <= 64 ? 1 : wmax <= 128 ? 2 : 4;  // longer reads are deferred by WPL=4
+            PA_TRY(launch_wave(a, idx, idx->nw, wpl, st));
         }
         if (idx->profile) {
             PA_HIP(hipEventRecord(e1, st));
@@ -1398,29 +1447,10 @@ static pa_status align_pass(pa_index *idx, const pa_reads *r, const DevParams &p
         }
         x.a = a;
         x.use_queue = 1;
-    } else {
-        x.use_queue = 0;
     }
-    {
-        KernelTimer kt(idx, st, PA_PROF_EXACT);
-        launch_exact_nw(idx->nw, x, egrid, st);
-        PA_HIP(hipGetLastError());
-    }
+    PA_TRY(launch_exact(idx, idx->nw, x, egrid, st));  // the queue, or every read
 #ifdef PA_STATS
-    unsigned long long d[40];
-    PA_HIP(hipMemcpyAsync(d, idx->counters, sizeof d, hipMemcpyDeviceToHost, st));
-    PA_HIP(hipStreamSynchronize(st));
-    fprintf(stderr, "[pa_stats] reads %llu lane-hard %llu exact %llu | wave kernel: windows %llu probed %llu walk %llu anchors %llu\n",
-            (unsigned long long)r->n, d[3], d[0], d[4], d[5], d[6], d[7]);
-    fprintf(stderr, "[pa_stats] lane hard reasons: long %llu mkq %llu bad %llu no-anchor %llu range %llu mismatches %llu rep %llu found %llu pending %llu\n",
-            d[8], d[9], d[10], d[11], d[12], d[13], d[14], d[15], d[16]);
-    fprintf(stderr, "[pa_stats] lane: cooperative probes %llu re-anchors %llu neighbour words %llu | pending: invalid %llu "
-            "2+ mismatches %llu neighbour present %llu\n", d[18], d[19], d[20], d[21], d[22], d[23]);
-    fprintf(stderr, "[pa_stats] lane: single-probe re-anchors %llu second walks given up unprobed %llu\n", d[32], d[33]);
-    fprintf(stderr, "[pa_stats] lane found: shared-neighbour+specific %llu second-walk specific %llu probed-shared+specific %llu"
-            " | unique by bound %llu, by off-walk counts %llu | probes past the Bloom filter %llu\n", d[24], d[25], d[26], d[27], d[28],
-            d[29]);
-    fprintf(stderr, "[pa_stats] lane seeds: anchor ranked among stretches %llu, second seed round %llu\n", d[30], d[31]);
+    PA_TRY(print_stats(idx, r, st));
 #endif
     return PA_OK;
 }
@@ -1440,28 +1470,35 @@ pa_status assign_classify(pa_index *idx, const pa_reads *r, const DevParams &p, 
 pa_status assign_lists(pa_index *idx, const pa_reads *r, const DevParams &p_in, const AssignBufs &as, bool queued,
                        const uint64_t *d_off, uint32_t *d_lists, hipStream_t st) {
     if (r->n == 0) return PA_OK;
+    const Switches sw;
     DevParams p;
-    PA_TRY(effective_params(r, p_in, p, st));
-    ExactArgs x{};
+    PA_TRY(effective_params(r, p_in, p, st, sw));
+    AlignArgs a = make_args(idx, r, p, 0, sw);
+    a.queue = idx->queue_hard;
+    a.qcount = (unsigned long long *)idx->counters + 3;
+    const DetailOut out{as.type, as.qf, as.hr, as.len, d_off, d_lists};
+    ExactArgs x;
     unsigned egrid = 0;
-    PA_TRY(prepare_exact(idx, r, x, egrid));
-    x.a = make_args(idx, r, p, 0);
-    x.a.queue = idx->queue_hard;
-    x.a.qcount = (unsigned long long *)idx->counters + 3;
+    PA_TRY(exact_args(idx, r, a, &out, x, egrid));
     x.use_queue = queued ? 1 : 0;
-    x.type_out = as.type;
-    x.qf_out = as.qf;
-    x.hr_out = as.hr;
-    x.len_out = as.len;
-    x.detail = 2;
-    x.list_off = d_off;
-    x.lists = d_lists;
-    KernelTimer kt(idx, st, PA_PROF_EXACT);
-    launch_exact_nw(idx->nw, x, egrid, st);
-    PA_HIP(hipGetLastError());
-    return PA_OK;
+    return launch_exact(idx, idx->nw, x, egrid, st);
 }
 
+// The detail pass over every read with everything left on the device: without
+// d_lists the per-read type, filter counts and list length; with d_off and
+// d_lists the lists too.
+pa_status detail_pass_device(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *d_type, uint32_t *d_qf,
+                             uint32_t *d_hr, uint32_t *d_len, const uint64_t *d_off, uint32_t *d_lists,
+                             hipStream_t st) {
+    if (r->n == 0) return PA_OK;
+    const DetailOut out{d_type, d_qf, d_hr, d_len, d_off, d_lists};
+    ExactArgs x;
+    unsigned egrid = 0;
+    PA_TRY(exact_args(idx, r, make_args(idx, r, p, 0, Switches{}), &out, x, egrid));
+    return launch_exact(nullptr, idx->nw, x, egrid, st);  // (not a kernel of the align passes' profile)
+}
+
+// pa_align_detail: a lengths pass, the list offsets by a host scan, a lists pass.
 pa_status align_detail(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *type, uint32_t *qf,
                        uint32_t *hr, uint64_t *list_off, uint32_t *lists, uint64_t list_cap, uint64_t *list_total,
                        hipStream_t st) {
@@ -1469,25 +1506,17 @@ pa_status align_detail(pa_index *idx, const pa_reads *r, const DevParams &p, uin
     if (list_off) list_off[0] = 0;
     if (list_total) *list_total = 0;
     if (n == 0) return PA_OK;
-    ExactArgs x{};
-    unsigned egrid = 0;
-    PA_TRY(prepare_exact(idx, r, x, egrid));
-    x.a = make_args(idx, r, p, 0);
-    x.use_queue = 0;
-    uint8_t *d_type = nullptr;
-    uint32_t *d_qf = nullptr, *d_hr = nullptr, *d_len = nullptr, *d_lists = nullptr;
-    uint64_t *d_off = nullptr;
-    PA_HIP(pa::dev_malloc(&d_type, n));
-    PA_HIP(pa::dev_malloc(&d_qf, n * 4));
-    PA_HIP(pa::dev_malloc(&d_hr, n * 4));
-    PA_HIP(pa::dev_malloc(&d_len, n * 4));
-    x.type_out = d_type;
-    x.qf_out = d_qf;
-    x.hr_out = d_hr;
-    x.len_out = d_len;
-    x.detail = 1;
-    launch_exact_nw(idx->nw, x, egrid, st);
-    PA_HIP(hipGetLastError());
+    struct Bufs {  // the device buffers, freed on every return (once the stream is done with them)
+        hipStream_t st;
+        unsigned char *per_read = nullptr;  // qf | hr | len | type
+        uint64_t *off = nullptr;
+        uint32_t *lists = nullptr;
+        ~Bufs() { (void)hipStreamSynchronize(st), pa::dev_free(per_read), pa::dev_free(off), pa::dev_free(lists); }
+    } d{st};
+    PA_HIP(pa::dev_malloc(&d.per_read, n * 13));
+    uint32_t *d_qf = (uint32_t *)d.per_read, *d_hr = d_qf + n, *d_len = d_hr + n;
+    uint8_t *d_type = (uint8_t *)(d_len + n);
+    PA_TRY(detail_pass_device(idx, r, p, d_type, d_qf, d_hr, d_len, nullptr, nullptr, st));
     std::vector<uint32_t> lens(n);
     PA_HIP(hipMemcpyAsync(lens.data(), d_len, n * 4, hipMemcpyDeviceToHost, st));
     PA_HIP(hipMemcpyAsync(type, d_type, n, hipMemcpyDeviceToHost, st));
@@ -1499,46 +1528,17 @@ pa_status align_detail(pa_index *idx, const pa_reads *r, const DevParams &p, uin
     const uint64_t total = offs[n];
     if (list_total) *list_total = total;
     if (list_off) std::memcpy(list_off, offs.data(), (n + 1) * 8);
-    pa_status rc = PA_OK;
-    if (lists && total > 0) {
-        if (list_cap < total) {
-            set_error("pa_align_detail: list_cap smaller than the required list length");
-            rc = PA_EINVAL;
-        } else {
-            PA_HIP(pa::dev_malloc(&d_off, (n + 1) * 8));
-            PA_HIP(pa::dev_malloc(&d_lists, total * 4));
-            PA_HIP(hipMemcpyAsync(d_off, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-            x.detail = 2;
-            x.list_off = d_off;
-            x.lists = d_lists;
-            launch_exact_nw(idx->nw, x, egrid, st);
-            PA_HIP(hipGetLastError());
-            PA_HIP(hipMemcpyAsync(lists, d_lists, total * 4, hipMemcpyDeviceToHost, st));
-            PA_HIP(hipStreamSynchronize(st));
-        }
+    if (!lists || total == 0) return PA_OK;
+    if (list_cap < total) {
+        set_error("pa_align_detail: list_cap smaller than the required list length");
+        return PA_EINVAL;
     }
-    pa::dev_free(d_type); pa::dev_free(d_qf); pa::dev_free(d_hr); pa::dev_free(d_len); pa::dev_free(d_off); pa::dev_free(d_lists);
-    return rc;
-}
-
-pa_status detail_pass_device(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *d_type, uint32_t *d_qf,
-                             uint32_t *d_hr, uint32_t *d_len, const uint64_t *d_off, uint32_t *d_lists,
-                             hipStream_t st) {
-    if (r->n == 0) return PA_OK;
-    ExactArgs x{};
-    unsigned egrid = 0;
-    PA_TRY(prepare_exact(idx, r, x, egrid));
-    x.a = make_args(idx, r, p, 0);
-    x.use_queue = 0;
-    x.type_out = d_type;
-    x.qf_out = d_qf;
-    x.hr_out = d_hr;
-    x.len_out = d_len;
-    x.detail = d_lists ? 2 : 1;
-    x.list_off = d_off;
-    x.lists = d_lists;
-    launch_exact_nw(idx->nw, x, egrid, st);
-    PA_HIP(hipGetLastError());
+    PA_HIP(pa::dev_malloc(&d.off, (n + 1) * 8));
+    PA_HIP(pa::dev_malloc(&d.lists, total * 4));
+    PA_HIP(hipMemcpyAsync(d.off, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    PA_TRY(detail_pass_device(idx, r, p, d_type, d_qf, d_hr, d_len, d.off, d.lists, st));
+    PA_HIP(hipMemcpyAsync(lists, d.lists, total * 4, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     return PA_OK;
 }
 
