@@ -788,6 +788,73 @@ pa_status pa_align_placements(const pa_index *idx, const pa_reads *reads, const 
                               list_cap, list_total, as_stream(stream));
 }
 
+// ---- pileup (csrc/pa_pileup.hip) ------------------------------------------------------
+
+pa_status pa_pileup_create(const pa_index *idx, pa_pileup **out) {
+    PA_CHECK(idx && out, PA_EINVAL, "NULL argument");
+    *out = nullptr;
+    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_HIP(hipSetDevice(idx->device));
+    return pa::pileup_create(idx, out);
+}
+
+pa_status pa_pileup_reset(pa_pileup *p, void *stream) {
+    PA_CHECK(p != nullptr, PA_EINVAL, "NULL argument");
+    PA_HIP(hipSetDevice(p->device));
+    return pa::pileup_reset(p, as_stream(stream));
+}
+
+pa_status pa_pileup_add(const pa_index *idx, const pa_reads *reads, const pa_params *params,
+                        uint32_t min_base_quality, pa_pileup *acc, void *stream) {
+    PA_CHECK(idx && reads && acc, PA_EINVAL, "NULL argument");
+    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
+    PA_CHECK(acc->idx == idx && acc->epoch == idx->epoch, PA_EINVAL,
+             "the pa_pileup was made for another index, or for this one before a pa_index_reduce");
+    pa::DevParams dp;
+    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    PA_CHECK(acc->reads_added + reads->n < (1ull << 32), PA_EUNSUPPORTED,
+             "a pa_pileup holds fewer than 2^32 reads (its counts are 32-bit)");
+    PA_HIP(hipSetDevice(idx->device));
+    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    return pa::pileup_add(const_cast<pa_index *>(idx), reads, dp, min_base_quality, acc, as_stream(stream));
+}
+
+pa_status pa_pileup_stats_get(const pa_pileup *p, pa_pileup_stats *out, void *stream) {
+    PA_CHECK(p && out, PA_EINVAL, "NULL argument");
+    PA_HIP(hipSetDevice(p->device));
+    return pa::pileup_stats(p, out, as_stream(stream));
+}
+
+pa_status pa_pileup_counts(const pa_pileup *p, uint32_t genome, uint64_t first, uint64_t count, uint32_t *acgt,
+                           void *stream) {
+    PA_CHECK(p != nullptr, PA_EINVAL, "NULL argument");
+    PA_CHECK(genome < p->n_genomes, PA_EINVAL, "genome number out of range");
+    const uint64_t len = p->h_foff[genome + 1] - p->h_foff[genome];
+    PA_CHECK(first <= len && count <= len - first, PA_EINVAL, "positions past the end of the genome");
+    PA_CHECK(acgt != nullptr || count == 0, PA_EINVAL, "NULL argument");
+    PA_HIP(hipSetDevice(p->device));
+    return pa::pileup_counts(p, genome, first, count, acgt, as_stream(stream));
+}
+
+pa_status pa_pileup_variants(const pa_pileup *p, uint32_t min_depth, uint32_t min_alt_count,
+                             uint32_t min_alt_permille, pa_variant *out, uint64_t cap, uint64_t *n, void *stream) {
+    PA_CHECK(p && n, PA_EINVAL, "NULL argument");
+    *n = 0;
+    PA_CHECK(min_depth >= 1, PA_EINVAL, "min_depth must be at least 1");
+    PA_CHECK(min_alt_count >= 1, PA_EINVAL, "min_alt_count must be at least 1");
+    PA_CHECK(min_alt_permille <= 1000, PA_EINVAL, "min_alt_permille must be at most 1000");
+    PA_HIP(hipSetDevice(p->device));
+    return pa::pileup_variants(p, min_depth, min_alt_count, min_alt_permille, out, out ? cap : 0, n,
+                               as_stream(stream));
+}
+
+void pa_pileup_free(pa_pileup *p) {
+    if (!p) return;
+    hipSetDevice(p->device);
+    pa::pileup_free(p);
+}
+
 pa_status pa_profile_enable(pa_index *idx, int32_t enable) {
     PA_CHECK(idx != nullptr, PA_EINVAL, "NULL argument");
     idx->profile = enable != 0;

@@ -286,6 +286,7 @@ struct PlaceArgs {
     const uint32_t *lists;
     uint64_t n_entries;
     int64_t *starts;           // [n_entries] (nullable)
+    uint8_t *agree;            // [n_entries] (nullable): 1 where every voting window named the placement's diagonal
     uint32_t *diff;            // the accumulator (nullable): unique category, the ambiguous one `entries` further
     uint64_t entries;
     const uint64_t *foff;      // forward bases before genome g
@@ -425,6 +426,7 @@ __global__ __launch_bounds__(kBlock) void k_place(PlaceArgs a) {
                 best = 0;
             }
             if (a.starts) a.starts[e] = best;
+            if (a.agree) a.agree[e] = best_cnt == votes && votes != 0;
             const uint64_t e0 = a.list_off[r];
             // (a p-demoted list holds G* twice: it counts once)
             if (a.diff && votes != 0 && !(e > e0 && a.lists[e0] == g)) {
@@ -568,53 +570,34 @@ pa_status coverage_reset(pa_coverage *cov, hipStream_t st) {
     return PA_OK;
 }
 
-pa_status coverage_place(pa_index *idx, const pa_reads *r, const DevParams &p, pa_coverage *acc, uint8_t *type,
-                         uint64_t *list_off, uint32_t *lists, int64_t *starts, uint64_t list_cap,
-                         uint64_t *list_total, hipStream_t st) {
-    const char *what = acc ? "pa_coverage_add" : "pa_align_placements";
+void placed_free(PlacedDev &pd) {
+    assign_free(pd.as);
+    pa::dev_free(pd.starts);
+    pa::dev_free(pd.agree);
+    pd = PlacedDev{};
+}
+
+pa_status place_device(pa_index *idx, const pa_reads *r, const DevParams &p, const char *what, pa_coverage *acc,
+                       uint64_t list_cap, bool want_starts, bool want_agree, PlacedDev &out, hipStream_t st) {
+    out = PlacedDev{};
     const uint64_t n = r->n;
-    if (list_off) list_off[0] = 0;
-    if (list_total) *list_total = 0;
     PA_TRY(index_prepare_coverage(idx, st));
     if (n == 0) return PA_OK;
-    int64_t *d_starts = nullptr, *d_ws = nullptr;
+    int64_t *d_ws = nullptr;
     unsigned long long *d_err = nullptr;
-    AssignDev as;
     auto cleanup = [&] {
         (void)hipStreamSynchronize(st);
-        assign_free(as);
-        pa::dev_free(d_starts); pa::dev_free(d_ws); pa::dev_free(d_err);
+        placed_free(out);
+        pa::dev_free(d_ws); pa::dev_free(d_err);
     };
-    const bool want_lists = lists || starts;
     // classification, list offsets and lists: the assign pass, left on the device
-    // (no lists for the *list_total query, or when the caller's capacity is short)
-    pa_status rc = assign_pass_device(idx, r, p, acc ? ~0ull : (want_lists ? list_cap : 0), as, st);
-    if (rc != PA_OK) return rc;
-    uint8_t *d_type = as.type;
-    uint64_t *d_off = as.off;
-    uint32_t *d_lists = as.lists;
-    const uint64_t total = as.total;
+    PA_TRY(assign_pass_device(idx, r, p, list_cap, out.as, st));
+    const uint64_t total = out.as.total;
+    if (total == 0 || !out.as.lists) return PA_OK;  // (nothing listed, or the capacity is short: nothing to place)
     C_HIP(pa::dev_malloc(&d_err, 16));
     C_HIP(hipMemsetAsync(d_err, 0, 16, st));
-    if (type) C_HIP(hipMemcpyAsync(type, d_type, n, hipMemcpyDeviceToHost, st));
-    if (list_off) C_HIP(hipMemcpyAsync(list_off, d_off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-    C_HIP(hipStreamSynchronize(st));
-    if (list_total) *list_total = total;
-    if (!acc && !want_lists) {  // (the query for *list_total)
-        cleanup();
-        return PA_OK;
-    }
-    if (want_lists && list_cap < total) {
-        set_error(std::string(what) + ": list_cap smaller than the required list length");
-        cleanup();
-        return PA_EINVAL;
-    }
-    if (total == 0) {
-        cleanup();
-        if (acc) acc->reads_added += n;
-        return PA_OK;
-    }
-    if (starts) C_HIP(pa::dev_malloc(&d_starts, total * 8));
+    if (want_starts) C_HIP(pa::dev_malloc(&out.starts, total * 8));
+    if (want_agree) C_HIP(pa::dev_malloc(&out.agree, total));
     const uint32_t wmax = r->max_len >= (uint64_t)idx->k ? (uint32_t)(r->max_len - idx->k + 1) : 1;
     const uint32_t rounds = std::max<uint32_t>(1, (wmax + 63) / 64);
     // waves to fill the device (256 CUs x 16) while the lanes' diagonals stay within 64 MiB
@@ -636,11 +619,12 @@ pa_status coverage_place(pa_index *idx, const pa_reads *r, const DevParams &p, p
     a.seq = r->seq;
     a.off = r->off;
     a.n_reads = n;
-    a.type = d_type;
-    a.list_off = d_off;
-    a.lists = d_lists;
+    a.type = out.as.type;
+    a.list_off = out.as.off;
+    a.lists = out.as.lists;
     a.n_entries = total;
-    a.starts = d_starts;
+    a.starts = out.starts;
+    a.agree = out.agree;
     a.diff = acc ? acc->diff : nullptr;
     a.entries = acc ? acc->entries : 0;
     a.foff = acc ? acc->foff : nullptr;
@@ -659,21 +643,58 @@ pa_status coverage_place(pa_index *idx, const pa_reads *r, const DevParams &p, p
         default: launch_place<8>(a, (unsigned)blocks, st); break;
     }
     C_HIP(hipGetLastError());
-    if (acc) {
-        acc->depth_valid = 0;
-        acc->reads_added += n;
-    }
+    if (acc) acc->depth_valid = 0;
     unsigned long long errs[2] = {0, 0};
     C_HIP(hipMemcpyAsync(errs, d_err, 16, hipMemcpyDeviceToHost, st));
-    if (lists) C_HIP(hipMemcpyAsync(lists, d_lists, total * 4, hipMemcpyDeviceToHost, st));
-    if (starts) C_HIP(hipMemcpyAsync(starts, d_starts, total * 8, hipMemcpyDeviceToHost, st));
     C_HIP(hipStreamSynchronize(st));
-    cleanup();
+    pa::dev_free(d_ws);
+    pa::dev_free(d_err);
+    d_ws = nullptr;
+    d_err = nullptr;
     if (errs[0] || errs[1]) {
         set_error(std::string(what) + ": " + std::to_string(errs[0]) + " listed genomes without a voting window, " +
                   std::to_string(errs[1]) + " positions-view entries out of range (invariant violated)");
+        cleanup();
         return PA_EINTERNAL;
     }
+    out.placed = true;
+    return PA_OK;
+}
+
+pa_status coverage_place(pa_index *idx, const pa_reads *r, const DevParams &p, pa_coverage *acc, uint8_t *type,
+                         uint64_t *list_off, uint32_t *lists, int64_t *starts, uint64_t list_cap,
+                         uint64_t *list_total, hipStream_t st) {
+    const char *what = acc ? "pa_coverage_add" : "pa_align_placements";
+    const uint64_t n = r->n;
+    if (list_off) list_off[0] = 0;
+    if (list_total) *list_total = 0;
+    const bool want_lists = lists || starts;
+    PlacedDev pd;
+    auto cleanup = [&] {
+        (void)hipStreamSynchronize(st);
+        placed_free(pd);
+    };
+    // (no lists for the *list_total query, or when the caller's capacity is short)
+    PA_TRY(place_device(idx, r, p, what, acc, acc ? ~0ull : (want_lists ? list_cap : 0), starts != nullptr, false, pd,
+                        st));
+    if (n == 0) return PA_OK;
+    const uint64_t total = pd.as.total;
+    if (acc) acc->reads_added += n;
+    if (type) C_HIP(hipMemcpyAsync(type, pd.as.type, n, hipMemcpyDeviceToHost, st));
+    if (list_off) C_HIP(hipMemcpyAsync(list_off, pd.as.off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    C_HIP(hipStreamSynchronize(st));
+    if (list_total) *list_total = total;
+    if (want_lists && list_cap < total) {
+        set_error(std::string(what) + ": list_cap smaller than the required list length");
+        cleanup();
+        return PA_EINVAL;
+    }
+    if (pd.placed) {
+        if (lists) C_HIP(hipMemcpyAsync(lists, pd.as.lists, total * 4, hipMemcpyDeviceToHost, st));
+        if (starts) C_HIP(hipMemcpyAsync(starts, pd.starts, total * 8, hipMemcpyDeviceToHost, st));
+        C_HIP(hipStreamSynchronize(st));
+    }
+    cleanup();
     return PA_OK;
 }
 

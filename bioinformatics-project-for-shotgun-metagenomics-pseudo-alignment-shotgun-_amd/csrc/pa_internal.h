@@ -212,6 +212,22 @@ struct pa_coverage {
     uint64_t reads_added = 0;
 };
 
+// Base-count accumulator of one index (pa_pileup.hip): four uint32 counts (A, C,
+// G, T) per forward genome base, position x of genome g at 4 (foff[g] + x).
+struct pa_pileup {
+    int device = 0;
+    const pa_index *idx = nullptr;     // the index it was made for, at
+    uint64_t epoch = 0;                //   this build of it
+    uint32_t n_genomes = 0;
+    int both = 0;
+    std::vector<uint64_t> h_foff;      // [G+1] forward bases before genome g
+    uint64_t *foff = nullptr;          // device copy
+    uint32_t *counts = nullptr;        // [4 h_foff[G]]
+    uint8_t *ref = nullptr;            // [h_foff[G]] the forward text's codes (its own copy: the calls outlive a reduce)
+    unsigned long long *stats = nullptr;  // [3] reads piled, reads skipped, bases counted
+    uint64_t reads_added = 0;
+};
+
 struct pa_result {
     int device = 0;
     uint32_t n_genomes = 0;
@@ -310,6 +326,31 @@ pa_status coverage_summary(pa_coverage *cov, uint32_t min_coverage, uint64_t *co
                            uint64_t *sum_a, hipStream_t st);
 pa_status coverage_depth(pa_coverage *cov, uint32_t genome, uint64_t first, uint64_t count, uint32_t *du,
                          uint32_t *da, hipStream_t st);
+// What coverage_place and the pileup pass share (pa_cover.hip): the positions
+// view, the assign pass left on the device, k_place's workspace and launch.
+// as.lists is null and placed false when nothing is listed or as.total >
+// list_cap; else starts / agree (when wanted) hold one value per list entry
+// and, with acc, the depths are accumulated.  Free with placed_free.
+struct PlacedDev {
+    AssignDev as;
+    int64_t *starts = nullptr;  // [as.total] s(read, genome)
+    uint8_t *agree = nullptr;   // [as.total] 1: every voting window named that diagonal
+    bool placed = false;
+};
+pa_status place_device(pa_index *idx, const pa_reads *r, const DevParams &p, const char *what, pa_coverage *acc,
+                       uint64_t list_cap, bool want_starts, bool want_agree, PlacedDev &out, hipStream_t st);
+void placed_free(PlacedDev &pd);
+// pileup (pa_pileup.hip)
+pa_status pileup_create(const pa_index *idx, pa_pileup **out);
+pa_status pileup_reset(pa_pileup *p, hipStream_t st);
+void pileup_free(pa_pileup *p);
+pa_status pileup_add(pa_index *idx, const pa_reads *r, const DevParams &p, uint32_t min_base_quality, pa_pileup *acc,
+                     hipStream_t st);
+pa_status pileup_stats(const pa_pileup *p, pa_pileup_stats *out, hipStream_t st);
+pa_status pileup_counts(const pa_pileup *p, uint32_t genome, uint64_t first, uint64_t count, uint32_t *acgt,
+                        hipStream_t st);
+pa_status pileup_variants(const pa_pileup *p, uint32_t min_depth, uint32_t min_alt_count, uint32_t min_alt_permille,
+                          pa_variant *out, uint64_t cap, uint64_t *n, hipStream_t st);
 pa_status reads_measure(pa_reads *r, hipStream_t st);  // q_min / len_min of a batch (at its creation)
 // the filters an align of batch r applies: quality thresholds no read can fail dropped
 pa_status effective_params(const pa_reads *r, const DevParams &p, DevParams &out, hipStream_t st);

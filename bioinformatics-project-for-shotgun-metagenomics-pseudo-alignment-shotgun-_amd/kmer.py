@@ -624,17 +624,46 @@ def _columnar(container) -> Tuple[List[str], np.ndarray, np.ndarray, np.ndarray]
 _COVERAGE: "weakref.WeakKeyDictionary[PseudoAlignment, Optional[N.Coverage]]" = weakref.WeakKeyDictionary()
 
 
+# Base-count accumulators of the alignments made with pileup=True, kept like
+# _COVERAGE and for the same reason: [accumulator or None, min_base_quality].
+_PILEUP: "weakref.WeakKeyDictionary[PseudoAlignment, list]" = weakref.WeakKeyDictionary()
+
+VARIANTS_HEADER = "#genome\tposition\tref\talt\tdepth\talt_count\tA\tC\tG\tT\n"
+
+
+def variant_permille(min_alt_fraction) -> int:
+    """The per-mille integer the device's calling rule uses for a fraction:
+    round(1000 * f), converted once, so the rule itself stays integer
+    (1000 * alt_count >= permille * depth)."""
+    if isinstance(min_alt_fraction, bool) or not isinstance(min_alt_fraction, (int, float)) \
+            or not 0 <= min_alt_fraction <= 1:
+        raise ValueError("min_alt_fraction must be a number in 0 .. 1")
+    return int(round(1000 * min_alt_fraction))
+
+
 class PseudoAlignment:
     """Pseudo-alignment of reads against a KmerReference (src/kmer.py:532-699).
 
     ``coverage=True`` (not in the reference, which leaves its EXTCOVERAGE
     extension out): every batch aligned through the host-parsed path is also
     placed on the genomes it maps to, and ``get_coverage`` reports the depth
-    and breadth per genome."""
+    and breadth per genome.
 
-    def __init__(self, kmer_reference: KmerReference, coverage: bool = False) -> None:
+    ``pileup=True`` (not in the reference either): the bases of every uniquely
+    mapped read of those batches are counted per genome position -- those of
+    quality byte >= ``min_base_quality`` when given -- and ``get_variants`` /
+    ``write_variants`` report the positions where the sample differs from the
+    reference."""
+
+    def __init__(self, kmer_reference: KmerReference, coverage: bool = False, pileup: bool = False,
+                 min_base_quality: Optional[int] = None) -> None:
         if coverage:
             _COVERAGE[self] = None  # (the accumulator is made with the first batch)
+        if min_base_quality is not None and (isinstance(min_base_quality, bool)
+                                             or not isinstance(min_base_quality, int) or min_base_quality < 0):
+            raise ValueError("min_base_quality must be a non-negative integer")
+        if pileup:
+            _PILEUP[self] = [None, min(min_base_quality or 0, 256)]
         self.kmer_reference: KmerReference = kmer_reference
         self.filtered_quality_reads: int = 0
         self.filtered_quality_kmers: int = 0
@@ -716,7 +745,8 @@ class PseudoAlignment:
         (N.FastqPrefetch, started before the index build); consumed here."""
         from data_file import FASTAQFile
         # (a coverage job takes the host-parsed path: the placements need the read columns)
-        fresh = not self._batches and not self._host and self._result is None and self not in _COVERAGE
+        fresh = (not self._batches and not self._host and self._result is None and self not in _COVERAGE
+                 and self not in _PILEUP)
         err = _check_align_args(self.kmer_reference, m, p, min_read_quality, min_kmer_quality, max_genomes)
         n = None
         if fresh and err is None and os.environ.get("PA_STREAM", "1") != "0":
@@ -792,6 +822,8 @@ class PseudoAlignment:
             stats, _, _, _ = self._result.fetch()
             if self in _COVERAGE:
                 self._coverage().add(reads, prm)
+            if self in _PILEUP:
+                self._pileup().add(reads, prm, _PILEUP[self][1])
             reads.close()
             delta = stats - self._gpu_stats
             self._gpu_stats = stats
@@ -946,6 +978,47 @@ class PseudoAlignment:
                 du, da = cov.depth(g)
                 out["Details"][name] = {"unique_cov": [int(x) for x in du], "ambiguous_cov": [int(x) for x in da]}
         return out
+
+    def _pileup(self) -> "N.Pileup":
+        slot = _PILEUP[self]
+        if slot[0] is None:
+            slot[0] = N.Pileup(self.kmer_reference.index)
+        return slot[0]
+
+    def _variant_records(self, min_depth, min_alt_count, min_alt_fraction):
+        if self not in _PILEUP:
+            raise ValueError("this alignment was made without pileup=True")
+        for v, name in ((min_depth, "min_depth"), (min_alt_count, "min_alt_count")):
+            if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v < 2 ** 32:
+                raise ValueError(f"{name} must be an integer of at least 1")
+        return self._pileup().variants(min_depth, min_alt_count, variant_permille(min_alt_fraction))
+
+    def get_variants(self, min_depth: int = 4, min_alt_count: int = 2,
+                     min_alt_fraction: float = 0.2) -> List[Dict[str, Any]]:
+        """The positions where the uniquely mapped reads differ from the reference:
+        one ``{"genome", "position", "ref", "alt", "depth", "alt_count", "A", "C",
+        "G", "T"}`` per (position, alternative base) with depth >= ``min_depth``,
+        alt_count >= ``min_alt_count`` and alt_count / depth >= ``min_alt_fraction``,
+        ordered by genome (FASTA order), position (0-based, forward) and base.
+        The fraction becomes the integer round(1000 * min_alt_fraction) once
+        (variant_permille) and the device compares 1000 * alt_count with it times
+        depth.  ValueError for an alignment made without ``pileup=True`` (or
+        loaded from a file)."""
+        names = [g.identifier for g in self.kmer_reference.genomes]
+        out = []
+        for v in self._variant_records(min_depth, min_alt_count, min_alt_fraction):
+            a = [int(x) for x in v["acgt"]]
+            out.append({"genome": names[int(v["genome"])], "position": int(v["position"]),
+                        "ref": "ACGT"[int(v["ref"])], "alt": "ACGT"[int(v["alt"])], "depth": int(v["depth"]),
+                        "alt_count": int(v["alt_count"]), "A": a[0], "C": a[1], "G": a[2], "T": a[3]})
+        return out
+
+    def write_variants(self, fh, min_depth: int = 4, min_alt_count: int = 2, min_alt_fraction: float = 0.2) -> None:
+        """get_variants as text: VARIANTS_HEADER, then one tab-separated line per record."""
+        fh.write(VARIANTS_HEADER)
+        fh.writelines("\t".join(str(v[c]) for c in ("genome", "position", "ref", "alt", "depth", "alt_count",
+                                                    "A", "C", "G", "T")) + "\n"
+                      for v in self.get_variants(min_depth, min_alt_count, min_alt_fraction))
 
     def get_reads_by_mapping_type(self, mapping_type: ReadMappingType) -> List[str]:
         return [rid for rid, d in self.reads.items() if d["mapping_type"] == mapping_type]

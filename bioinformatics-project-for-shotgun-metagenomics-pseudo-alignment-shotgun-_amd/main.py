@@ -6,6 +6,8 @@
                     [--filter-similar [--similarity-threshold T]]
                     [--coverage [--genomes a,b,c] [--min-coverage N] [--full-coverage]]
                     [--assignments FILE]
+                    [--variants FILE [--variant-min-depth N] [--variant-min-count N]
+                     [--variant-min-fraction F] [--variant-min-base-quality Q]]
 
 Same tasks (reference | dumpref | align | dumpalign), flags, flag-combination
 checks, default coercions and error exits as src/main.py:61-402:
@@ -66,6 +68,20 @@ def _has_assignments_flag(argv: List[str]) -> bool:
     return False
 
 
+_VARIANT_FLAGS = ("--variants", "--variant-min-depth", "--variant-min-count", "--variant-min-fraction",
+                  "--variant-min-base-quality")
+
+
+def _has_variants_flag(argv: List[str]) -> bool:
+    """A --variants / --variant-* flag on the command line, in any spelling
+    argparse accepts (as _has_coverage_flag)."""
+    for a in argv:
+        name = a.split("=", 1)[0]
+        if len(name) > 2 and name.startswith("--") and any(f.startswith(name) for f in _VARIANT_FLAGS):
+            return True
+    return False
+
+
 def _early_reads_path(argv: List[str]) -> Optional[str]:
     """The --reads file of a `-t dumpalign` command line, read off argv before
     argparse and the heavy imports (every spelling argparse accepts: `-t X`,
@@ -96,6 +112,8 @@ def _early_reads_path(argv: List[str]) -> Optional[str]:
     if _has_coverage_flag(argv):  # (a coverage job parses the reads on the host)
         return None
     if _has_assignments_flag(argv):  # (so does a job that writes every read's assignment)
+        return None
+    if _has_variants_flag(argv):  # (and a pileup job: the base counts need the read columns)
         return None
     if os.environ.get("PA_GPUS", "1") not in ("", "0", "1"):  # (read-sharded over GPUs: no whole-file prefetch)
         return None
@@ -199,6 +217,16 @@ def parse_arguments(args: Optional[List[str]] = None) -> argparse.Namespace:
     # not in the reference: read -> genome as text, dumpalign with --reads
     parser.add_argument("--assignments", default=None, metavar="FILE",
                         help="write one line per read (id, mapping, genomes) to FILE")
+    # not in the reference: per-base pileup of the uniquely mapped reads and its SNV calls, dumpalign with --reads
+    parser.add_argument("--variants", default=None, metavar="FILE",
+                        help="write one line per called variant (genome, position, ref, alt, counts) to FILE")
+    parser.add_argument("--variant-min-depth", type=int, default=None, help="counted bases a position needs (default: 4)")
+    parser.add_argument("--variant-min-count", type=int, default=None,
+                        help="reads the alternative base needs (default: 2)")
+    parser.add_argument("--variant-min-fraction", type=float, default=None,
+                        help="share of the depth the alternative base needs (default: 0.2)")
+    parser.add_argument("--variant-min-base-quality", type=int, default=None,
+                        help="count only bases whose quality byte is at least this (default: all)")
     return parser.parse_args(args)
 
 
@@ -273,7 +301,8 @@ def _prefetch_reads(reads_file: str):
 def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: str, m: int, p: int,
                                     min_read_quality, min_kmer_quality, max_genomes,
                                     prefetch=None, per_read: bool = False,
-                                    coverage: bool = False, assignments: bool = False) -> PseudoAlignment:
+                                    coverage: bool = False, assignments: bool = False,
+                                    pileup: bool = False, min_base_quality=None) -> PseudoAlignment:
     # the FASTQ file goes straight to the device (parsed there, aligned in
     # windows); a file outside that subset of the grammar is parsed the exact
     # way (FASTAQFile), which also raises the reference's errors.  per_read
@@ -284,7 +313,9 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
     _stage("reference built")
     # coverage: the reads are parsed on the host and aligned on one device (align_reads_from_file
     # then takes its exact path: the placements need the read columns)
-    alignment = PseudoAlignment(kmer_reference, coverage=True) if coverage else PseudoAlignment(kmer_reference)
+    # pileup: likewise (the base counts need the read columns)
+    alignment = (PseudoAlignment(kmer_reference, coverage=coverage, pileup=pileup, min_base_quality=min_base_quality)
+                 if coverage or pileup else PseudoAlignment(kmer_reference))
     # assignments: the host parse too -- every read's line needs its id and the read columns
     if per_read or assignments:
         alignment.align_reads_from_container(FASTAQFile(reads_file).container, m, p, min_read_quality,
@@ -327,6 +358,23 @@ def _check_task(args: argparse.Namespace) -> None:
         if args.task != "dumpalign" or not args.reads:
             sys.exit("Error: --assignments is only allowed for task 'dumpalign' with --reads.")
         validate_file_writable(args.assignments, "Assignments output")
+    if args.variants is None and any(v is not None for v in (args.variant_min_depth, args.variant_min_count,
+                                                             args.variant_min_fraction,
+                                                             args.variant_min_base_quality)):
+        sys.exit("Error: --variant-min-depth, --variant-min-count, --variant-min-fraction and "
+                 "--variant-min-base-quality need --variants.")
+    if args.variants is not None:
+        if args.task != "dumpalign" or not args.reads:
+            sys.exit("Error: --variants is only allowed for task 'dumpalign' with --reads.")
+        if args.variant_min_depth is not None and args.variant_min_depth < 1:
+            sys.exit("Error: --variant-min-depth must be at least 1.")
+        if args.variant_min_count is not None and args.variant_min_count < 1:
+            sys.exit("Error: --variant-min-count must be at least 1.")
+        if args.variant_min_fraction is not None and not 0 <= args.variant_min_fraction <= 1:
+            sys.exit("Error: --variant-min-fraction must be in 0 .. 1.")
+        if args.variant_min_base_quality is not None and args.variant_min_base_quality < 0:
+            sys.exit("Error: --variant-min-base-quality must be at least 0.")
+        validate_file_writable(args.variants, "Variants output")
     if args.task == "reference":
         if extra:
             sys.exit("Error: For task 'reference', only -g, -k, -r, --filter-similar, and --similarity-threshold "
@@ -388,6 +436,11 @@ def _print_alignment(alignment: PseudoAlignment, args: argparse.Namespace) -> No
     if args.assignments is not None:
         with open(args.assignments, "w") as fh:
             alignment.write_assignments(fh)
+    if args.variants is not None:
+        with open(args.variants, "w") as fh:
+            alignment.write_variants(fh, 4 if args.variant_min_depth is None else args.variant_min_depth,
+                                     2 if args.variant_min_count is None else args.variant_min_count,
+                                     0.2 if args.variant_min_fraction is None else args.variant_min_fraction)
 
 
 def _run(args: argparse.Namespace) -> None:
@@ -426,19 +479,21 @@ def _run(args: argparse.Namespace) -> None:
     elif args.task == "dumpalign":
         if args.referencefile and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
-            host_parsed = args.coverage or args.assignments is not None
+            host_parsed = args.coverage or args.assignments is not None or args.variants is not None
             pf = None if host_parsed else _prefetch_reads(args.reads)
             ref = _load_reference(args.referencefile)
             _check_strands(args, ref)
             _print_alignment(create_alignment_from_reference(ref, args.reads, *filt, prefetch=pf,
                                                              coverage=args.coverage,
-                                                             assignments=args.assignments is not None), args)
+                                                             assignments=args.assignments is not None,
+                                                             pileup=args.variants is not None,
+                                                             min_base_quality=args.variant_min_base_quality), args)
         elif args.genomefile and args.kmer_size and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
             validate_file_readable(args.genomefile, "Genome FASTA")
             # (a coverage job runs on one device: the depth arrays of read shards are not reduced;
-            # an assignments job too: its lines come from one host-parsed batch)
-            host_parsed = args.coverage or args.assignments is not None
+            # an assignments job too: its lines come from one host-parsed batch; and a pileup job, as coverage)
+            host_parsed = args.coverage or args.assignments is not None or args.variants is not None
             sharded = None if host_parsed else _dumpalign_sharded(args, filt)
             if sharded is not None:
                 _print_json(sharded.get_summary())
@@ -448,7 +503,9 @@ def _run(args: argparse.Namespace) -> None:
                                    reads_file=args.reads, both_strands=args.both_strands)
             _print_alignment(create_alignment_from_reference(ref, args.reads, *filt, prefetch=pf,
                                                              coverage=args.coverage,
-                                                             assignments=args.assignments is not None), args)
+                                                             assignments=args.assignments is not None,
+                                                             pileup=args.variants is not None,
+                                                             min_base_quality=args.variant_min_base_quality), args)
         elif args.alignfile:
             validate_file_readable(args.alignfile, "Alignment output")
             try:

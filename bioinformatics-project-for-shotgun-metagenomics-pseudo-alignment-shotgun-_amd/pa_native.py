@@ -51,6 +51,8 @@ EXPORTS = (
     "pa_comm_unique_id", "pa_comm_init", "pa_comm_free", "pa_comm_count", "pa_counters_reduce",
     "pa_index_prepare_coverage", "pa_coverage_create", "pa_coverage_reset", "pa_coverage_add", "pa_coverage_summary",
     "pa_coverage_depth", "pa_coverage_free", "pa_align_placements",
+    "pa_pileup_create", "pa_pileup_reset", "pa_pileup_add", "pa_pileup_stats_get", "pa_pileup_counts",
+    "pa_pileup_variants", "pa_pileup_free",
     "pa_profile_enable", "pa_profile_read", "pa_profile_read_kernels", "pa_mem_trim",
     "pa_parse_text", "pa_parse_file", "pa_seqset_sizes", "pa_seqset_export", "pa_seqset_free", "pa_gz_inflate_file",
 )
@@ -88,6 +90,15 @@ class Stats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("unique_mapped_reads", "ambiguous_mapped_reads", "unmapped_reads",
                                                "filtered_quality_reads", "filtered_quality_kmers",
                                                "filtered_hr_kmers")]
+
+
+class PileupStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("reads_piled", "reads_skipped", "bases_counted")]
+
+
+# pa_variant, one record of Pileup.variants (40 bytes, no implicit padding)
+VARIANT_DTYPE = np.dtype([("genome", "<u4"), ("ref", "u1"), ("alt", "u1"), ("pad", "u1", (2,)), ("position", "<u8"),
+                          ("depth", "<u4"), ("alt_count", "<u4"), ("acgt", "<u4", (4,))])
 
 
 class IndexInfo(ctypes.Structure):
@@ -176,6 +187,13 @@ def lib():
         "pa_coverage_depth": (I32, [P, U32, U64, U64, P, P, P]),
         "pa_coverage_free": (None, [P]),
         "pa_align_placements": (I32, [P, P, ctypes.POINTER(Params), P, P, P, P, U64, ctypes.POINTER(U64), P]),
+        "pa_pileup_create": (I32, [P, PP]),
+        "pa_pileup_reset": (I32, [P, P]),
+        "pa_pileup_add": (I32, [P, P, ctypes.POINTER(Params), U32, P, P]),
+        "pa_pileup_stats_get": (I32, [P, ctypes.POINTER(PileupStats), P]),
+        "pa_pileup_counts": (I32, [P, U32, U64, U64, P, P]),
+        "pa_pileup_variants": (I32, [P, U32, U32, U32, P, U64, ctypes.POINTER(U64), P]),
+        "pa_pileup_free": (None, [P]),
         "pa_profile_enable": (I32, [P, I32]),
         "pa_profile_read": (I32, [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.POINTER(U64)]),
         "pa_profile_read_kernels": (I32, [P, P, P]),
@@ -1031,6 +1049,85 @@ class Coverage:
     def close(self):
         if getattr(self, "_h", None):
             lib().pa_coverage_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class Pileup:
+    """Per-base A/C/G/T counts of one index from its uniquely mapped reads, and
+    the SNV calls made from them (pa_pileup): ``add``
+    classifies a batch as align_detail does, places the unique reads and counts
+    the bases of those whose windows agree on one diagonal; ``counts`` /
+    ``variants`` read the result in forward genome coordinates."""
+
+    def __init__(self, index: Index):
+        h = P()
+        _check(lib().pa_pileup_create(index.handle, ctypes.byref(h)))
+        self._h = h
+        self._index = index  # (kept alive: the accumulator is checked against it)
+        self.n_genomes = index.n_genomes
+        self.lengths = [int(x) for x in index.genome_lengths]  # forward bases per genome
+
+    @property
+    def handle(self):
+        return self._h
+
+    def add(self, reads: Reads, params: Params, min_base_quality: int = 0, stream=None) -> None:
+        """Bases whose quality byte is < min_base_quality are not counted (0: all are)."""
+        if not 0 <= int(min_base_quality) < 2 ** 32:
+            raise ValueError("min_base_quality must be in 0 .. 2^32 - 1")
+        _check(lib().pa_pileup_add(self._index.handle, reads.handle, ctypes.byref(params), int(min_base_quality),
+                                   self._h, _stream(stream)))
+
+    def reset(self, stream=None) -> None:
+        _check(lib().pa_pileup_reset(self._h, _stream(stream)))
+
+    def stats(self, stream=None) -> dict:
+        """{"reads_piled", "reads_skipped", "bases_counted"} since the last reset."""
+        s = PileupStats()
+        _check(lib().pa_pileup_stats_get(self._h, ctypes.byref(s), _stream(stream)))
+        return {n: int(getattr(s, n)) for n, _ in PileupStats._fields_}
+
+    def counts(self, genome: int, first: int = 0, count: Optional[int] = None, stream=None) -> np.ndarray:
+        """(n, 4) uint32: the A, C, G, T counts of positions [first, first + count)
+        of one genome (count None: to its end)."""
+        genome, first = int(genome), int(first)
+        if not 0 <= genome < self.n_genomes:
+            raise ValueError("genome number out of range")
+        if first < 0 or (count is not None and int(count) < 0):
+            raise ValueError("positions past the end of the genome")
+        if count is None:
+            count = self.lengths[genome] - first
+            if count < 0:
+                raise ValueError("positions past the end of the genome")
+        count = int(count)
+        out = np.zeros((max(count, 1), 4), dtype=np.uint32)
+        _check(lib().pa_pileup_counts(self._h, genome, first, count, _ptr(out), _stream(stream)))
+        return out[:count]
+
+    def variants(self, min_depth: int, min_alt_count: int, min_alt_permille: int, stream=None) -> np.ndarray:
+        """The calls as a structured array (VARIANT_DTYPE), ordered by (genome,
+        position, alternative base).  The first call has room for 4096 records;
+        a longer result is fetched once more with the count the first reported."""
+        args = []
+        for v, name in ((min_depth, "min_depth"), (min_alt_count, "min_alt_count"),
+                        (min_alt_permille, "min_alt_permille")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 2 ** 32:
+                raise ValueError(f"{name} must be an integer in 0 .. 2^32 - 1")
+            args.append(int(v))
+        out = np.zeros(4096, dtype=VARIANT_DTYPE)
+        n = U64(0)
+        st = lib().pa_pileup_variants(self._h, *args, _ptr(out), out.size, ctypes.byref(n), _stream(stream))
+        if st == PA_EINVAL and n.value > out.size:
+            out = np.zeros(int(n.value), dtype=VARIANT_DTYPE)
+            st = lib().pa_pileup_variants(self._h, *args, _ptr(out), out.size, ctypes.byref(n), _stream(stream))
+        _check(st)
+        return out[:int(n.value)]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().pa_pileup_free(self._h)
             self._h = None
 
     __del__ = close

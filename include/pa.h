@@ -34,6 +34,8 @@
  *   pa_align_placements      --min-coverage, --full-coverage), which the reference leaves out: it
  *                            has no coverage code, so the definition is DESIGN.md section 10; the
  *                            occurrence sets it places reads with are kmers[w][g], src/kmer.py:140-150
+ *   pa_pileup_*              per-base counts and SNV calls from the uniquely mapped reads (--variants);
+ *                            no reference counterpart: the definition is DESIGN.md section 13
  *   pa_align_batch           one-shot host-buffer form of pa_align
  *   pa_align_fastq_file      FASTAQFile + align_reads_from_container as one
  *                            device-parsed stream                          src/data_file.py:134-158,
@@ -396,6 +398,68 @@ void pa_coverage_free(pa_coverage *cov);
 pa_status pa_align_placements(const pa_index *idx, const pa_reads *reads, const pa_params *params,
                               uint8_t *read_type, uint64_t *list_off, uint32_t *lists, int64_t *starts,
                               uint64_t list_cap, uint64_t *list_total, void *stream);
+
+/* ---- pileup: what the placed reads say at each position ----
+ *
+ * Every read is classified as pa_align_detail classifies it with the same
+ * params; only PA_UNIQUELY_MAPPED reads (list exactly [g]) contribute.  Such a
+ * read is placed as for coverage, s = s(read, g), and piled up only if all of
+ * its voting windows vote for s; a read whose windows name two or more
+ * diagonals (across a repeat boundary, chimeric) is counted in reads_skipped
+ * and adds nothing.  Base i of a piled read lies at region position q = s + i;
+ * q outside the region is skipped; on a forward index x = q, b = seq[i]; on a
+ * both-strand index q < |g| is x = q, b = seq[i], q == |g| (the N) is skipped,
+ * q > |g| is x = 2|g| - q, b = complement(seq[i]).  A base that is not one of
+ * A C G T, or whose quality byte < min_base_quality (raw byte, strict, 0
+ * filters nothing), is skipped; else count[g][x][b] += 1 (uint32, b = 0-3 for
+ * ACGT, x a forward coordinate).
+ *
+ * Calls: position x of genome g with reference code ref < 4 (forward text) and
+ * depth D = the sum of its four counts yields one record per base b != ref, in
+ * A, C, G, T order, when D >= min_depth, count[b] >= min_alt_count and
+ * 1000 count[b] >= min_alt_permille D (64-bit integers).  Records come ordered
+ * by (genome, position, alternative base).  A non-ACGT reference base keeps
+ * its counts and is never called.
+ *
+ * The placements use the positions view (see coverage above; PA_EUNSUPPORTED /
+ * PA_ENOMEM as there).  A pileup job runs on one device; the accumulator's
+ * bytes are not part of pa_index_info. */
+typedef struct pa_pileup pa_pileup;
+typedef struct {
+    uint64_t reads_piled, reads_skipped, bases_counted;
+} pa_pileup_stats;
+typedef struct {
+    uint32_t genome;
+    uint8_t ref, alt, pad[2]; /* codes 0-3 */
+    uint64_t position;        /* 0-based, forward */
+    uint32_t depth, alt_count;
+    uint32_t acgt[4];
+} pa_variant;
+/* A zeroed accumulator for this index on its device: 16 B of counts per
+ * forward genome base, plus its own copy of the forward reference codes (1 B
+ * per base), so counts and calls stay readable whatever becomes of the index.
+ * It takes reads of this index until its next pa_index_reduce (pa_pileup_add:
+ * PA_EINVAL after, and for any other index).  PA_ENOMEM when it does not fit --
+ * the index stays usable. */
+pa_status pa_pileup_create(const pa_index *idx, pa_pileup **out);
+pa_status pa_pileup_reset(pa_pileup *p, void *stream); /* counts and stats to zero */
+/* Classify, place and count.  PA_EUNSUPPORTED when the reads added since the
+ * last reset would reach 2^32; PA_EINTERNAL if a listed genome gets no vote
+ * (an invariant: never skipped silently).  Returns when done. */
+pa_status pa_pileup_add(const pa_index *idx, const pa_reads *reads, const pa_params *params,
+                        uint32_t min_base_quality, pa_pileup *acc, void *stream);
+pa_status pa_pileup_stats_get(const pa_pileup *p, pa_pileup_stats *out, void *stream);
+/* Counts of positions [first, first + count) of one genome, forward
+ * coordinates: acgt[count][4].  PA_EINVAL: genome >= n_genomes, or a range past |g|. */
+pa_status pa_pileup_counts(const pa_pileup *p, uint32_t genome, uint64_t first, uint64_t count,
+                           uint32_t *acgt /* [count][4] */, void *stream);
+/* The calls.  *n is always the full record count; with cap < *n nothing is
+ * written and the call returns PA_EINVAL, so the caller retries with the
+ * capacity it now knows (out == NULL behaves as cap == 0).  PA_EINVAL also
+ * unless min_depth >= 1, min_alt_count >= 1 and min_alt_permille <= 1000. */
+pa_status pa_pileup_variants(const pa_pileup *p, uint32_t min_depth, uint32_t min_alt_count,
+                             uint32_t min_alt_permille, pa_variant *out, uint64_t cap, uint64_t *n, void *stream);
+void pa_pileup_free(pa_pileup *p);
 
 /* upload + pa_align + fetch for host buffers (stats and per-genome arrays accumulate: +=, min) */
 pa_status pa_align_batch(const pa_index *idx, const uint8_t *seq, const uint8_t *qual, const uint64_t *read_off,

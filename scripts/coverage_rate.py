@@ -25,6 +25,14 @@ one list entry per read) next to pa_align_detail on the same library, and adds
 the kernels' own times over profiled_calls such calls (pa_profile_read_kernels)
 and the counter pass (pa_align + fetch) on the same batch.  --mode coverage rides the assign pass since
 pa_coverage_add classifies through it (PA_ASSIGN=0: the exact pass, as before).
+--mode pileup times pa_pileup_add next to pa_coverage_add
+and pa_align_reads on the same library and batch, with the positions view in
+place: the three share the assign pass, the two adds share k_place, so
+coverage_add_s - align_reads_s bounds k_place (plus the depth atomics) and
+pileup_add_s - coverage_add_s is k_pileup's cost over those atomics.  It adds
+the align kernels' own times over profiled pileup adds, pa_pileup_variants over
+the whole reference (its two passes and the copy of the records), and the stats.
+
 --read-err / --rc-rate / --foreign-rate give bench.py's c2mix reads (0.015, 0.2, 0.2).
 """
 
@@ -100,7 +108,7 @@ def time_assign(index, reads, prm, runs):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("detail", "coverage", "assign"), required=True)
+    ap.add_argument("--mode", choices=("detail", "coverage", "assign", "pileup"), required=True)
     ap.add_argument("--reads", type=int, default=10_000_000)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--genomes", type=int, default=50)
@@ -139,6 +147,35 @@ def main():
         dmed, dts, dentries = time_detail(index, reads, prm, args.runs)
         assert dentries == entries
         out.update(align_detail_s=dmed, align_detail_runs_s=dts, ratio_detail_over_assign=dmed / med)
+    elif args.mode == "pileup":
+        index.prepare_coverage()
+        med, ts, entries = time_assign(index, reads, prm, args.runs)
+        out.update(align_reads_s=med, align_reads_runs_s=ts, list_entries=entries)
+        cov = N.Coverage(index)
+        med, ts = timed(lambda: cov.add(reads, prm), args.runs)
+        out.update(coverage_add_s=med, coverage_add_runs_s=ts)
+        cov.close()
+        pl = N.Pileup(index)
+        med, ts = timed(lambda: pl.add(reads, prm), args.runs)
+        out.update(pileup_add_s=med, pileup_add_runs_s=ts, pileup_reads_per_s=args.reads / med,
+                   ratio_pileup_add_over_coverage_add=med / out["coverage_add_s"])
+        med, ts = timed(lambda: pl.add(reads, prm, 60), args.runs)  # (synthesized qualities: normal(60, 8), so about half the bases)
+        out.update(pileup_add_quality_s=med)
+        index.profile_enable(True)
+        index.profile_read_kernels()
+        pl.add(reads, prm)
+        out["profiled_calls"] = 1
+        out["kernels_ms_launches"] = index.profile_read_kernels()
+        index.profile_enable(False)
+        pl.reset()
+        pl.add(reads, prm)
+        out["stats"] = pl.stats()
+        for name, triple in (("variants_4_2_200", (4, 2, 200)), ("variants_1_1_0", (1, 1, 0))):
+            holder = {}
+            med, ts = timed(lambda: holder.update(v=pl.variants(*triple)), args.runs)
+            out[name + "_s"] = med
+            out[name + "_records"] = int(holder["v"].size)
+        pl.close()
     else:
         med, ts, entries = time_detail(index, reads, prm, args.runs)
         out.update(align_detail_branch_s=med, align_detail_branch_runs_s=ts, list_entries=entries)
