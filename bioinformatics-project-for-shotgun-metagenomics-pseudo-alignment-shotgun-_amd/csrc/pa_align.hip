@@ -470,6 +470,140 @@ __device__ __forceinline__ uint32_t block_max(uint32_t v, uint32_t *red) {
     return s;
 }
 
+// The exact kernel's front half, shared with k_abund_cand (one workgroup per
+// read, the scratch invariant of k_align_exact: g_* clean between reads).
+//
+// exact_windows: the read's windows -- quality and --max-genomes filters, the
+// table probe, the distinct k-mers' hash (slot -> first window).  Returns 0
+// when no k-mer of the read is retained (else the threads that retained one);
+// qf / hr get the filtered and the redundant windows' counts.
+template <int NW>
+__device__ __forceinline__ uint32_t exact_windows(const AlignArgs &a, const ExactArgs &x, const ExactWs &ws,
+                                                  const Slot<NW> *table, uint32_t G, int k, uint64_t mask0,
+                                                  bool has_mkq, bool has_mg, uint64_t off, uint32_t W, uint32_t *red,
+                                                  uint32_t &qf_out, uint32_t &hr_out) {
+    for (uint32_t i = threadIdx.x; i < x.dh; i += kBlock) {
+        st_agent(&ws.dh_key[i], EMPTY);
+        st_agent(&ws.dh_min[i], NONE);
+        st_agent(&ws.ch_key[i], NONE);
+        st_agent(&ws.ch_cnt[i], 0u);
+        st_agent(&ws.ch_min[i], NONE);
+    }
+    __syncthreads();
+    // ---- windows
+    uint32_t qf = 0, hr = 0, any = 0;
+    for (uint32_t w = threadIdx.x; w < W; w += kBlock) {
+        ws.wslot[w] = EMPTY;
+        if (has_mkq) {
+            uint32_t s = 0;
+            for (int i = 0; i < k; i++) s += a.qual[off + w + i];
+            if ((int64_t)s < (int64_t)a.prm.mkq * k) {
+                qf++;
+                continue;
+            }
+        }
+        Key<NW> key;
+#pragma unroll
+        for (int j = 0; j < NW; j++) key.w[j] = 0;
+        bool clean = true;
+        for (int i = 0; i < k; i++) {
+            uint32_t c = base_code(a.seq[off + w + i]);
+            clean &= c < 4;
+            key_push(key, c & 3, mask0);
+        }
+        if (!clean) continue;
+        uint64_t slot;
+        uint32_t cls, tpos;
+        if (!table_find<NW, true>(table, a.cap, key, home_of(key, key_hash(key), a.home), slot, cls, tpos)) continue;
+        if (has_mg && (int64_t)class_size_of(cls, G, a.class_genomes) > (int64_t)a.prm.mg) {
+            hr++;
+            continue;
+        }
+        ws.wslot[w] = slot;
+        ws.wcls[w] = cls_of(cls);
+        any = 1;
+        uint32_t p = (uint32_t)(fmix64(slot) & (x.dh - 1));
+        for (;;) {
+            uint64_t old = atomicCAS((unsigned long long *)&ws.dh_key[p], (unsigned long long)EMPTY,
+                                     (unsigned long long)slot);
+            if (old == EMPTY || old == slot) break;
+            p = (p + 1) & (x.dh - 1);
+        }
+        atomicMin(&ws.dh_min[p], w);
+    }
+    qf_out = block_sum(qf, red);
+    hr_out = block_sum(hr, red);
+    return block_sum(any, red);
+}
+
+// exact_totals: distinct k-mers -> specific and total counts per genome.  A
+// specific k-mer counts for its genome directly; the others are first
+// grouped by genome set (a read's k-mers fall in a handful of sets, e.g.
+// one set of every genome for a conserved stretch), and every set then
+// adds its k-mer count and first window to its genomes once, the
+// block striding over the set's genome list.  Afterwards g_tot[g] is the
+// number of distinct retained k-mers whose genome set holds g (the reference's
+// generate_genome_counts(map_count=False), src/kmer.py:431-442), g_spec[g]
+// those specific to g, and touched[0 .. n_touched) the genomes with any.
+__device__ __forceinline__ void exact_totals(const AlignArgs &a, const ExactArgs &x, const ExactWs &ws, uint32_t G,
+                                             uint32_t W, uint32_t &n_touched, uint32_t &n_cls) {
+    for (uint32_t w = threadIdx.x; w < W; w += kBlock) {
+        const uint64_t slot = ws.wslot[w];
+        if (slot == EMPTY) continue;
+        uint32_t p = (uint32_t)(fmix64(slot) & (x.dh - 1));
+        while (ld_agent(&ws.dh_key[p]) != slot) p = (p + 1) & (x.dh - 1);
+        if (ld_agent(&ws.dh_min[p]) != w) continue;
+        const uint32_t c = ws.wcls[w];
+        if (c < G) {
+            atomicAdd(&ws.g_spec[c], 1u);
+            atomicMin(&ws.g_specmin[c], w);
+            if (atomicAdd(&ws.g_tot[c], 1u) == 0) ws.touched[atomicAdd(&n_touched, 1u)] = c;
+            atomicMin(&ws.g_totmin[c], w);
+        } else {
+            uint32_t q = (uint32_t)(fmix64(c) & (x.dh - 1));
+            for (;;) {
+                const uint32_t old = atomicCAS(&ws.ch_key[q], NONE, c);
+                if (old == NONE) {
+                    ws.cls_list[atomicAdd(&n_cls, 1u)] = q;
+                    break;
+                }
+                if (old == c) break;
+                q = (q + 1) & (x.dh - 1);
+            }
+            atomicAdd(&ws.ch_cnt[q], 1u);
+            atomicMin(&ws.ch_min[q], w);
+        }
+    }
+    __syncthreads();
+    const uint32_t ncl = n_cls;
+    for (uint32_t i = 0; i < ncl; i++) {
+        const uint32_t q = ld_agent(&ws.cls_list[i]);
+        const uint32_t c = ld_agent(&ws.ch_key[q]), cnt = ld_agent(&ws.ch_cnt[q]), mw = ld_agent(&ws.ch_min[q]);
+        const uint32_t *rec = a.class_genomes + (c - G);  // [size, genomes...]
+        const uint32_t sz = rec[0];
+        for (uint32_t j = threadIdx.x; j < sz; j += kBlock) {
+            const uint32_t g = rec[1 + j];
+            if (atomicAdd(&ws.g_tot[g], cnt) == 0) ws.touched[atomicAdd(&n_touched, 1u)] = g;
+            atomicMin(&ws.g_totmin[g], mw);
+        }
+    }
+    __syncthreads();
+}
+
+// exact_restore: the scratch invariant, after a read that touched nt genomes.
+__device__ __forceinline__ void exact_restore(const ExactWs &ws, uint32_t nt, uint32_t &n_touched, uint32_t &n_cls) {
+    for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
+        const uint32_t g = ws.touched[t];
+        st_agent(&ws.g_spec[g], 0u);
+        st_agent(&ws.g_specmin[g], NONE);
+        st_agent(&ws.g_tot[g], 0u);
+        st_agent(&ws.g_totmin[g], NONE);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) n_touched = n_cls = 0;
+    __syncthreads();
+}
+
 constexpr uint32_t kRankLds = 2048;  // genomes of a read's list ranked in LDS (16 KB); more: over the scratch
 template <int NW>
 __global__ __launch_bounds__(kBlock) void k_align_exact(ExactArgs x) {
@@ -520,108 +654,12 @@ __global__ __launch_bounds__(kBlock) void k_align_exact(ExactArgs x) {
                 continue;
             }
         }
-        for (uint32_t i = threadIdx.x; i < x.dh; i += kBlock) {
-            st_agent(&ws.dh_key[i], EMPTY);
-            st_agent(&ws.dh_min[i], NONE);
-            st_agent(&ws.ch_key[i], NONE);
-            st_agent(&ws.ch_cnt[i], 0u);
-            st_agent(&ws.ch_min[i], NONE);
-        }
-        __syncthreads();
-        // ---- windows
-        uint32_t qf = 0, hr = 0, any = 0;
-        for (uint32_t w = threadIdx.x; w < W; w += kBlock) {
-            ws.wslot[w] = EMPTY;
-            if (has_mkq) {
-                uint32_t s = 0;
-                for (int i = 0; i < k; i++) s += a.qual[off + w + i];
-                if ((int64_t)s < (int64_t)a.prm.mkq * k) {
-                    qf++;
-                    continue;
-                }
-            }
-            Key<NW> key;
-#pragma unroll
-            for (int j = 0; j < NW; j++) key.w[j] = 0;
-            bool clean = true;
-            for (int i = 0; i < k; i++) {
-                uint32_t c = base_code(a.seq[off + w + i]);
-                clean &= c < 4;
-                key_push(key, c & 3, mask0);
-            }
-            if (!clean) continue;
-            uint64_t slot;
-            uint32_t cls, tpos;
-            if (!table_find<NW, true>(table, a.cap, key, home_of(key, key_hash(key), a.home), slot, cls, tpos)) continue;
-            if (has_mg && (int64_t)class_size_of(cls, G, a.class_genomes) > (int64_t)a.prm.mg) {
-                hr++;
-                continue;
-            }
-            ws.wslot[w] = slot;
-            ws.wcls[w] = cls_of(cls);
-            any = 1;
-            uint32_t p = (uint32_t)(fmix64(slot) & (x.dh - 1));
-            for (;;) {
-                uint64_t old = atomicCAS((unsigned long long *)&ws.dh_key[p], (unsigned long long)EMPTY,
-                                         (unsigned long long)slot);
-                if (old == EMPTY || old == slot) break;
-                p = (p + 1) & (x.dh - 1);
-            }
-            atomicMin(&ws.dh_min[p], w);
-        }
-        qf = block_sum(qf, red);
-        hr = block_sum(hr, red);
-        any = block_sum(any, red);
+        uint32_t qf, hr;
+        const uint32_t any = exact_windows<NW>(a, x, ws, table, G, k, mask0, has_mkq, has_mg, off, W, red, qf, hr);
         uint8_t type = PA_UNMAPPED;
         uint32_t list_len = 0;
         if (any) {
-            // ---- distinct k-mers -> specific and total counts per genome.  A
-            // specific k-mer counts for its genome directly; the others are first
-            // grouped by genome set (a read's k-mers fall in a handful of sets, e.g.
-            // one set of every genome for a conserved stretch), and every set then
-            // adds its k-mer count and first window to its genomes once, the
-            // block striding over the set's genome list.
-            for (uint32_t w = threadIdx.x; w < W; w += kBlock) {
-                const uint64_t slot = ws.wslot[w];
-                if (slot == EMPTY) continue;
-                uint32_t p = (uint32_t)(fmix64(slot) & (x.dh - 1));
-                while (ld_agent(&ws.dh_key[p]) != slot) p = (p + 1) & (x.dh - 1);
-                if (ld_agent(&ws.dh_min[p]) != w) continue;
-                const uint32_t c = ws.wcls[w];
-                if (c < G) {
-                    atomicAdd(&ws.g_spec[c], 1u);
-                    atomicMin(&ws.g_specmin[c], w);
-                    if (atomicAdd(&ws.g_tot[c], 1u) == 0) ws.touched[atomicAdd(&n_touched, 1u)] = c;
-                    atomicMin(&ws.g_totmin[c], w);
-                } else {
-                    uint32_t q = (uint32_t)(fmix64(c) & (x.dh - 1));
-                    for (;;) {
-                        const uint32_t old = atomicCAS(&ws.ch_key[q], NONE, c);
-                        if (old == NONE) {
-                            ws.cls_list[atomicAdd(&n_cls, 1u)] = q;
-                            break;
-                        }
-                        if (old == c) break;
-                        q = (q + 1) & (x.dh - 1);
-                    }
-                    atomicAdd(&ws.ch_cnt[q], 1u);
-                    atomicMin(&ws.ch_min[q], w);
-                }
-            }
-            __syncthreads();
-            const uint32_t ncl = n_cls;
-            for (uint32_t i = 0; i < ncl; i++) {
-                const uint32_t q = ld_agent(&ws.cls_list[i]);
-                const uint32_t c = ld_agent(&ws.ch_key[q]), cnt = ld_agent(&ws.ch_cnt[q]), mw = ld_agent(&ws.ch_min[q]);
-                const uint32_t *rec = a.class_genomes + (c - G);  // [size, genomes...]
-                const uint32_t sz = rec[0];
-                for (uint32_t j = threadIdx.x; j < sz; j += kBlock) {
-                    const uint32_t g = rec[1 + j];
-                    if (atomicAdd(&ws.g_tot[g], cnt) == 0) ws.touched[atomicAdd(&n_touched, 1u)] = g;
-                    atomicMin(&ws.g_totmin[g], mw);
-                }
-            }
-            __syncthreads();
+            exact_totals(a, x, ws, G, W, n_touched, n_cls);
             const uint32_t nt = n_touched;
             // ---- decision (src/kmer.py:444-480)
             uint32_t nspec = 0, maxcnt = 0;
@@ -749,17 +787,7 @@ __global__ __launch_bounds__(kBlock) void k_align_exact(ExactArgs x) {
                 }
             }
             __syncthreads();
-            // ---- restore the scratch invariant
-            for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
-                const uint32_t g = ws.touched[t];
-                st_agent(&ws.g_spec[g], 0u);
-                st_agent(&ws.g_specmin[g], NONE);
-                st_agent(&ws.g_tot[g], 0u);
-                st_agent(&ws.g_totmin[g], NONE);
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) n_touched = n_cls = 0;
-            __syncthreads();
+            exact_restore(ws, nt, n_touched, n_cls);
         }
         if (threadIdx.x == 0) {
             if (x.detail) {
@@ -773,6 +801,92 @@ __global__ __launch_bounds__(kBlock) void k_align_exact(ExactArgs x) {
                 if (has_mg && hr) atomicAdd(&a.stats[5], (unsigned long long)hr);
             }
         }
+        __syncthreads();
+    }
+}
+
+// The compatibility sets of the abundance pass (pa_abund.hip, DESIGN.md section
+// 14), here because it is k_align_exact's front half with another ending: for
+// every queued read -- the reads the assign pass typed ambiguous -- the genomes
+// g whose total count T(g) = g_tot[g] is the read's maximum.  x.detail 1: their
+// number to len_out[r]; 2: the genomes, ascending, at lists[list_off[r] ..).
+// A set may be larger than the workgroup: up to kRankLds genomes are staged in
+// LDS and each one's place is the number of smaller ones; a larger set is
+// ranked over the scratch's touched list.
+template <int NW>
+__global__ __launch_bounds__(kBlock) void k_abund_cand(ExactArgs x) {
+    const AlignArgs &a = x.a;
+    __shared__ uint32_t red[kWaves];
+    __shared__ uint32_t n_touched, n_cls, n_rank;
+    __shared__ uint32_t rank_g[kRankLds];
+    const uint32_t G = a.G;
+    const int k = a.k;
+    const uint64_t mask0 = k > 0 ? mask0_of(k, NW) : 0;
+    const Slot<NW> *table = (const Slot<NW> *)a.table;
+    const bool has_mkq = a.prm.flags & F_MKQ, has_mg = a.prm.flags & F_MG;
+    ExactWs ws = exact_ws(x.ws + (uint64_t)blockIdx.x * x.ws_stride, x.wcap, x.dh, G);
+    for (uint32_t g = threadIdx.x; g < G; g += kBlock) {
+        st_agent(&ws.g_spec[g], 0u);
+        st_agent(&ws.g_specmin[g], NONE);
+        st_agent(&ws.g_tot[g], 0u);
+        st_agent(&ws.g_totmin[g], NONE);
+    }
+    if (threadIdx.x == 0) n_touched = n_cls = 0;
+    __syncthreads();
+    const uint64_t nq = *a.qcount;
+    for (uint64_t q = blockIdx.x; q < nq; q += gridDim.x) {
+        const uint64_t r = a.queue[q];
+        const uint64_t off = a.off[r];
+        const uint32_t len = (uint32_t)(a.off[r + 1] - off);
+        const uint32_t W = (k > 0 && len >= (uint32_t)k) ? len - k + 1 : 0;
+        uint32_t qf, hr;
+        const uint32_t any = exact_windows<NW>(a, x, ws, table, G, k, mask0, has_mkq, has_mg, off, W, red, qf, hr);
+        uint32_t nc = 0;
+        if (any) {
+            exact_totals(a, x, ws, G, W, n_touched, n_cls);
+            const uint32_t nt = n_touched;
+            uint32_t mx = 0;
+            for (uint32_t t = threadIdx.x; t < nt; t += kBlock) mx = max(mx, ld_agent(&ws.g_tot[ws.touched[t]]));
+            mx = block_max(mx, red);
+            if (threadIdx.x == 0) n_rank = 0;
+            __syncthreads();
+            uint32_t mine = 0;
+            for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
+                const uint32_t g = ws.touched[t];
+                if (ld_agent(&ws.g_tot[g]) != mx) continue;
+                mine++;
+                if (x.detail == 2) {
+                    const uint32_t i = atomicAdd(&n_rank, 1u);
+                    if (i < kRankLds) rank_g[i] = g;
+                }
+            }
+            nc = block_sum(mine, red);  // (its barriers also publish rank_g)
+            if (x.detail == 2) {
+                const uint64_t o = x.list_off[r], end = x.list_off[r + 1];
+                if (nc <= kRankLds) {
+                    for (uint32_t i = threadIdx.x; i < nc; i += kBlock) {
+                        const uint32_t g = rank_g[i];
+                        uint32_t rank = 0;
+                        for (uint32_t u = 0; u < nc; u++) rank += rank_g[u] < g;
+                        if (o + rank < end) x.lists[o + rank] = g;
+                    }
+                } else {
+                    for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
+                        const uint32_t g = ws.touched[t];
+                        if (ld_agent(&ws.g_tot[g]) != mx) continue;
+                        uint32_t rank = 0;
+                        for (uint32_t u = 0; u < nt; u++) {
+                            const uint32_t h = ws.touched[u];
+                            rank += h < g && ld_agent(&ws.g_tot[h]) == mx;
+                        }
+                        if (o + rank < end) x.lists[o + rank] = g;
+                    }
+                }
+            }
+            __syncthreads();
+            exact_restore(ws, nt, n_touched, n_cls);
+        }
+        if (threadIdx.x == 0 && x.detail == 1) x.len_out[r] = nc;
         __syncthreads();
     }
 }
@@ -1496,6 +1610,32 @@ pa_status detail_pass_device(pa_index *idx, const pa_reads *r, const DevParams &
     unsigned egrid = 0;
     PA_TRY(exact_args(idx, r, make_args(idx, r, p, 0, Switches{}), &out, x, egrid));
     return launch_exact(nullptr, idx->nw, x, egrid, st);  // (not a kernel of the align passes' profile)
+}
+
+// The abundance pass's candidate kernel over a queue of batch-local read
+// numbers (n_queued of them, also at *d_count): without d_sets the sets' sizes
+// to d_len[read], with d_off (n + 1 offsets) and d_sets the sets themselves.
+pa_status candidates_pass(pa_index *idx, const pa_reads *r, const DevParams &p_in, const uint32_t *d_queue,
+                          const unsigned long long *d_count, uint64_t n_queued, uint32_t *d_len, const uint64_t *d_off,
+                          uint32_t *d_sets, hipStream_t st) {
+    if (r->n == 0 || n_queued == 0) return PA_OK;
+    const Switches sw;
+    DevParams p;
+    PA_TRY(effective_params(r, p_in, p, st, sw));
+    AlignArgs a = make_args(idx, r, p, 0, sw);
+    a.queue = const_cast<uint32_t *>(d_queue);
+    a.qcount = const_cast<unsigned long long *>(d_count);
+    const DetailOut out{nullptr, nullptr, nullptr, d_len, d_off, d_sets};
+    ExactArgs x;
+    unsigned egrid = 0;
+    PA_TRY(exact_args(idx, r, a, &out, x, egrid));
+    x.use_queue = 1;
+    const unsigned grid = (unsigned)std::min<uint64_t>(egrid, n_queued);
+    with_int<1, 2, 3, 4, 5, 6, 7, 8>(idx->nw, [&](auto w) {
+        hipLaunchKernelGGL(k_abund_cand<w()>, dim3(grid), dim3(kBlock), 0, st, x);
+    });
+    PA_HIP(hipGetLastError());
+    return PA_OK;
 }
 
 // pa_align_detail: a lengths pass, the list offsets by a host scan, a lists pass.

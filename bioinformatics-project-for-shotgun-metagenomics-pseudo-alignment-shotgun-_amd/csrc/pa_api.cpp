@@ -855,6 +855,82 @@ void pa_pileup_free(pa_pileup *p) {
     pa::pileup_free(p);
 }
 
+// ---- abundance (csrc/pa_abund.hip) ------------------------------------------------------
+
+pa_status pa_abundance_create(const pa_index *idx, pa_abundance **out) {
+    PA_CHECK(idx && out, PA_EINVAL, "NULL argument");
+    *out = nullptr;
+    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_HIP(hipSetDevice(idx->device));
+    return pa::abundance_create(idx, out);
+}
+
+pa_status pa_abundance_reset(pa_abundance *a, void *stream) {
+    PA_CHECK(a != nullptr, PA_EINVAL, "NULL argument");
+    PA_HIP(hipSetDevice(a->device));
+    return pa::abundance_reset(a, as_stream(stream));
+}
+
+pa_status pa_abundance_add(const pa_index *idx, const pa_reads *reads, const pa_params *params, pa_abundance *acc,
+                           void *stream) {
+    PA_CHECK(idx && reads && acc, PA_EINVAL, "NULL argument");
+    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
+    PA_CHECK(acc->idx == idx && acc->epoch == idx->epoch, PA_EINVAL,
+             "the pa_abundance was made for another index, or for this one before a pa_index_reduce");
+    pa::DevParams dp;
+    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    PA_HIP(hipSetDevice(idx->device));
+    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    return pa::abundance_add(const_cast<pa_index *>(idx), reads, dp, acc, as_stream(stream));
+}
+
+pa_status pa_abundance_info_get(const pa_abundance *a, pa_abundance_info *out, void *stream) {
+    PA_CHECK(a && out, PA_EINVAL, "NULL argument");
+    PA_HIP(hipSetDevice(a->device));
+    return pa::abundance_info(a, out, as_stream(stream));
+}
+
+pa_status pa_abundance_classes(const pa_abundance *a, uint64_t *class_off, uint32_t *genomes, uint64_t *counts,
+                               uint64_t cap_classes, uint64_t cap_entries, uint64_t *n_classes, uint64_t *n_entries,
+                               void *stream) {
+    PA_CHECK(a && n_classes && n_entries, PA_EINVAL, "NULL argument");
+    *n_classes = *n_entries = 0;
+    PA_HIP(hipSetDevice(a->device));
+    return pa::abundance_classes(a, class_off, genomes, counts, cap_classes, cap_entries, n_classes, n_entries,
+                                 as_stream(stream));
+}
+
+pa_status pa_abundance_estimate(const pa_abundance *a, uint32_t max_iterations, double tolerance,
+                                double *read_fraction, double *abundance, uint32_t *iterations_done,
+                                double *last_delta, void *stream) {
+    PA_CHECK(a != nullptr, PA_EINVAL, "NULL argument");
+    PA_CHECK(max_iterations >= 1 && max_iterations <= 10000, PA_EINVAL, "max_iterations must be 1 to 10000");
+    PA_CHECK(tolerance >= 0, PA_EINVAL, "tolerance must be a number that is not negative");  // (false for NaN too)
+    PA_HIP(hipSetDevice(a->device));
+    return pa::abundance_estimate(a, max_iterations, tolerance, read_fraction, abundance, iterations_done, last_delta,
+                                  as_stream(stream));
+}
+
+void pa_abundance_free(pa_abundance *a) {
+    if (!a) return;
+    hipSetDevice(a->device);
+    pa::abundance_free(a);
+}
+
+pa_status pa_align_candidates(const pa_index *idx, const pa_reads *reads, const pa_params *params, uint8_t *read_type,
+                              uint64_t *set_off, uint32_t *sets, uint64_t cap, uint64_t *total, void *stream) {
+    PA_CHECK(idx && reads && read_type && set_off && total, PA_EINVAL, "NULL argument");
+    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
+    pa::DevParams dp;
+    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    PA_HIP(hipSetDevice(idx->device));
+    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    return pa::align_candidates(const_cast<pa_index *>(idx), reads, dp, read_type, set_off, sets, cap, total,
+                                as_stream(stream));
+}
+
 pa_status pa_profile_enable(pa_index *idx, int32_t enable) {
     PA_CHECK(idx != nullptr, PA_EINVAL, "NULL argument");
     idx->profile = enable != 0;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <map>
 #include <string>
 #include <vector>
 
@@ -228,6 +229,20 @@ struct pa_pileup {
     uint64_t reads_added = 0;
 };
 
+// Abundance accumulator of one index (pa_abund.hip): the reads' compatibility
+// classes.  The unique reads are counted per genome on the device; the classes
+// of the ambiguous reads, a few thousand at most, are merged on the host batch
+// after batch, keyed by their ascending genome list (the reported order).
+struct pa_abundance {
+    int device = 0;
+    const pa_index *idx = nullptr;     // the index it was made for, at
+    uint64_t epoch = 0;                //   this build of it
+    uint32_t n_genomes = 0;
+    std::vector<double> h_len;         // [G] L_g = |g| - k + 1 (forward windows)
+    unsigned long long *counts = nullptr;  // device [4 + G]: reads unique, ambiguous, unmapped, dropped; unique reads of g
+    std::map<std::vector<uint32_t>, uint64_t> classes;  // C -> n_C of the ambiguous reads
+};
+
 struct pa_result {
     int device = 0;
     uint32_t n_genomes = 0;
@@ -351,6 +366,22 @@ pa_status pileup_counts(const pa_pileup *p, uint32_t genome, uint64_t first, uin
                         hipStream_t st);
 pa_status pileup_variants(const pa_pileup *p, uint32_t min_depth, uint32_t min_alt_count, uint32_t min_alt_permille,
                           pa_variant *out, uint64_t cap, uint64_t *n, hipStream_t st);
+// abundance (pa_abund.hip; the candidate kernel is k_align_exact's sibling in pa_align.hip)
+pa_status candidates_pass(pa_index *idx, const pa_reads *r, const DevParams &p, const uint32_t *d_queue,
+                          const unsigned long long *d_count, uint64_t n_queued, uint32_t *d_len, const uint64_t *d_off,
+                          uint32_t *d_sets, hipStream_t st);
+pa_status abundance_create(const pa_index *idx, pa_abundance **out);
+pa_status abundance_reset(pa_abundance *a, hipStream_t st);
+void abundance_free(pa_abundance *a);
+pa_status abundance_add(pa_index *idx, const pa_reads *r, const DevParams &p, pa_abundance *acc, hipStream_t st);
+pa_status abundance_info(const pa_abundance *a, pa_abundance_info *out, hipStream_t st);
+pa_status abundance_classes(const pa_abundance *a, uint64_t *class_off, uint32_t *genomes, uint64_t *counts,
+                            uint64_t cap_classes, uint64_t cap_entries, uint64_t *n_classes, uint64_t *n_entries,
+                            hipStream_t st);
+pa_status abundance_estimate(const pa_abundance *a, uint32_t max_iterations, double tolerance, double *read_fraction,
+                             double *abundance, uint32_t *iterations_done, double *last_delta, hipStream_t st);
+pa_status align_candidates(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *type, uint64_t *set_off,
+                           uint32_t *sets, uint64_t cap, uint64_t *total, hipStream_t st);
 pa_status reads_measure(pa_reads *r, hipStream_t st);  // q_min / len_min of a batch (at its creation)
 // the filters an align of batch r applies: quality thresholds no read can fail dropped
 pa_status effective_params(const pa_reads *r, const DevParams &p, DevParams &out, hipStream_t st);

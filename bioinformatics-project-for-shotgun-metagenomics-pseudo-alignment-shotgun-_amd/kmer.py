@@ -628,6 +628,29 @@ _COVERAGE: "weakref.WeakKeyDictionary[PseudoAlignment, Optional[N.Coverage]]" = 
 # _COVERAGE and for the same reason: [accumulator or None, min_base_quality].
 _PILEUP: "weakref.WeakKeyDictionary[PseudoAlignment, list]" = weakref.WeakKeyDictionary()
 
+# Abundance accumulators of the alignments made with abundance=True, kept like
+# _COVERAGE and for the same reason.
+_ABUNDANCE: "weakref.WeakKeyDictionary[PseudoAlignment, Optional[N.Abundance]]" = weakref.WeakKeyDictionary()
+
+ABUNDANCE_HEADER = "#genome\tlength\tunique_reads\tcompatible_reads\testimated_reads\tread_fraction\tabundance\n"
+
+
+def abundance_text(names, lengths, unique_reads, compatible_reads, read_fraction, abundance, n_reads, iterations,
+                   last_delta, n_classes) -> str:
+    """The --abundance file: ABUNDANCE_HEADER, one tab-separated line per genome
+    (estimated_reads = read_fraction * n_reads; floats as format(x, ".9g")) and a
+    last comment line with the EM's iterations, its last delta and the classes."""
+    def f(x) -> str:
+        return format(float(x), ".9g")
+    lines = [ABUNDANCE_HEADER]
+    for g, name in enumerate(names):
+        lines.append("\t".join((str(name), str(int(lengths[g])), str(int(unique_reads[g])),
+                                str(int(compatible_reads[g])), f(float(read_fraction[g]) * n_reads),
+                                f(read_fraction[g]), f(abundance[g]))) + "\n")
+    lines.append(f"#iterations\t{int(iterations)}\tlast_delta\t{f(last_delta)}\tclasses\t{int(n_classes)}\n")
+    return "".join(lines)
+
+
 VARIANTS_HEADER = "#genome\tposition\tref\talt\tdepth\talt_count\tA\tC\tG\tT\n"
 
 
@@ -653,10 +676,17 @@ class PseudoAlignment:
     mapped read of those batches are counted per genome position -- those of
     quality byte >= ``min_base_quality`` when given -- and ``get_variants`` /
     ``write_variants`` report the positions where the sample differs from the
-    reference."""
+    reference.
+
+    ``abundance=True`` (not in the reference either): every read of those batches
+    is counted in its compatibility class, and ``get_abundance`` /
+    ``write_abundance`` report an EM estimate of the genomes' shares of the
+    sample."""
 
     def __init__(self, kmer_reference: KmerReference, coverage: bool = False, pileup: bool = False,
-                 min_base_quality: Optional[int] = None) -> None:
+                 min_base_quality: Optional[int] = None, abundance: bool = False) -> None:
+        if abundance:
+            _ABUNDANCE[self] = None  # (the accumulator is made with the first batch)
         if coverage:
             _COVERAGE[self] = None  # (the accumulator is made with the first batch)
         if min_base_quality is not None and (isinstance(min_base_quality, bool)
@@ -746,7 +776,7 @@ class PseudoAlignment:
         from data_file import FASTAQFile
         # (a coverage job takes the host-parsed path: the placements need the read columns)
         fresh = (not self._batches and not self._host and self._result is None and self not in _COVERAGE
-                 and self not in _PILEUP)
+                 and self not in _PILEUP and self not in _ABUNDANCE)
         err = _check_align_args(self.kmer_reference, m, p, min_read_quality, min_kmer_quality, max_genomes)
         n = None
         if fresh and err is None and os.environ.get("PA_STREAM", "1") != "0":
@@ -824,6 +854,8 @@ class PseudoAlignment:
                 self._coverage().add(reads, prm)
             if self in _PILEUP:
                 self._pileup().add(reads, prm, _PILEUP[self][1])
+            if self in _ABUNDANCE:
+                self._abundance().add(reads, prm)
             reads.close()
             delta = stats - self._gpu_stats
             self._gpu_stats = stats
@@ -1019,6 +1051,50 @@ class PseudoAlignment:
         fh.writelines("\t".join(str(v[c]) for c in ("genome", "position", "ref", "alt", "depth", "alt_count",
                                                     "A", "C", "G", "T")) + "\n"
                       for v in self.get_variants(min_depth, min_alt_count, min_alt_fraction))
+
+    def _abundance(self) -> "N.Abundance":
+        ab = _ABUNDANCE[self]
+        if ab is None:
+            ab = _ABUNDANCE[self] = N.Abundance(self.kmer_reference.index)
+        return ab
+
+    def get_abundance(self, iterations: int = 200, tolerance: float = 1e-9) -> Dict[str, Any]:
+        """The EM estimate over the reads' compatibility classes (DESIGN.md section
+        14): ``{"genomes": [{"genome", "length", "unique_reads", "compatible_reads",
+        "estimated_reads", "read_fraction", "abundance"}, ...], "reads", "iterations",
+        "last_delta", "classes"}``, one entry per genome of the index in FASTA
+        order.  compatible_reads counts the reads whose class holds the genome,
+        estimated_reads = read_fraction * reads.  ValueError for an alignment made
+        without ``abundance=True`` (or loaded from a file), iterations outside
+        1 .. 10000 and a negative tolerance."""
+        if self not in _ABUNDANCE:
+            raise ValueError("this alignment was made without abundance=True")
+        if isinstance(iterations, bool) or not isinstance(iterations, int) or not 1 <= iterations <= 10000:
+            raise ValueError("iterations must be an integer in 1 .. 10000")
+        if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float)) or not tolerance >= 0:
+            raise ValueError("tolerance must be a number that is not negative")
+        ab = self._abundance()
+        names = [g.identifier for g in self.kmer_reference.genomes]
+        G = len(names)
+        off, gen, cnt = ab.classes()
+        compatible = np.zeros(G, dtype=np.uint64)
+        np.add.at(compatible, gen, np.repeat(cnt, np.diff(off).astype(np.int64)))
+        unique = self._result.fetch()[1] if self._result is not None else np.zeros(G, dtype=np.uint64)
+        theta, share, done, delta = ab.estimate(iterations, float(tolerance))
+        n_reads = int(cnt.sum())
+        return {"genomes": [{"genome": names[g], "length": ab.lengths[g], "unique_reads": int(unique[g]),
+                             "compatible_reads": int(compatible[g]), "estimated_reads": float(theta[g]) * n_reads,
+                             "read_fraction": float(theta[g]), "abundance": float(share[g])} for g in range(G)],
+                "reads": n_reads, "iterations": done, "last_delta": delta, "classes": int(cnt.size)}
+
+    def write_abundance(self, fh, iterations: int = 200, tolerance: float = 1e-9) -> None:
+        """get_abundance as text (abundance_text)."""
+        a = self.get_abundance(iterations, tolerance)
+        rows = a["genomes"]
+        fh.write(abundance_text([r["genome"] for r in rows], [r["length"] for r in rows],
+                                [r["unique_reads"] for r in rows], [r["compatible_reads"] for r in rows],
+                                [r["read_fraction"] for r in rows], [r["abundance"] for r in rows], a["reads"],
+                                a["iterations"], a["last_delta"], a["classes"]))
 
     def get_reads_by_mapping_type(self, mapping_type: ReadMappingType) -> List[str]:
         return [rid for rid, d in self.reads.items() if d["mapping_type"] == mapping_type]

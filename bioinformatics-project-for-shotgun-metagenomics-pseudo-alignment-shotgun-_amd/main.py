@@ -8,6 +8,7 @@
                     [--assignments FILE]
                     [--variants FILE [--variant-min-depth N] [--variant-min-count N]
                      [--variant-min-fraction F] [--variant-min-base-quality Q]]
+                    [--abundance FILE [--abundance-iterations N] [--abundance-tolerance X]]
 
 Same tasks (reference | dumpref | align | dumpalign), flags, flag-combination
 checks, default coercions and error exits as src/main.py:61-402:
@@ -82,6 +83,19 @@ def _has_variants_flag(argv: List[str]) -> bool:
     return False
 
 
+_ABUNDANCE_FLAGS = ("--abundance", "--abundance-iterations", "--abundance-tolerance")
+
+
+def _has_abundance_flag(argv: List[str]) -> bool:
+    """An --abundance* flag on the command line, in any spelling argparse accepts
+    (as _has_coverage_flag)."""
+    for a in argv:
+        name = a.split("=", 1)[0]
+        if len(name) > 2 and name.startswith("--") and any(f.startswith(name) for f in _ABUNDANCE_FLAGS):
+            return True
+    return False
+
+
 def _early_reads_path(argv: List[str]) -> Optional[str]:
     """The --reads file of a `-t dumpalign` command line, read off argv before
     argparse and the heavy imports (every spelling argparse accepts: `-t X`,
@@ -114,6 +128,8 @@ def _early_reads_path(argv: List[str]) -> Optional[str]:
     if _has_assignments_flag(argv):  # (so does a job that writes every read's assignment)
         return None
     if _has_variants_flag(argv):  # (and a pileup job: the base counts need the read columns)
+        return None
+    if _has_abundance_flag(argv):  # (and an abundance job: the candidate pass needs the read columns)
         return None
     if os.environ.get("PA_GPUS", "1") not in ("", "0", "1"):  # (read-sharded over GPUs: no whole-file prefetch)
         return None
@@ -227,6 +243,12 @@ def parse_arguments(args: Optional[List[str]] = None) -> argparse.Namespace:
                         help="share of the depth the alternative base needs (default: 0.2)")
     parser.add_argument("--variant-min-base-quality", type=int, default=None,
                         help="count only bases whose quality byte is at least this (default: all)")
+    # not in the reference: the genomes' shares of the sample (compatibility classes + EM), dumpalign with --reads
+    parser.add_argument("--abundance", default=None, metavar="FILE",
+                        help="write one line per genome (reads, estimated reads, read fraction, abundance) to FILE")
+    parser.add_argument("--abundance-iterations", type=int, default=None, help="EM iterations at most (default: 200)")
+    parser.add_argument("--abundance-tolerance", type=float, default=None,
+                        help="stop once no read fraction moves by this much (default: 1e-9; 0: never)")
     return parser.parse_args(args)
 
 
@@ -302,7 +324,8 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
                                     min_read_quality, min_kmer_quality, max_genomes,
                                     prefetch=None, per_read: bool = False,
                                     coverage: bool = False, assignments: bool = False,
-                                    pileup: bool = False, min_base_quality=None) -> PseudoAlignment:
+                                    pileup: bool = False, min_base_quality=None,
+                                    abundance: bool = False) -> PseudoAlignment:
     # the FASTQ file goes straight to the device (parsed there, aligned in
     # windows); a file outside that subset of the grammar is parsed the exact
     # way (FASTAQFile), which also raises the reference's errors.  per_read
@@ -313,9 +336,10 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
     _stage("reference built")
     # coverage: the reads are parsed on the host and aligned on one device (align_reads_from_file
     # then takes its exact path: the placements need the read columns)
-    # pileup: likewise (the base counts need the read columns)
-    alignment = (PseudoAlignment(kmer_reference, coverage=coverage, pileup=pileup, min_base_quality=min_base_quality)
-                 if coverage or pileup else PseudoAlignment(kmer_reference))
+    # pileup: likewise (the base counts need the read columns); abundance: likewise (the candidate pass does)
+    alignment = (PseudoAlignment(kmer_reference, coverage=coverage, pileup=pileup, min_base_quality=min_base_quality,
+                                 abundance=abundance)
+                 if coverage or pileup or abundance else PseudoAlignment(kmer_reference))
     # assignments: the host parse too -- every read's line needs its id and the read columns
     if per_read or assignments:
         alignment.align_reads_from_container(FASTAQFile(reads_file).container, m, p, min_read_quality,
@@ -375,6 +399,16 @@ def _check_task(args: argparse.Namespace) -> None:
         if args.variant_min_base_quality is not None and args.variant_min_base_quality < 0:
             sys.exit("Error: --variant-min-base-quality must be at least 0.")
         validate_file_writable(args.variants, "Variants output")
+    if args.abundance is None and (args.abundance_iterations is not None or args.abundance_tolerance is not None):
+        sys.exit("Error: --abundance-iterations and --abundance-tolerance need --abundance.")
+    if args.abundance is not None:
+        if args.task != "dumpalign" or not args.reads:
+            sys.exit("Error: --abundance is only allowed for task 'dumpalign' with --reads.")
+        if args.abundance_iterations is not None and not 1 <= args.abundance_iterations <= 10000:
+            sys.exit("Error: --abundance-iterations must be in 1 .. 10000.")
+        if args.abundance_tolerance is not None and not args.abundance_tolerance >= 0:
+            sys.exit("Error: --abundance-tolerance must be at least 0.")
+        validate_file_writable(args.abundance, "Abundance output")
     if args.task == "reference":
         if extra:
             sys.exit("Error: For task 'reference', only -g, -k, -r, --filter-similar, and --similarity-threshold "
@@ -441,6 +475,10 @@ def _print_alignment(alignment: PseudoAlignment, args: argparse.Namespace) -> No
             alignment.write_variants(fh, 4 if args.variant_min_depth is None else args.variant_min_depth,
                                      2 if args.variant_min_count is None else args.variant_min_count,
                                      0.2 if args.variant_min_fraction is None else args.variant_min_fraction)
+    if args.abundance is not None:
+        with open(args.abundance, "w") as fh:
+            alignment.write_abundance(fh, 200 if args.abundance_iterations is None else args.abundance_iterations,
+                                      1e-9 if args.abundance_tolerance is None else args.abundance_tolerance)
 
 
 def _run(args: argparse.Namespace) -> None:
@@ -479,7 +517,8 @@ def _run(args: argparse.Namespace) -> None:
     elif args.task == "dumpalign":
         if args.referencefile and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
-            host_parsed = args.coverage or args.assignments is not None or args.variants is not None
+            host_parsed = (args.coverage or args.assignments is not None or args.variants is not None
+                           or args.abundance is not None)
             pf = None if host_parsed else _prefetch_reads(args.reads)
             ref = _load_reference(args.referencefile)
             _check_strands(args, ref)
@@ -487,13 +526,16 @@ def _run(args: argparse.Namespace) -> None:
                                                              coverage=args.coverage,
                                                              assignments=args.assignments is not None,
                                                              pileup=args.variants is not None,
-                                                             min_base_quality=args.variant_min_base_quality), args)
+                                                             min_base_quality=args.variant_min_base_quality,
+                                                             abundance=args.abundance is not None), args)
         elif args.genomefile and args.kmer_size and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
             validate_file_readable(args.genomefile, "Genome FASTA")
             # (a coverage job runs on one device: the depth arrays of read shards are not reduced;
-            # an assignments job too: its lines come from one host-parsed batch; and a pileup job, as coverage)
-            host_parsed = args.coverage or args.assignments is not None or args.variants is not None
+            # an assignments job too: its lines come from one host-parsed batch; a pileup job and an
+            # abundance job, as coverage)
+            host_parsed = (args.coverage or args.assignments is not None or args.variants is not None
+                           or args.abundance is not None)
             sharded = None if host_parsed else _dumpalign_sharded(args, filt)
             if sharded is not None:
                 _print_json(sharded.get_summary())
@@ -505,7 +547,8 @@ def _run(args: argparse.Namespace) -> None:
                                                              coverage=args.coverage,
                                                              assignments=args.assignments is not None,
                                                              pileup=args.variants is not None,
-                                                             min_base_quality=args.variant_min_base_quality), args)
+                                                             min_base_quality=args.variant_min_base_quality,
+                                                             abundance=args.abundance is not None), args)
         elif args.alignfile:
             validate_file_readable(args.alignfile, "Alignment output")
             try:

@@ -53,6 +53,8 @@ EXPORTS = (
     "pa_coverage_depth", "pa_coverage_free", "pa_align_placements",
     "pa_pileup_create", "pa_pileup_reset", "pa_pileup_add", "pa_pileup_stats_get", "pa_pileup_counts",
     "pa_pileup_variants", "pa_pileup_free",
+    "pa_abundance_create", "pa_abundance_reset", "pa_abundance_add", "pa_abundance_info_get", "pa_abundance_classes",
+    "pa_abundance_estimate", "pa_abundance_free", "pa_align_candidates",
     "pa_profile_enable", "pa_profile_read", "pa_profile_read_kernels", "pa_mem_trim",
     "pa_parse_text", "pa_parse_file", "pa_seqset_sizes", "pa_seqset_export", "pa_seqset_free", "pa_gz_inflate_file",
 )
@@ -94,6 +96,11 @@ class Stats(ctypes.Structure):
 
 class PileupStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("reads_piled", "reads_skipped", "bases_counted")]
+
+
+class AbundanceInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("reads_unique", "reads_ambiguous", "reads_unmapped", "reads_dropped",
+                                               "n_classes", "class_entries")]
 
 
 # pa_variant, one record of Pileup.variants (40 bytes, no implicit padding)
@@ -194,6 +201,15 @@ def lib():
         "pa_pileup_counts": (I32, [P, U32, U64, U64, P, P]),
         "pa_pileup_variants": (I32, [P, U32, U32, U32, P, U64, ctypes.POINTER(U64), P]),
         "pa_pileup_free": (None, [P]),
+        "pa_abundance_create": (I32, [P, PP]),
+        "pa_abundance_reset": (I32, [P, P]),
+        "pa_abundance_add": (I32, [P, P, ctypes.POINTER(Params), P, P]),
+        "pa_abundance_info_get": (I32, [P, ctypes.POINTER(AbundanceInfo), P]),
+        "pa_abundance_classes": (I32, [P, P, P, P, U64, U64, ctypes.POINTER(U64), ctypes.POINTER(U64), P]),
+        "pa_abundance_estimate": (I32, [P, U32, ctypes.c_double, P, P, ctypes.POINTER(U32),
+                                        ctypes.POINTER(ctypes.c_double), P]),
+        "pa_abundance_free": (None, [P]),
+        "pa_align_candidates": (I32, [P, P, ctypes.POINTER(Params), P, P, P, U64, ctypes.POINTER(U64), P]),
         "pa_profile_enable": (I32, [P, I32]),
         "pa_profile_read": (I32, [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.POINTER(U64)]),
         "pa_profile_read_kernels": (I32, [P, P, P]),
@@ -1128,6 +1144,109 @@ class Pileup:
     def close(self):
         if getattr(self, "_h", None):
             lib().pa_pileup_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def align_candidates_call(index: Index, reads: Reads, params: Params, cap: int, stream=None):
+    """One pa_align_candidates call with room for `cap` set entries (0: no
+    buffer): (status, types, set offsets, sets, total).  PA_EINVAL with total >
+    cap is the protocol's overflow: everything but the sets is valid."""
+    n = reads.n
+    types = np.zeros(max(n, 1), dtype=np.uint8)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    sets = np.zeros(max(int(cap), 1), dtype=np.uint32) if cap else None
+    total = U64(0)
+    st = lib().pa_align_candidates(index.handle, reads.handle, ctypes.byref(params), _ptr(types), _ptr(off),
+                                   _ptr(sets), int(cap), ctypes.byref(total), _stream(stream))
+    return st, types[:n], off, sets, int(total.value)
+
+
+def align_candidates(index: Index, reads: Reads, params: Params, stream=None):
+    """pa_align_candidates: (types, set offsets, sets) -- every read's mapping type
+    and its compatibility set C(r), ascending genome numbers (DESIGN.md section
+    14).  The first call has room for two entries per read; a batch with larger
+    sets is run once more with the capacity the first call reported."""
+    st, types, off, sets, total = align_candidates_call(index, reads, params, 2 * reads.n, stream)
+    if st == PA_EINVAL and total > 2 * reads.n:
+        st, types, off, sets, total = align_candidates_call(index, reads, params, total, stream)
+    _check(st)
+    if sets is None:
+        sets = np.zeros(0, dtype=np.uint32)
+    return types, off, sets[:total]
+
+
+class Abundance:
+    """The compatibility classes of the reads added to it and the EM estimate
+    made from them (pa_abundance): ``add`` classifies a
+    batch as align_detail does and counts every read's compatibility set;
+    ``classes`` reads the classes, ``estimate`` runs the EM."""
+
+    def __init__(self, index: Index):
+        h = P()
+        _check(lib().pa_abundance_create(index.handle, ctypes.byref(h)))
+        self._h = h
+        self._index = index  # (kept alive: the accumulator is checked against it)
+        self.n_genomes = index.n_genomes
+        self.lengths = [int(x) for x in index.genome_lengths]  # forward bases per genome
+
+    @property
+    def handle(self):
+        return self._h
+
+    def add(self, reads: Reads, params: Params, stream=None) -> None:
+        _check(lib().pa_abundance_add(self._index.handle, reads.handle, ctypes.byref(params), self._h,
+                                      _stream(stream)))
+
+    def reset(self, stream=None) -> None:
+        _check(lib().pa_abundance_reset(self._h, _stream(stream)))
+
+    def info(self, stream=None) -> dict:
+        """{"reads_unique", "reads_ambiguous", "reads_unmapped", "reads_dropped",
+        "n_classes", "class_entries"} since the last reset."""
+        s = AbundanceInfo()
+        _check(lib().pa_abundance_info_get(self._h, ctypes.byref(s), _stream(stream)))
+        return {n: int(getattr(s, n)) for n, _ in AbundanceInfo._fields_}
+
+    def classes_call(self, cap_classes: int, cap_entries: int, stream=None):
+        """One pa_abundance_classes call: (status, class offsets, genomes, counts,
+        n_classes, n_entries); with too small a capacity nothing is written."""
+        off = np.zeros(int(cap_classes) + 1, dtype=np.uint64)
+        cnt = np.zeros(max(int(cap_classes), 1), dtype=np.uint64)
+        gen = np.zeros(max(int(cap_entries), 1), dtype=np.uint32)
+        nc, ne = U64(0), U64(0)
+        st = lib().pa_abundance_classes(self._h, _ptr(off), _ptr(gen), _ptr(cnt), int(cap_classes), int(cap_entries),
+                                        ctypes.byref(nc), ctypes.byref(ne), _stream(stream))
+        return st, off, gen, cnt, int(nc.value), int(ne.value)
+
+    def classes(self, stream=None):
+        """(class offsets [n + 1], genomes, counts [n]): the classes sorted by
+        genome list.  The first call has room for 4096 classes and 16384 entries;
+        more are fetched once more with the sizes the first call reported."""
+        st, off, gen, cnt, nc, ne = self.classes_call(4096, 16384, stream)
+        if st == PA_EINVAL and (nc > 4096 or ne > 16384):
+            st, off, gen, cnt, nc, ne = self.classes_call(nc, ne, stream)
+        _check(st)
+        return off[:nc + 1], gen[:ne], cnt[:nc]
+
+    def estimate(self, iterations: int = 200, tolerance: float = 1e-9, stream=None):
+        """(read_fraction, abundance, iterations done, last delta): the EM over the
+        classes, float64 arrays per genome."""
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) \
+                or not 1 <= int(iterations) <= 10000:
+            raise ValueError("iterations must be an integer in 1 .. 10000")
+        G = self.n_genomes
+        theta = np.zeros(max(G, 1), dtype=np.float64)
+        ab = np.zeros(max(G, 1), dtype=np.float64)
+        it, delta = U32(0), ctypes.c_double(0.0)
+        _check(lib().pa_abundance_estimate(self._h, int(iterations), float(tolerance), _ptr(theta), _ptr(ab),
+                                           ctypes.byref(it), ctypes.byref(delta), _stream(stream)))
+        return theta[:G], ab[:G], int(it.value), float(delta.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().pa_abundance_free(self._h)
             self._h = None
 
     __del__ = close

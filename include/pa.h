@@ -36,6 +36,10 @@
  *                            occurrence sets it places reads with are kmers[w][g], src/kmer.py:140-150
  *   pa_pileup_*              per-base counts and SNV calls from the uniquely mapped reads (--variants);
  *                            no reference counterpart: the definition is DESIGN.md section 13
+ *   pa_abundance_* /         what is in the sample and in what proportions (--abundance): the reads'
+ *   pa_align_candidates      compatibility classes and an EM over them; no reference counterpart: the
+ *                            definition is DESIGN.md section 14 (T_r(g) is generate_genome_counts(
+ *                            map_count=False), src/kmer.py:431-442)
  *   pa_align_batch           one-shot host-buffer form of pa_align
  *   pa_align_fastq_file      FASTAQFile + align_reads_from_container as one
  *                            device-parsed stream                          src/data_file.py:134-158,
@@ -460,6 +464,65 @@ pa_status pa_pileup_counts(const pa_pileup *p, uint32_t genome, uint64_t first, 
 pa_status pa_pileup_variants(const pa_pileup *p, uint32_t min_depth, uint32_t min_alt_count,
                              uint32_t min_alt_permille, pa_variant *out, uint64_t cap, uint64_t *n, void *stream);
 void pa_pileup_free(pa_pileup *p);
+
+/* ---- abundance: compatibility classes and an EM over them ----
+ *
+ * Every read is classified as pa_align_detail classifies it with the same
+ * params.  Its compatibility set C(r): none for a dropped, unmapped or
+ * shorter-than-k read; {g} for a PA_UNIQUELY_MAPPED read with list [g]; for a
+ * PA_AMBIGUOUSLY_MAPPED read (a p-demoted one included) the genomes g with
+ * T_r(g) = max_h T_r(h), T_r(g) the number of distinct retained k-mers of the
+ * read whose genome set holds g (retained: passed --min-kmer-quality, in the
+ * index, passed --max-genomes) -- never empty.  A class is a distinct set C, an
+ * ascending genome list, with n_C = its reads; classes are reported sorted
+ * lexicographically by genome list, a proper prefix first.  N = sum of n_C.
+ *
+ * The EM: L_g = |g| - k + 1 (forward windows); theta_g = 1/G for every genome
+ * of the index; one iteration is d_C = sum_{g in C} theta_g / L_g, then
+ * theta'_g = (1/N) sum_{C holds g} n_C (theta_g / L_g) / d_C (a class with
+ * d_C == 0 adds nothing).  max_iterations (1 .. 10000, else PA_EINVAL)
+ * iterations run; the loop stops early after one with max_g |theta'_g -
+ * theta_g| < tolerance (0: never; negative or NaN: PA_EINVAL).  read_fraction[g]
+ * = theta_g, abundance[g] = (theta_g / L_g) / sum_h (theta_h / L_h) (0 when
+ * the sum is 0); N == 0 gives zeros and 0 iterations.  All in double precision
+ * and without floating-point atomics: the same classes give the same bits,
+ * whatever batches the reads came in.
+ *
+ * The accumulator serves its index until the next pa_index_reduce
+ * (pa_abundance_add: PA_EINVAL after, and for any other index); its bytes are
+ * not part of pa_index_info.  An abundance job runs on one device. */
+typedef struct pa_abundance pa_abundance;
+typedef struct {
+    uint64_t reads_unique, reads_ambiguous, reads_unmapped, reads_dropped, n_classes, class_entries;
+} pa_abundance_info;
+pa_status pa_abundance_create(const pa_index *idx, pa_abundance **out);
+pa_status pa_abundance_reset(pa_abundance *a, void *stream);
+/* Classify, find the ambiguous reads' sets, reduce them to classes on the
+ * device (a 64-bit hash of each list, a sort, every list compared with its
+ * run's first: a collision is never merged -- the batch is hashed again with
+ * another seed, PA_EINTERNAL after three).  Returns when done; after an error
+ * `acc` may hold a part of the batch: reset it. */
+pa_status pa_abundance_add(const pa_index *idx, const pa_reads *reads, const pa_params *params,
+                           pa_abundance *acc, void *stream);
+pa_status pa_abundance_info_get(const pa_abundance *a, pa_abundance_info *out, void *stream);
+/* class_off[n_classes + 1], genomes[n_entries], counts[n_classes].  *n_classes
+ * and *n_entries are always the full sizes; with too small a cap nothing is
+ * written and the call returns PA_EINVAL, so the caller retries with the
+ * capacities it now knows (NULL arrays behave as caps of 0). */
+pa_status pa_abundance_classes(const pa_abundance *a, uint64_t *class_off, uint32_t *genomes, uint64_t *counts,
+                               uint64_t cap_classes, uint64_t cap_entries, uint64_t *n_classes, uint64_t *n_entries,
+                               void *stream);
+/* read_fraction / abundance: n_genomes doubles each; any output may be NULL. */
+pa_status pa_abundance_estimate(const pa_abundance *a, uint32_t max_iterations, double tolerance,
+                                double *read_fraction, double *abundance, uint32_t *iterations_done,
+                                double *last_delta, void *stream);
+void pa_abundance_free(pa_abundance *a);
+/* Per read C(r): read_type[n], set_off[n + 1], sets (ascending genomes).  If
+ * cap < *total the call returns PA_EINVAL with *total, read_type and set_off
+ * valid: the caller retries (sets == NULL behaves as cap == 0), as pa_align_reads. */
+pa_status pa_align_candidates(const pa_index *idx, const pa_reads *reads, const pa_params *params,
+                              uint8_t *read_type, uint64_t *set_off, uint32_t *sets, uint64_t cap,
+                              uint64_t *total, void *stream);
 
 /* upload + pa_align + fetch for host buffers (stats and per-genome arrays accumulate: +=, min) */
 pa_status pa_align_batch(const pa_index *idx, const uint8_t *seq, const uint8_t *qual, const uint64_t *read_off,

@@ -33,6 +33,17 @@ pileup_add_s - coverage_add_s is k_pileup's cost over those atomics.  It adds
 the align kernels' own times over profiled pileup adds, pa_pileup_variants over
 the whole reference (its two passes and the copy of the records), and the stats.
 
+--mode abundance times pa_abundance_add next to
+pa_align_reads, pa_align_candidates, pa_coverage_add and pa_align_detail with
+its lists on the same library and batch.  The add is the assign pass, the
+candidate kernel over the ambiguous reads and the interning, and
+pa_align_candidates is the first two plus the copy of the sets to the host, so
+align_candidates_s - align_reads_s bounds the candidate kernel's two passes
+from above and abundance_add_s - align_reads_s the candidate kernel plus the
+interning.  It adds the align kernels' own times over one profiled add, the
+accumulator's info (reads by type, classes) and pa_abundance_estimate for 200
+iterations (tolerance 0) and with the default tolerance.
+
 --read-err / --rc-rate / --foreign-rate give bench.py's c2mix reads (0.015, 0.2, 0.2).
 """
 
@@ -108,7 +119,7 @@ def time_assign(index, reads, prm, runs):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("detail", "coverage", "assign", "pileup"), required=True)
+    ap.add_argument("--mode", choices=("detail", "coverage", "assign", "pileup", "abundance"), required=True)
     ap.add_argument("--reads", type=int, default=10_000_000)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--genomes", type=int, default=50)
@@ -176,6 +187,45 @@ def main():
             out[name + "_s"] = med
             out[name + "_records"] = int(holder["v"].size)
         pl.close()
+    elif args.mode == "abundance":
+        med, ts, entries = time_assign(index, reads, prm, args.runs)
+        out.update(align_reads_s=med, align_reads_runs_s=ts, list_entries=entries)
+        holder = {}
+        med, ts = timed(lambda: holder.update(c=N.align_candidates(index, reads, prm)), args.runs)
+        out.update(align_candidates_s=med, align_candidates_runs_s=ts, set_entries=int(holder["c"][2].size))
+        ab = N.Abundance(index)
+        med, ts = timed(lambda: ab.add(reads, prm), args.runs)
+        out.update(abundance_add_s=med, abundance_add_runs_s=ts, abundance_reads_per_s=args.reads / med)
+        index.profile_enable(True)
+        index.profile_read_kernels()
+        ab.add(reads, prm)
+        out["profiled_calls"] = 1
+        out["kernels_ms_launches"] = index.profile_read_kernels()
+        index.profile_enable(False)
+        ab.reset()
+        ab.add(reads, prm)
+        info = ab.info()
+        out["info"] = info
+        amb = max(info["reads_ambiguous"], 1)
+        out["candidate_passes_upper_s"] = out["align_candidates_s"] - out["align_reads_s"]
+        out["candidates_and_interning_s"] = out["abundance_add_s"] - out["align_reads_s"]
+        out["candidate_ns_per_ambiguous_read_upper"] = 1e9 * out["candidate_passes_upper_s"] / amb
+        out["added_ns_per_ambiguous_read"] = 1e9 * out["candidates_and_interning_s"] / amb
+        med, ts = timed(lambda: holder.update(e=ab.estimate(200, 0.0)), args.runs)
+        out.update(estimate_200_s=med, estimate_200_runs_s=ts)
+        med, ts = timed(lambda: holder.update(d=ab.estimate()), args.runs)
+        out.update(estimate_default_s=med, estimate_default_iterations=holder["d"][2],
+                   estimate_default_last_delta=holder["d"][3],
+                   read_fraction_max=float(holder["e"][0].max()), read_fraction_min=float(holder["e"][0].min()))
+        ab.close()
+        index.prepare_coverage()
+        cov = N.Coverage(index)
+        med, ts = timed(lambda: cov.add(reads, prm), args.runs)
+        out.update(coverage_add_s=med, coverage_add_runs_s=ts)
+        cov.close()
+        dmed, dts, dentries = time_detail(index, reads, prm, args.runs)
+        out.update(align_detail_s=dmed, align_detail_runs_s=dts,
+                   ratio_abundance_add_over_align_detail=out["abundance_add_s"] / dmed)
     else:
         med, ts, entries = time_detail(index, reads, prm, args.runs)
         out.update(align_detail_branch_s=med, align_detail_branch_runs_s=ts, list_entries=entries)
