@@ -244,23 +244,7 @@ __global__ __launch_bounds__(kBlock) void k_em_delta(const double *__restrict__ 
     if (threadIdx.x == 0) *out = red[0];
 }
 
-// Device buffers of one call, freed on every return once the stream is done with them.
-struct Bufs {
-    hipStream_t st;
-    std::vector<void *> p;
-    explicit Bufs(hipStream_t s) : st(s) {}
-    ~Bufs() {
-        (void)hipStreamSynchronize(st);
-        for (void *q : p) pa::dev_free(q);
-    }
-    template <typename T>
-    hipError_t get(T **out, uint64_t bytes) {
-        *out = nullptr;
-        const hipError_t e = pa::dev_malloc(out, std::max<uint64_t>(bytes, 16));
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-};
+using pa::Bufs;
 
 // The candidate pass left on the device.
 struct CandDev {
@@ -278,7 +262,7 @@ pa_status candidates_device(pa_index *idx, const pa_reads *r, const pa::DevParam
                             unsigned long long *counts, CandDev &out, Bufs &b, hipStream_t st) {
     const uint64_t n = r->n;
     const uint32_t G = idx->n_genomes;
-    PA_TRY(pa::assign_pass_device(idx, r, p, ~0ull, out.as, st));
+    PA_TRY(pa::assign_pass_device(idx, r, p, ~0ull, out.as, b, st));
     unsigned long long *d_qcount = nullptr;
     PA_HIP(b.get(&out.queue, n * 4));
     PA_HIP(b.get(&out.len, (n + 1) * 4));
@@ -299,13 +283,10 @@ pa_status candidates_device(pa_index *idx, const pa_reads *r, const pa::DevParam
     out.nq = nq;
     PA_TRY(pa::candidates_pass(idx, r, p, out.queue, d_qcount, nq, out.len, nullptr, nullptr, st));
     auto len64 = rocprim::make_transform_iterator(out.len, Widen{});
-    size_t tmp_bytes = 0;
-    void *tmp = nullptr;
-    PA_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, len64, out.off, (uint64_t)0, (size_t)(n + 1),
-                                   rocprim::plus<uint64_t>(), st));
-    PA_HIP(b.get(&tmp, tmp_bytes));
-    PA_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, len64, out.off, (uint64_t)0, (size_t)(n + 1),
-                                   rocprim::plus<uint64_t>(), st));
+    PA_HIP(pa::with_temp(b, [&](void *tmp, size_t &tmp_bytes) {
+        return rocprim::exclusive_scan(tmp, tmp_bytes, len64, out.off, (uint64_t)0, (size_t)(n + 1),
+                                       rocprim::plus<uint64_t>(), st);
+    }));
     uint64_t total = 0;
     PA_HIP(hipMemcpyAsync(&total, out.off + n, 8, hipMemcpyDeviceToHost, st));
     PA_HIP(hipStreamSynchronize(st));
@@ -339,7 +320,7 @@ pa_status intern_batch(const CandDev &c, pa_abundance *acc, Bufs &b, hipStream_t
     PA_HIP(b.get(&run_cnt, nq * 8));
     PA_HIP(b.get(&run_off, (nq + 1) * 8));
     PA_HIP(b.get(&err, 8));
-    size_t sort_bytes = 0, scan_bytes = 0, scan2_bytes = 0;
+    size_t sort_bytes = 0, scan_bytes = 0;  // (one temporary for the sort and the scan of every attempt)
     auto len64 = rocprim::make_transform_iterator(run_len, Widen{});
     PA_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, vals, vals2, (size_t)nq, 0, 64, st));
     PA_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, flag, rid, (size_t)nq, rocprim::plus<uint32_t>(), st));
@@ -378,12 +359,10 @@ pa_status intern_batch(const CandDev &c, pa_abundance *acc, Bufs &b, hipStream_t
     PA_HIP(hipMemcpyAsync(&n_runs, rid + (nq - 1), 4, hipMemcpyDeviceToHost, st));
     PA_HIP(hipStreamSynchronize(st));
     PA_HIP(hipMemsetAsync(run_len + n_runs, 0, 4, st));
-    PA_HIP(rocprim::exclusive_scan(nullptr, scan2_bytes, len64, run_off, (uint64_t)0, (size_t)n_runs + 1,
-                                   rocprim::plus<uint64_t>(), st));
-    void *tmp2 = nullptr;
-    PA_HIP(b.get(&tmp2, scan2_bytes));
-    PA_HIP(rocprim::exclusive_scan(tmp2, scan2_bytes, len64, run_off, (uint64_t)0, (size_t)n_runs + 1,
-                                   rocprim::plus<uint64_t>(), st));
+    PA_HIP(pa::with_temp(b, [&](void *tmp2, size_t &scan2_bytes) {
+        return rocprim::exclusive_scan(tmp2, scan2_bytes, len64, run_off, (uint64_t)0, (size_t)n_runs + 1,
+                                       rocprim::plus<uint64_t>(), st);
+    }));
     uint64_t entries = 0;
     PA_HIP(hipMemcpyAsync(&entries, run_off + n_runs, 8, hipMemcpyDeviceToHost, st));
     PA_HIP(hipStreamSynchronize(st));
@@ -425,31 +404,19 @@ pa_status collect(const pa_abundance *a, hipStream_t st, std::map<std::vector<ui
 namespace pa {
 
 pa_status abundance_create(const pa_index *idx, pa_abundance **out) {
-    pa_abundance *a = new (std::nothrow) pa_abundance();
+    ErrOp op("pa_abundance_create");
+    std::unique_ptr<pa_abundance, void (*)(pa_abundance *)> a(new (std::nothrow) pa_abundance(), abundance_free);
     if (!a) {
         set_error("out of host memory");
         return PA_ENOMEM;
     }
     const uint32_t G = idx->n_genomes;
-    a->device = idx->device;
-    a->idx = idx;
-    a->epoch = idx->epoch;
-    a->n_genomes = G;
-    a->h_len.assign(G, 0.0);
-    for (uint32_t g = 0; g < G; g++) {
-        const uint64_t len = idx->both_strands ? idx->h_fwd_len[g] : idx->h_goff[g + 1] - idx->h_goff[g];
-        a->h_len[g] = (double)len - (double)idx->k + 1.0;
-    }
-    hipError_t e = pa::dev_malloc(&a->counts, (4 + (uint64_t)G) * 8);
-    if (e == hipSuccess) e = hipMemset(a->counts, 0, (4 + (uint64_t)G) * 8);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error(std::string("pa_abundance_create: ") + hipGetErrorString(e));
-        abundance_free(a);
-        return e == hipErrorOutOfMemory ? PA_ENOMEM : PA_EDEVICE;
-    }
-    *out = a;
+    acc_bind(*a, idx);
+    for (uint64_t len : forward_lengths(idx)) a->h_len.push_back((double)len - (double)idx->k + 1.0);
+    PA_HIP(pa::dev_malloc(&a->counts, (4 + (uint64_t)G) * 8));
+    PA_HIP(hipMemset(a->counts, 0, (4 + (uint64_t)G) * 8));
+    PA_HIP(hipStreamSynchronize(nullptr));
+    *out = a.release();
     return PA_OK;
 }
 
@@ -470,11 +437,8 @@ pa_status abundance_add(pa_index *idx, const pa_reads *r, const DevParams &p, pa
     if (r->n == 0) return PA_OK;
     Bufs b(st);
     CandDev c;
-    pa_status rc = candidates_device(idx, r, p, ~0ull, acc->counts, c, b, st);
-    if (rc == PA_OK) rc = intern_batch(c, acc, b, st);
-    (void)hipStreamSynchronize(st);
-    assign_free(c.as);
-    return rc;
+    PA_TRY(candidates_device(idx, r, p, ~0ull, acc->counts, c, b, st));
+    return intern_batch(c, acc, b, st);
 }
 
 pa_status align_candidates(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *type, uint64_t *set_off,
@@ -486,18 +450,11 @@ pa_status align_candidates(pa_index *idx, const pa_reads *r, const DevParams &p,
     if (!sets) cap = 0;
     Bufs b(st);
     CandDev c;
-    pa_status rc = candidates_device(idx, r, p, cap, nullptr, c, b, st);
-    hipError_t e = hipSuccess;
-    if (rc == PA_OK) {
-        e = hipMemcpyAsync(type, c.as.type, n, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(set_off, c.off, (n + 1) * 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && c.sets) e = hipMemcpyAsync(sets, c.sets, c.total * 4, hipMemcpyDeviceToHost, st);
-    }
-    const hipError_t e2 = hipStreamSynchronize(st);
-    assign_free(c.as);
-    PA_TRY(rc);
-    PA_HIP(e);
-    PA_HIP(e2);
+    PA_TRY(candidates_device(idx, r, p, cap, nullptr, c, b, st));
+    PA_HIP(hipMemcpyAsync(type, c.as.type, n, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipMemcpyAsync(set_off, c.off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (c.sets) PA_HIP(hipMemcpyAsync(sets, c.sets, c.total * 4, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     *total = c.total;
     if (c.total > cap) {
         set_error("pa_align_candidates: cap smaller than the required length");

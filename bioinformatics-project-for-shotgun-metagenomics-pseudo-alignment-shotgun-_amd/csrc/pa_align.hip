@@ -929,17 +929,12 @@ struct Switches {
     int dbg_mode = env_int("PA_DBG_MODE", 0);        // PA_STATS / PA_DISSECT builds: stop each read after phase N
 };
 
-// Runtime choices as compile-time constants: each helper calls a generic
-// lambda with std::integral_constants, every call returning the same type; a
-// combination no helper lists is not instantiated.
-template <int N> using int_c = std::integral_constant<int, N>;
-
-// f(N) for the first N of the list that equals n, else for the last one
-template <int N0, int... Ns, class F>
-auto with_int(int n, F &&f) {
-    if constexpr (sizeof...(Ns) == 0) return f(int_c<N0>{});
-    else return n == N0 ? f(int_c<N0>{}) : with_int<Ns...>(n, f);
-}
+// Runtime choices as compile-time constants (with_int, pa_internal.h): each
+// helper calls a generic lambda with std::integral_constants, every call
+// returning the same type; a combination no helper lists is not instantiated.
+using pa::int_c;
+using pa::with_int;
+using pa::with_nw;
 
 // f(NEED_Q, WIN_Q, MG) for the six filter sets of a pass (window quality implies read quality)
 template <class F>
@@ -1099,7 +1094,7 @@ pa_status launch_lane(const AlignArgs &a0, const Switches &sw, hipStream_t st, p
 // The exact kernel for keys of nw words, timed (prof: the index, or null) as PA_PROF_EXACT.
 pa_status launch_exact(pa_index *prof, int nw, const ExactArgs &x, unsigned grid, hipStream_t st) {
     KernelTimer kt(prof, st, PA_PROF_EXACT);
-    with_int<1, 2, 3, 4, 5, 6, 7, 8>(nw, [&](auto w) {
+    with_nw(nw, [&](auto w) {
         hipLaunchKernelGGL(k_align_exact<w()>, dim3(grid), dim3(kBlock), 0, st, x);
     });
     PA_HIP(hipGetLastError());
@@ -1204,11 +1199,7 @@ pa_status ensure_workspace(pa_index *idx, size_t bytes) {
     pa::dev_free(idx->ws.ptr);
     idx->ws.ptr = nullptr;
     idx->ws.bytes = 0;
-    hipError_t e = pa::dev_malloc(&idx->ws.ptr, bytes);
-    if (e != hipSuccess) {
-        set_error(std::string("workspace allocation failed: ") + hipGetErrorString(e));
-        return PA_ENOMEM;
-    }
+    PA_HIP(pa::dev_malloc(&idx->ws.ptr, bytes));
     idx->ws.bytes = bytes;
     return PA_OK;
 }
@@ -1314,18 +1305,15 @@ pa_status reads_measure(pa_reads *r, hipStream_t st) {
     r->q_min = 255;
     r->len_min = 0;
     if (!r->qual || r->n == 0) return PA_OK;
+    Bufs b(st);
     uint32_t *d = nullptr, h[2] = {255, 0xFFFFFFFFu};
-    PA_HIP(pa::dev_malloc(&d, 8));
-    hipError_t e = hipMemcpyAsync(d, h, 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        const unsigned qgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(2048, (r->n_bases >> 14) + 1));
-        hipLaunchKernelGGL(k_reads_qstats, dim3(qgrid), dim3(256), 0, st, r->qual, r->off, r->n, d);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    pa::dev_free(d);
-    PA_HIP(e);
+    PA_HIP(b.get(&d, 8));
+    PA_HIP(hipMemcpyAsync(d, h, 8, hipMemcpyHostToDevice, st));
+    const unsigned qgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(2048, (r->n_bases >> 14) + 1));
+    hipLaunchKernelGGL(k_reads_qstats, dim3(qgrid), dim3(256), 0, st, r->qual, r->off, r->n, d);
+    PA_HIP(hipGetLastError());
+    PA_HIP(hipMemcpyAsync(h, d, 8, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     r->q_min = (int32_t)h[0];
     r->len_min = (int64_t)h[1];
     return PA_OK;
@@ -1631,7 +1619,7 @@ pa_status candidates_pass(pa_index *idx, const pa_reads *r, const DevParams &p_i
     PA_TRY(exact_args(idx, r, a, &out, x, egrid));
     x.use_queue = 1;
     const unsigned grid = (unsigned)std::min<uint64_t>(egrid, n_queued);
-    with_int<1, 2, 3, 4, 5, 6, 7, 8>(idx->nw, [&](auto w) {
+    with_nw(idx->nw, [&](auto w) {
         hipLaunchKernelGGL(k_abund_cand<w()>, dim3(grid), dim3(kBlock), 0, st, x);
     });
     PA_HIP(hipGetLastError());
@@ -1646,15 +1634,12 @@ pa_status align_detail(pa_index *idx, const pa_reads *r, const DevParams &p, uin
     if (list_off) list_off[0] = 0;
     if (list_total) *list_total = 0;
     if (n == 0) return PA_OK;
-    struct Bufs {  // the device buffers, freed on every return (once the stream is done with them)
-        hipStream_t st;
-        unsigned char *per_read = nullptr;  // qf | hr | len | type
-        uint64_t *off = nullptr;
-        uint32_t *lists = nullptr;
-        ~Bufs() { (void)hipStreamSynchronize(st), pa::dev_free(per_read), pa::dev_free(off), pa::dev_free(lists); }
-    } d{st};
-    PA_HIP(pa::dev_malloc(&d.per_read, n * 13));
-    uint32_t *d_qf = (uint32_t *)d.per_read, *d_hr = d_qf + n, *d_len = d_hr + n;
+    Bufs b(st);
+    unsigned char *per_read = nullptr;  // qf | hr | len | type
+    uint64_t *d_off = nullptr;
+    uint32_t *d_lists = nullptr;
+    PA_HIP(b.get(&per_read, n * 13));
+    uint32_t *d_qf = (uint32_t *)per_read, *d_hr = d_qf + n, *d_len = d_hr + n;
     uint8_t *d_type = (uint8_t *)(d_len + n);
     PA_TRY(detail_pass_device(idx, r, p, d_type, d_qf, d_hr, d_len, nullptr, nullptr, st));
     std::vector<uint32_t> lens(n);
@@ -1673,11 +1658,11 @@ pa_status align_detail(pa_index *idx, const pa_reads *r, const DevParams &p, uin
         set_error("pa_align_detail: list_cap smaller than the required list length");
         return PA_EINVAL;
     }
-    PA_HIP(pa::dev_malloc(&d.off, (n + 1) * 8));
-    PA_HIP(pa::dev_malloc(&d.lists, total * 4));
-    PA_HIP(hipMemcpyAsync(d.off, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-    PA_TRY(detail_pass_device(idx, r, p, d_type, d_qf, d_hr, d_len, d.off, d.lists, st));
-    PA_HIP(hipMemcpyAsync(lists, d.lists, total * 4, hipMemcpyDeviceToHost, st));
+    PA_HIP(b.get(&d_off, (n + 1) * 8));
+    PA_HIP(b.get(&d_lists, total * 4));
+    PA_HIP(hipMemcpyAsync(d_off, offs.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    PA_TRY(detail_pass_device(idx, r, p, d_type, d_qf, d_hr, d_len, d_off, d_lists, st));
+    PA_HIP(hipMemcpyAsync(lists, d_lists, total * 4, hipMemcpyDeviceToHost, st));
     PA_HIP(hipStreamSynchronize(st));
     return PA_OK;
 }

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <chrono>
@@ -25,7 +26,16 @@
 
 namespace pa {
 static thread_local std::string g_err;
+static thread_local const char *g_op = nullptr;
 void set_error(const std::string &msg) { g_err = msg; }
+ErrOp::ErrOp(const char *name) : prev(g_op) { g_op = name; }
+ErrOp::~ErrOp() { g_op = prev; }
+const char *err_op() { return g_op ? g_op : ""; }
+pa_status hip_failed(hipError_t e, const char *where) {
+    (void)hipGetLastError();
+    set_error((g_op ? std::string(g_op) + ": " : std::string()) + "HIP error: " + hipGetErrorString(e) + " at " + where);
+    return e == hipErrorOutOfMemory ? PA_ENOMEM : PA_EDEVICE;
+}
 }  // namespace pa
 
 using pa::set_error;
@@ -62,6 +72,50 @@ pa_status to_dev_params(const pa_params *p, uint32_t n_genomes, pa::DevParams *o
     out->mg = (int32_t)clampi(p->max_genomes, -1, (int64_t)n_genomes);
     out->flags = p->flags;
     return PA_OK;
+}
+
+// An index a call may use: not NULL, not emptied by a failed reduce.
+pa_status check_index(const pa_index *idx) {
+    PA_CHECK(idx != nullptr, PA_EINVAL, "NULL argument");
+    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    return PA_OK;
+}
+
+// A result made for this index, on its device.
+pa_status check_result(const pa_index *idx, const pa_result *acc) {
+    PA_CHECK(acc->n_genomes == idx->n_genomes, PA_EINVAL, "result was created for a different index");
+    PA_CHECK(acc->device == idx->device, PA_EINVAL, "index and result must live on the same device");
+    return PA_OK;
+}
+
+// ... and a batch of reads on its device.
+pa_status check_batch(const pa_index *idx, const pa_reads *reads) {
+    PA_CHECK(reads != nullptr, PA_EINVAL, "NULL argument");  // (before the index's state, as ever)
+    PA_TRY(check_index(idx));
+    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
+    return PA_OK;
+}
+
+// The accumulator of `type` (not NULL) was made for this build of this index.
+pa_status check_acc(const pa::AccBase *acc, const pa_index *idx, const char *type) {
+    PA_CHECK(pa::acc_matches(*acc, idx), PA_EINVAL,
+             std::string("the ") + type + " was made for another index, or for this one before a pa_index_reduce");
+    return PA_OK;
+}
+
+// The index's device current and its align-side view made.
+pa_status prepare_pass(const pa_index *idx, void *stream) {
+    PA_HIP(hipSetDevice(idx->device));
+    return pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream));
+}
+
+// What every per-batch entry point starts with, in this order: the handles,
+// the parameters, the device, the index's align-side view.
+pa_status begin_align(const pa_index *idx, const pa_reads *reads, const pa_params *params, void *stream,
+                      pa::DevParams *dp) {
+    PA_TRY(check_batch(idx, reads));
+    PA_TRY(to_dev_params(params, idx->n_genomes, dp));
+    return prepare_pass(idx, stream);
 }
 
 }  // namespace
@@ -173,8 +227,8 @@ pa_status pa_index_build_ex(int32_t device, const char *genomes, const uint64_t 
 }
 
 pa_status pa_index_reduce(pa_index *idx, const uint32_t *keep, uint32_t n_keep, uint32_t flags, void *stream) {
-    PA_CHECK(idx != nullptr && (n_keep == 0 || keep != nullptr), PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(n_keep == 0 || keep != nullptr, PA_EINVAL, "NULL argument");
+    PA_TRY(check_index(idx));
     for (uint32_t i = 0; i < n_keep; i++) {
         PA_CHECK(keep[i] < idx->n_genomes, PA_EINVAL, "genome number out of range");
         PA_CHECK(i == 0 || keep[i] > keep[i - 1], PA_EINVAL, "genome numbers must be ascending");
@@ -190,8 +244,7 @@ pa_status pa_index_reduce(pa_index *idx, const uint32_t *keep, uint32_t n_keep, 
 }
 
 pa_status pa_index_prepare(pa_index *idx, void *stream) {
-    PA_CHECK(idx != nullptr, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_TRY(check_index(idx));
     PA_HIP(hipSetDevice(idx->device));
     PA_TRY(pa::index_prepare(idx, as_stream(stream), ~0ull, true));
     PA_HIP(hipStreamSynchronize(as_stream(stream)));
@@ -199,8 +252,7 @@ pa_status pa_index_prepare(pa_index *idx, void *stream) {
 }
 
 pa_status pa_index_prepare_ex(pa_index *idx, uint64_t expected_reads, void *stream) {
-    PA_CHECK(idx != nullptr, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_TRY(check_index(idx));
     PA_HIP(hipSetDevice(idx->device));
     PA_TRY(pa::index_prepare(idx, as_stream(stream), expected_reads, true));
     PA_HIP(hipStreamSynchronize(as_stream(stream)));
@@ -239,16 +291,16 @@ pa_status pa_index_strands(const pa_index *idx, uint32_t *both) {
 
 pa_status pa_index_lookup(const pa_index *idx, const char *kmers, uint64_t n, uint32_t kmer_len, int64_t *cls_out,
                           uint32_t *size_out, void *stream) {
-    PA_CHECK(idx && cls_out && (n == 0 || kmers), PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(cls_out && (n == 0 || kmers), PA_EINVAL, "NULL argument");
+    PA_TRY(check_index(idx));
     PA_HIP(hipSetDevice(idx->device));
     return pa::index_lookup(idx, kmers, n, kmer_len, cls_out, size_out, as_stream(stream));
 }
 
 pa_status pa_index_positions(const pa_index *idx, const char *kmers, uint64_t n, uint32_t kmer_len, uint32_t flags,
                              pa_kmer_hit *hits, uint64_t cap, uint64_t *n_hits, void *stream) {
-    PA_CHECK(idx && n_hits && (n == 0 || kmers), PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(n_hits && (n == 0 || kmers), PA_EINVAL, "NULL argument");
+    PA_TRY(check_index(idx));
     PA_CHECK((flags & ~PA_POS_REVERSE) == 0, PA_EINVAL, "unknown flag bits");
     PA_CHECK(n < PA_POS_RC_BIT, PA_EINVAL, "too many queries");
     PA_HIP(hipSetDevice(idx->device));
@@ -257,8 +309,8 @@ pa_status pa_index_positions(const pa_index *idx, const char *kmers, uint64_t n,
 
 pa_status pa_index_class_genomes(const pa_index *idx, int64_t cls, uint32_t *genomes, uint32_t cap, uint32_t *n,
                                  void *stream) {
-    PA_CHECK(idx && n, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(n != nullptr, PA_EINVAL, "NULL argument");
+    PA_TRY(check_index(idx));
     PA_CHECK(cls >= 0 && (uint64_t)cls < (uint64_t)idx->n_genomes + idx->class_entries, PA_EINVAL,
              "class id out of range");
     if ((uint64_t)cls < idx->n_genomes) {
@@ -307,66 +359,51 @@ pa_status pa_reads_upload(int32_t device, const uint8_t *seq, const uint8_t *qua
         max_len = std::max<uint32_t>(max_len, (uint32_t)l);
     }
     PA_HIP(hipSetDevice(device));
-    pa_reads *r = new (std::nothrow) pa_reads();
+    pa::ErrOp op("pa_reads_upload");
+    std::unique_ptr<pa_reads, void (*)(pa_reads *)> r(new (std::nothrow) pa_reads(), pa_reads_free);
     PA_CHECK(r != nullptr, PA_ENOMEM, "out of host memory");
     r->device = device;
     r->n = n_reads;
     r->n_bases = nb;
     r->max_len = max_len;
     hipStream_t st = as_stream(stream);
-    auto fail = [&](hipError_t e) {
-        set_error(std::string("pa_reads_upload: ") + hipGetErrorString(e));
-        pa::dev_free(r->seq); pa::dev_free(r->qual); pa::dev_free(r->off);
-        delete r;
-        return e == hipErrorOutOfMemory ? PA_ENOMEM : PA_EDEVICE;
-    };
-    hipError_t e;
-    if ((e = pa::dev_malloc(&r->seq, nb + pa::kReadPad)) != hipSuccess) return fail(e);
-    if ((e = pa::dev_malloc(&r->qual, nb + pa::kReadPad)) != hipSuccess) return fail(e);
-    if ((e = pa::dev_malloc(&r->off, (n_reads + 1) * 8)) != hipSuccess) return fail(e);
+    PA_HIP(pa::dev_malloc(&r->seq, nb + pa::kReadPad));
+    PA_HIP(pa::dev_malloc(&r->qual, nb + pa::kReadPad));
+    PA_HIP(pa::dev_malloc(&r->off, (n_reads + 1) * 8));
     if (nb) {
-        if ((e = hipMemcpyAsync(r->seq, seq + read_off[0], nb, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
-        if ((e = hipMemcpyAsync(r->qual, qual + read_off[0], nb, hipMemcpyHostToDevice, st)) != hipSuccess) return fail(e);
+        PA_HIP(hipMemcpyAsync(r->seq, seq + read_off[0], nb, hipMemcpyHostToDevice, st));
+        PA_HIP(hipMemcpyAsync(r->qual, qual + read_off[0], nb, hipMemcpyHostToDevice, st));
     }
-    if (read_off[0] == 0) {
-        if ((e = hipMemcpyAsync(r->off, read_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, st)) != hipSuccess)
-            return fail(e);
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e);
-    } else {
-        uint64_t *tmp = new (std::nothrow) uint64_t[n_reads + 1];
-        if (!tmp) return fail(hipErrorOutOfMemory);
-        for (uint64_t i = 0; i <= n_reads; i++) tmp[i] = read_off[i] - read_off[0];
-        e = hipMemcpyAsync(r->off, tmp, (n_reads + 1) * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        delete[] tmp;
-        if (e != hipSuccess) return fail(e);
+    std::vector<uint64_t> rebased;  // (offsets that do not start at 0)
+    if (read_off[0] != 0) {
+        rebased.resize(n_reads + 1);
+        for (uint64_t i = 0; i <= n_reads; i++) rebased[i] = read_off[i] - read_off[0];
     }
-    if (pa::reads_measure(r, st) != PA_OK) return fail(hipErrorUnknown);
-    *out = r;
+    PA_HIP(hipMemcpyAsync(r->off, rebased.empty() ? read_off : rebased.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice,
+                          st));
+    PA_HIP(hipStreamSynchronize(st));
+    PA_TRY(pa::reads_measure(r.get(), st));
+    *out = r.release();
     return PA_OK;
 }
 
 pa_status pa_reads_synthesize_mix(const pa_index *idx, uint64_t n_reads, uint32_t read_len, uint64_t first_read,
                                   uint64_t seed, double sub_rate, double rc_rate, double foreign_rate, void *stream,
                                   pa_reads **out) {
-    PA_CHECK(idx && out, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(out != nullptr, PA_EINVAL, "NULL argument");
+    PA_TRY(check_index(idx));
     *out = nullptr;
     PA_CHECK(read_len > 0, PA_EINVAL, "read_len must be positive");
     PA_CHECK(rc_rate >= 0 && foreign_rate >= 0 && rc_rate + foreign_rate <= 1, PA_EINVAL,
              "rc_rate and foreign_rate must be >= 0 with a sum <= 1");
     PA_HIP(hipSetDevice(idx->device));
-    pa_reads *r = new (std::nothrow) pa_reads();
+    std::unique_ptr<pa_reads, void (*)(pa_reads *)> r(new (std::nothrow) pa_reads(), pa_reads_free);
     PA_CHECK(r != nullptr, PA_ENOMEM, "out of host memory");
-    pa_status rc = pa::reads_synthesize(idx, r, n_reads, read_len, first_read, seed, sub_rate, rc_rate, foreign_rate,
-                                        as_stream(stream));
-    if (rc == PA_OK) rc = pa::reads_measure(r, as_stream(stream));
-    if (rc != PA_OK) {
-        pa::dev_free(r->seq); pa::dev_free(r->qual); pa::dev_free(r->off);
-        delete r;
-        return rc;
-    }
-    *out = r;
+    r->device = idx->device;
+    PA_TRY(pa::reads_synthesize(idx, r.get(), n_reads, read_len, first_read, seed, sub_rate, rc_rate, foreign_rate,
+                                as_stream(stream)));
+    PA_TRY(pa::reads_measure(r.get(), as_stream(stream)));
+    *out = r.release();
     return PA_OK;
 }
 
@@ -425,29 +462,21 @@ void pa_reads_free(pa_reads *reads) {
 }
 
 pa_status pa_result_create(const pa_index *idx, pa_result **out) {
-    PA_CHECK(idx && out, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(out != nullptr, PA_EINVAL, "NULL argument");
+    PA_TRY(check_index(idx));
     *out = nullptr;
     PA_HIP(hipSetDevice(idx->device));
-    pa_result *r = new (std::nothrow) pa_result();
+    pa::ErrOp op("pa_result_create");
+    std::unique_ptr<pa_result, void (*)(pa_result *)> r(new (std::nothrow) pa_result(), pa_result_free);
     PA_CHECK(r != nullptr, PA_ENOMEM, "out of host memory");
     r->device = idx->device;
     r->n_genomes = idx->n_genomes;
     const uint64_t G = idx->n_genomes;
-    if (pa::dev_malloc(&r->sum_block, (6 + 2 * G) * 8) != hipSuccess ||
-        pa::dev_malloc(&r->min_block, std::max<uint64_t>(G, 1) * 8) != hipSuccess) {
-        pa::dev_free(r->sum_block);
-        delete r;
-        set_error("pa_result_create: device allocation failed");
-        return PA_ENOMEM;
-    }
-    pa_status rc = pa_result_reset(r, nullptr);
-    if (rc == PA_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = PA_EDEVICE;
-    if (rc != PA_OK) {
-        pa_result_free(r);
-        return rc;
-    }
-    *out = r;
+    PA_HIP(pa::dev_malloc(&r->sum_block, (6 + 2 * G) * 8));
+    PA_HIP(pa::dev_malloc(&r->min_block, std::max<uint64_t>(G, 1) * 8));
+    PA_TRY(pa_result_reset(r.get(), nullptr));
+    PA_HIP(hipStreamSynchronize(nullptr));
+    *out = r.release();
     return PA_OK;
 }
 
@@ -521,8 +550,8 @@ void pa_result_free(pa_result *res) {
 
 pa_status pa_align(const pa_index *idx, const pa_reads *reads, const pa_params *params, uint64_t read_index_base,
                    pa_result *acc, void *stream) {
-    PA_CHECK(idx && reads && acc, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_CHECK(reads && acc, PA_EINVAL, "NULL argument");
+    PA_TRY(check_index(idx));
     PA_CHECK(acc->n_genomes == idx->n_genomes, PA_EINVAL, "result was created for a different index");
     PA_CHECK(reads->device == idx->device && acc->device == idx->device, PA_EINVAL,
              "index, reads and result must live on the same device");
@@ -537,10 +566,9 @@ pa_status pa_align(const pa_index *idx, const pa_reads *reads, const pa_params *
 pa_status pa_align_fastq_file(const pa_index *idx, const char *path, const pa_params *params,
                               uint64_t read_index_base, pa_result *acc, int32_t threads, uint64_t window_bytes,
                               void *stream, uint64_t *n_reads) {
-    PA_CHECK(idx && path && acc, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
-    PA_CHECK(acc->n_genomes == idx->n_genomes, PA_EINVAL, "result was created for a different index");
-    PA_CHECK(acc->device == idx->device, PA_EINVAL, "index and result must live on the same device");
+    PA_CHECK(path && acc, PA_EINVAL, "NULL argument");
+    PA_TRY(check_index(idx));
+    PA_TRY(check_result(idx, acc));
     pa::DevParams dp;
     PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
     PA_HIP(hipSetDevice(idx->device));
@@ -552,10 +580,9 @@ pa_status pa_align_fastq_file(const pa_index *idx, const char *path, const pa_pa
 pa_status pa_align_fastq_range(const pa_index *idx, const char *path, uint64_t offset, uint64_t length,
                                const pa_params *params, uint64_t read_index_base, pa_result *acc, int32_t threads,
                                uint64_t window_bytes, void *stream, uint64_t *n_reads, pa_idset **ids) {
-    PA_CHECK(idx && path && acc, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
-    PA_CHECK(acc->n_genomes == idx->n_genomes, PA_EINVAL, "result was created for a different index");
-    PA_CHECK(acc->device == idx->device, PA_EINVAL, "index and result must live on the same device");
+    PA_CHECK(path && acc, PA_EINVAL, "NULL argument");
+    PA_TRY(check_index(idx));
+    PA_TRY(check_result(idx, acc));
     PA_CHECK(length > 0, PA_EINVAL, "empty byte range");
     if (ids) *ids = nullptr;
     pa::DevParams dp;
@@ -624,10 +651,9 @@ void pa_fastq_prefetch_free(pa_fastq_prefetch *pf) { pa::fastq_prefetch_free(pf)
 
 pa_status pa_align_fastq_prefetched(const pa_index *idx, pa_fastq_prefetch *pf, const pa_params *params,
                                     uint64_t read_index_base, pa_result *acc, void *stream, uint64_t *n_reads) {
-    PA_CHECK(idx && pf && acc, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
-    PA_CHECK(acc->n_genomes == idx->n_genomes, PA_EINVAL, "result was created for a different index");
-    PA_CHECK(acc->device == idx->device, PA_EINVAL, "index and result must live on the same device");
+    PA_CHECK(pf && acc, PA_EINVAL, "NULL argument");
+    PA_TRY(check_index(idx));
+    PA_TRY(check_result(idx, acc));
     pa::DevParams dp;
     PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
     PA_HIP(hipSetDevice(idx->device));
@@ -639,13 +665,9 @@ pa_status pa_align_fastq_prefetched(const pa_index *idx, pa_fastq_prefetch *pf, 
 pa_status pa_align_detail(const pa_index *idx, const pa_reads *reads, const pa_params *params, uint8_t *read_type,
                           uint32_t *filtered_kmers, uint32_t *redundant_kmers, uint64_t *list_off, uint32_t *lists,
                           uint64_t list_cap, uint64_t *list_total, void *stream) {
-    PA_CHECK(idx && reads && read_type && filtered_kmers && redundant_kmers && list_off, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
-    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
+    PA_CHECK(read_type && filtered_kmers && redundant_kmers && list_off, PA_EINVAL, "NULL argument");
     pa::DevParams dp;
-    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
-    PA_HIP(hipSetDevice(idx->device));
-    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    PA_TRY(begin_align(idx, reads, params, stream, &dp));
     return pa::align_detail(const_cast<pa_index *>(idx), reads, dp, read_type, filtered_kmers, redundant_kmers,
                             list_off, lists, list_cap, list_total, as_stream(stream));
 }
@@ -653,13 +675,9 @@ pa_status pa_align_detail(const pa_index *idx, const pa_reads *reads, const pa_p
 pa_status pa_align_reads(const pa_index *idx, const pa_reads *reads, const pa_params *params, uint8_t *read_type,
                          uint32_t *filtered_kmers, uint32_t *redundant_kmers, uint64_t *list_off, uint32_t *lists,
                          uint64_t list_cap, uint64_t *list_total, void *stream) {
-    PA_CHECK(idx && reads && read_type && list_off && list_total, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
-    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
+    PA_CHECK(read_type && list_off && list_total, PA_EINVAL, "NULL argument");
     pa::DevParams dp;
-    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
-    PA_HIP(hipSetDevice(idx->device));
-    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    PA_TRY(begin_align(idx, reads, params, stream, &dp));
     return pa::align_reads(const_cast<pa_index *>(idx), reads, dp, read_type, filtered_kmers, redundant_kmers,
                            list_off, lists, list_cap, list_total, as_stream(stream));
 }
@@ -667,8 +685,7 @@ pa_status pa_align_reads(const pa_index *idx, const pa_reads *reads, const pa_pa
 pa_status pa_align_batch(const pa_index *idx, const uint8_t *seq, const uint8_t *qual, const uint64_t *read_off,
                          uint64_t n_reads, uint64_t read_index_base, const pa_params *params, pa_stats *stats,
                          uint64_t *unique_reads, uint64_t *ambiguous_reads, uint64_t *first_key, void *stream) {
-    PA_CHECK(idx != nullptr, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_TRY(check_index(idx));
     pa_reads *r = nullptr;
     pa_result *res = nullptr;
     PA_TRY(pa_reads_upload(idx->device, seq, qual, read_off, n_reads, stream, &r));
@@ -708,8 +725,7 @@ pa_status pa_align_batch(const pa_index *idx, const uint8_t *seq, const uint8_t 
 // ---- coverage (csrc/pa_cover.hip) ---------------------------------------------------
 
 pa_status pa_index_prepare_coverage(pa_index *idx, void *stream) {
-    PA_CHECK(idx != nullptr, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_TRY(check_index(idx));
     PA_HIP(hipSetDevice(idx->device));
     PA_TRY(pa::index_prepare_coverage(idx, as_stream(stream)));
     PA_HIP(hipStreamSynchronize(as_stream(stream)));
@@ -717,9 +733,9 @@ pa_status pa_index_prepare_coverage(pa_index *idx, void *stream) {
 }
 
 pa_status pa_coverage_create(const pa_index *idx, pa_coverage **out) {
-    PA_CHECK(idx && out, PA_EINVAL, "NULL argument");
+    PA_CHECK(out != nullptr, PA_EINVAL, "NULL argument");
     *out = nullptr;
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_TRY(check_index(idx));
     PA_HIP(hipSetDevice(idx->device));
     return pa::coverage_create(idx, out);
 }
@@ -732,17 +748,14 @@ pa_status pa_coverage_reset(pa_coverage *cov, void *stream) {
 
 pa_status pa_coverage_add(const pa_index *idx, const pa_reads *reads, const pa_params *params, pa_coverage *acc,
                           void *stream) {
-    PA_CHECK(idx && reads && acc, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
-    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
-    PA_CHECK(acc->idx == idx && acc->epoch == idx->epoch, PA_EINVAL,
-             "the pa_coverage was made for another index, or for this one before a pa_index_reduce");
+    PA_CHECK(acc != nullptr, PA_EINVAL, "NULL argument");
+    PA_TRY(check_batch(idx, reads));
+    PA_TRY(check_acc(acc, idx, "pa_coverage"));
     pa::DevParams dp;
     PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
     PA_CHECK(acc->reads_added + reads->n < (1ull << 32), PA_EUNSUPPORTED,
              "a pa_coverage holds fewer than 2^32 reads (its depths are 32-bit)");
-    PA_HIP(hipSetDevice(idx->device));
-    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    PA_TRY(prepare_pass(idx, stream));
     return pa::coverage_place(const_cast<pa_index *>(idx), reads, dp, acc, nullptr, nullptr, nullptr, nullptr, 0,
                               nullptr, as_stream(stream));
 }
@@ -777,13 +790,9 @@ void pa_coverage_free(pa_coverage *cov) {
 pa_status pa_align_placements(const pa_index *idx, const pa_reads *reads, const pa_params *params,
                               uint8_t *read_type, uint64_t *list_off, uint32_t *lists, int64_t *starts,
                               uint64_t list_cap, uint64_t *list_total, void *stream) {
-    PA_CHECK(idx && reads && read_type && list_off, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
-    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
+    PA_CHECK(read_type && list_off, PA_EINVAL, "NULL argument");
     pa::DevParams dp;
-    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
-    PA_HIP(hipSetDevice(idx->device));
-    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    PA_TRY(begin_align(idx, reads, params, stream, &dp));
     return pa::coverage_place(const_cast<pa_index *>(idx), reads, dp, nullptr, read_type, list_off, lists, starts,
                               list_cap, list_total, as_stream(stream));
 }
@@ -791,9 +800,9 @@ pa_status pa_align_placements(const pa_index *idx, const pa_reads *reads, const 
 // ---- pileup (csrc/pa_pileup.hip) ------------------------------------------------------
 
 pa_status pa_pileup_create(const pa_index *idx, pa_pileup **out) {
-    PA_CHECK(idx && out, PA_EINVAL, "NULL argument");
+    PA_CHECK(out != nullptr, PA_EINVAL, "NULL argument");
     *out = nullptr;
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_TRY(check_index(idx));
     PA_HIP(hipSetDevice(idx->device));
     return pa::pileup_create(idx, out);
 }
@@ -806,17 +815,14 @@ pa_status pa_pileup_reset(pa_pileup *p, void *stream) {
 
 pa_status pa_pileup_add(const pa_index *idx, const pa_reads *reads, const pa_params *params,
                         uint32_t min_base_quality, pa_pileup *acc, void *stream) {
-    PA_CHECK(idx && reads && acc, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
-    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
-    PA_CHECK(acc->idx == idx && acc->epoch == idx->epoch, PA_EINVAL,
-             "the pa_pileup was made for another index, or for this one before a pa_index_reduce");
+    PA_CHECK(acc != nullptr, PA_EINVAL, "NULL argument");
+    PA_TRY(check_batch(idx, reads));
+    PA_TRY(check_acc(acc, idx, "pa_pileup"));
     pa::DevParams dp;
     PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
     PA_CHECK(acc->reads_added + reads->n < (1ull << 32), PA_EUNSUPPORTED,
              "a pa_pileup holds fewer than 2^32 reads (its counts are 32-bit)");
-    PA_HIP(hipSetDevice(idx->device));
-    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    PA_TRY(prepare_pass(idx, stream));
     return pa::pileup_add(const_cast<pa_index *>(idx), reads, dp, min_base_quality, acc, as_stream(stream));
 }
 
@@ -858,9 +864,9 @@ void pa_pileup_free(pa_pileup *p) {
 // ---- abundance (csrc/pa_abund.hip) ------------------------------------------------------
 
 pa_status pa_abundance_create(const pa_index *idx, pa_abundance **out) {
-    PA_CHECK(idx && out, PA_EINVAL, "NULL argument");
+    PA_CHECK(out != nullptr, PA_EINVAL, "NULL argument");
     *out = nullptr;
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
+    PA_TRY(check_index(idx));
     PA_HIP(hipSetDevice(idx->device));
     return pa::abundance_create(idx, out);
 }
@@ -873,15 +879,12 @@ pa_status pa_abundance_reset(pa_abundance *a, void *stream) {
 
 pa_status pa_abundance_add(const pa_index *idx, const pa_reads *reads, const pa_params *params, pa_abundance *acc,
                            void *stream) {
-    PA_CHECK(idx && reads && acc, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
-    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
-    PA_CHECK(acc->idx == idx && acc->epoch == idx->epoch, PA_EINVAL,
-             "the pa_abundance was made for another index, or for this one before a pa_index_reduce");
+    PA_CHECK(acc != nullptr, PA_EINVAL, "NULL argument");
+    PA_TRY(check_batch(idx, reads));
+    PA_TRY(check_acc(acc, idx, "pa_abundance"));
     pa::DevParams dp;
     PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
-    PA_HIP(hipSetDevice(idx->device));
-    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    PA_TRY(prepare_pass(idx, stream));
     return pa::abundance_add(const_cast<pa_index *>(idx), reads, dp, acc, as_stream(stream));
 }
 
@@ -920,13 +923,9 @@ void pa_abundance_free(pa_abundance *a) {
 
 pa_status pa_align_candidates(const pa_index *idx, const pa_reads *reads, const pa_params *params, uint8_t *read_type,
                               uint64_t *set_off, uint32_t *sets, uint64_t cap, uint64_t *total, void *stream) {
-    PA_CHECK(idx && reads && read_type && set_off && total, PA_EINVAL, "NULL argument");
-    PA_CHECK(!idx->released, PA_EINVAL, "the index was released by a failed pa_index_reduce: it may only be freed");
-    PA_CHECK(reads->device == idx->device, PA_EINVAL, "index and reads must live on the same device");
+    PA_CHECK(read_type && set_off && total, PA_EINVAL, "NULL argument");
     pa::DevParams dp;
-    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
-    PA_HIP(hipSetDevice(idx->device));
-    PA_TRY(pa::index_prepare(const_cast<pa_index *>(idx), as_stream(stream)));
+    PA_TRY(begin_align(idx, reads, params, stream, &dp));
     return pa::align_candidates(const_cast<pa_index *>(idx), reads, dp, read_type, set_off, sets, cap, total,
                                 as_stream(stream));
 }

@@ -71,39 +71,12 @@ __global__ __launch_bounds__(kBlock) void k_assign_unset(const uint8_t *__restri
 
 inline uint64_t up16(uint64_t b) { return (b + 15) / 16 * 16; }
 
-#define A_HIP(call)          \
-    do {                     \
-        hipError_t e_ = (call); \
-        if (e_ != hipSuccess) { \
-            (void)hipStreamSynchronize(st); \
-            pa::assign_free(out); \
-            if (tmp) pa::dev_free(tmp); \
-            PA_HIP(e_);      \
-        }                    \
-    } while (0)
-#define A_TRY(call)          \
-    do {                     \
-        pa_status s_ = (call); \
-        if (s_ != PA_OK) {   \
-            (void)hipStreamSynchronize(st); \
-            pa::assign_free(out); \
-            if (tmp) pa::dev_free(tmp); \
-            return s_;       \
-        }                    \
-    } while (0)
-
 }  // namespace
 
 namespace pa {
 
-void assign_free(AssignDev &d) {
-    pa::dev_free(d.block);
-    pa::dev_free(d.lists);
-    d = AssignDev{};
-}
-
 pa_status assign_pass_device(pa_index *idx, const pa_reads *r, const DevParams &p, uint64_t list_cap, AssignDev &out,
-                             hipStream_t st) {
+                             Bufs &b, hipStream_t st) {
     out = AssignDev{};
     const uint64_t n = r->n;
     if (n == 0) return PA_OK;
@@ -111,15 +84,13 @@ pa_status assign_pass_device(pa_index *idx, const pa_reads *r, const DevParams &
         set_error("pa_align_reads: a batch holds at most 2^32 - 2 reads (split it)");
         return PA_EUNSUPPORTED;
     }
-    void *tmp = nullptr;
     const uint64_t G = idx->n_genomes;
     // one allocation: off [n + 1] | qf [n] | hr [n] | len [n + 1] | g [n] | type [n] | scratch | unset count
     const uint64_t b_off = 0, b_qf = b_off + up16((n + 1) * 8), b_hr = b_qf + up16(n * 4), b_len = b_hr + up16(n * 4),
                    b_g = b_len + up16((n + 1) * 4), b_type = b_g + n * 4, b_scr = up16(b_type + n),
                    b_cnt = b_scr + up16((6 + 3 * G) * 8), bytes = b_cnt + 16;
     unsigned char *blk = nullptr;
-    A_HIP(pa::dev_malloc(&blk, bytes));
-    out.block = blk;
+    PA_HIP(b.get(&blk, bytes));
     out.off = (uint64_t *)(blk + b_off);
     out.qf = (uint32_t *)(blk + b_qf);
     out.hr = (uint32_t *)(blk + b_hr);
@@ -136,42 +107,37 @@ pa_status assign_pass_device(pa_index *idx, const pa_reads *r, const DevParams &
     as.lane = !(e && e[0] == '0');
     unsigned long long *d_cnt = (unsigned long long *)(blk + b_cnt);
     // g and type (adjacent) unset; the scratch counters and the count zero; len[n] = 0 (the scan's last input)
-    A_HIP(hipMemsetAsync(blk + b_g, 0xFF, n * 5, st));
-    A_HIP(hipMemsetAsync(blk + b_scr, 0, b_cnt + 16 - b_scr, st));
-    A_HIP(hipMemsetAsync(out.len + n, 0, 4, st));
+    PA_HIP(hipMemsetAsync(blk + b_g, 0xFF, n * 5, st));
+    PA_HIP(hipMemsetAsync(blk + b_scr, 0, b_cnt + 16 - b_scr, st));
+    PA_HIP(hipMemsetAsync(out.len + n, 0, 4, st));
     bool queued = false;
-    A_TRY(assign_classify(idx, r, p, as, &queued, st));
+    PA_TRY(assign_classify(idx, r, p, as, &queued, st));
     // list offsets: a device scan of the list lengths, widened on the fly
     auto len64 = rocprim::make_transform_iterator(out.len, Widen{});
-    size_t tmp_bytes = 0;
-    A_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, len64, out.off, (uint64_t)0, (size_t)(n + 1),
-                                  rocprim::plus<uint64_t>(), st));
-    A_HIP(pa::dev_malloc(&tmp, std::max<size_t>(tmp_bytes, 16)));
-    A_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, len64, out.off, (uint64_t)0, (size_t)(n + 1),
-                                  rocprim::plus<uint64_t>(), st));
+    PA_HIP(with_temp(b, [&](void *tmp, size_t &tmp_bytes) {
+        return rocprim::exclusive_scan(tmp, tmp_bytes, len64, out.off, (uint64_t)0, (size_t)(n + 1),
+                                       rocprim::plus<uint64_t>(), st);
+    }));
     uint64_t total = 0;
-    A_HIP(hipMemcpyAsync(&total, out.off + n, 8, hipMemcpyDeviceToHost, st));
-    A_HIP(hipStreamSynchronize(st));
+    PA_HIP(hipMemcpyAsync(&total, out.off + n, 8, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     out.total = total;
     if (total > 0 && total <= list_cap) {
-        A_HIP(pa::dev_malloc(&out.lists, total * 4));
+        PA_HIP(b.get(&out.lists, total * 4));
         if (queued) {
             hipLaunchKernelGGL(k_assign_scatter, dim3(grid_for(n)), dim3(kBlock), 0, st, as.g, out.off, n, total,
                                out.lists);
-            A_HIP(hipGetLastError());
+            PA_HIP(hipGetLastError());
         }
-        A_TRY(assign_lists(idx, r, p, as, queued, out.off, out.lists, st));
+        PA_TRY(assign_lists(idx, r, p, as, queued, out.off, out.lists, st));
     }
     // every read settled by exactly one kernel -- at least by one: none still unset
     hipLaunchKernelGGL(k_assign_unset, dim3(std::min(grid_for(n), 2048u)), dim3(kBlock), 0, st, out.type, n, d_cnt);
-    A_HIP(hipGetLastError());
+    PA_HIP(hipGetLastError());
     unsigned long long unset = 0;
-    A_HIP(hipMemcpyAsync(&unset, d_cnt, 8, hipMemcpyDeviceToHost, st));
-    A_HIP(hipStreamSynchronize(st));
-    pa::dev_free(tmp);
-    tmp = nullptr;
+    PA_HIP(hipMemcpyAsync(&unset, d_cnt, 8, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     if (unset) {
-        assign_free(out);
         set_error("pa_align_reads: " + std::to_string(unset) + " reads were settled by no kernel (invariant violated)");
         return PA_EINTERNAL;
     }
@@ -185,20 +151,17 @@ pa_status align_reads(pa_index *idx, const pa_reads *r, const DevParams &p, uint
     *list_total = 0;
     if (n == 0) return PA_OK;
     if (!lists) list_cap = 0;
+    Bufs b(st);
     AssignDev d;
-    PA_TRY(assign_pass_device(idx, r, p, list_cap, d, st));
-    hipError_t e = hipMemcpyAsync(type, d.type, n, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && qf) e = hipMemcpyAsync(qf, d.qf, n * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && hr) e = hipMemcpyAsync(hr, d.hr, n * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(list_off, d.off, (n + 1) * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && d.lists) e = hipMemcpyAsync(lists, d.lists, d.total * 4, hipMemcpyDeviceToHost, st);
-    const hipError_t e2 = hipStreamSynchronize(st);
-    const uint64_t total = d.total;
-    assign_free(d);
-    PA_HIP(e);
-    PA_HIP(e2);
-    *list_total = total;
-    if (total > list_cap) {
+    PA_TRY(assign_pass_device(idx, r, p, list_cap, d, b, st));
+    PA_HIP(hipMemcpyAsync(type, d.type, n, hipMemcpyDeviceToHost, st));
+    if (qf) PA_HIP(hipMemcpyAsync(qf, d.qf, n * 4, hipMemcpyDeviceToHost, st));
+    if (hr) PA_HIP(hipMemcpyAsync(hr, d.hr, n * 4, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipMemcpyAsync(list_off, d.off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (d.lists) PA_HIP(hipMemcpyAsync(lists, d.lists, d.total * 4, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
+    *list_total = d.total;
+    if (d.total > list_cap) {
         set_error("pa_align_reads: list_cap smaller than the required list length");
         return PA_EINVAL;
     }

@@ -156,20 +156,10 @@ __global__ void k_view_scatter(const uint32_t *__restrict__ K, const uint32_t *_
     head[slot] = rk;
 }
 
-#define C_HIP(call)                                                                                  \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            (void)hipGetLastError();                                                                 \
-            pa::set_error(std::string(what) + ": " + hipGetErrorString(e_) + " (" #call ")");       \
-            cleanup();                                                                               \
-            return e_ == hipErrorOutOfMemory ? PA_ENOMEM : PA_EDEVICE;                               \
-        }                                                                                            \
-    } while (0)
-
 template <int NW>
 pa_status view_build(pa_index *idx, hipStream_t st) {
-    const char *what = "pa_index_prepare_coverage";
+    pa::ErrOp op("pa_index_prepare_coverage");
+    pa::Bufs b(st);
     const uint32_t G = idx->n_genomes;
     const uint64_t total = idx->h_goff[G];
     const int k = (int)idx->k;
@@ -179,24 +169,14 @@ pa_status view_build(pa_index *idx, hipStream_t st) {
     }();
     uint32_t *head = nullptr, *first = nullptr, *K = nullptr, *K2 = nullptr, *V = nullptr, *V2 = nullptr;
     unsigned long long *d_n = nullptr;  // [0] valid windows, [1] errors
-    void *tmp = nullptr, *tmp2 = nullptr;
-    bool keep = false;
-    auto cleanup = [&] {
-        (void)hipStreamSynchronize(st);
-        pa::dev_free(K); pa::dev_free(K2); pa::dev_free(V); pa::dev_free(V2); pa::dev_free(d_n); pa::dev_free(tmp); pa::dev_free(tmp2);
-        if (!keep) {
-            pa::dev_free(head);
-            pa::dev_free(first);
-        }
-    };
     const Slot<NW> *table = (const Slot<NW> *)idx->table;
-    C_HIP(pa::dev_malloc(&head, std::max<uint64_t>(idx->cap, 1) * 4));
-    C_HIP(pa::dev_malloc(&K, total * 4));
-    C_HIP(pa::dev_malloc(&K2, total * 4));
-    C_HIP(pa::dev_malloc(&V, total * 4));
-    C_HIP(pa::dev_malloc(&V2, total * 4));
-    C_HIP(pa::dev_malloc(&d_n, 16));
-    C_HIP(hipMemsetAsync(d_n, 0, 16, st));
+    PA_HIP(b.get(&head, std::max<uint64_t>(idx->cap, 1) * 4));
+    PA_HIP(b.get(&K, total * 4));
+    PA_HIP(b.get(&K2, total * 4));
+    PA_HIP(b.get(&V, total * 4));
+    PA_HIP(b.get(&V2, total * 4));
+    PA_HIP(b.get(&d_n, 16));
+    PA_HIP(hipMemsetAsync(d_n, 0, 16, st));
     hipLaunchKernelGGL(k_fill32, dim3(grid_for(idx->cap)), dim3(kBlock), 0, st, head, idx->cap, NONE);
     hipLaunchKernelGGL(k_fill32, dim3(grid_for(total)), dim3(kBlock), 0, st, K, total, NONE);
     hipLaunchKernelGGL(k_iota32, dim3(grid_for(total)), dim3(kBlock), 0, st, V, total);
@@ -214,50 +194,45 @@ pa_status view_build(pa_index *idx, hipStream_t st) {
                 hipLaunchKernelGGL((k_view_scan<NW, true>), dim3(grid), dim3(kBlock), 0, st, idx->codes, idx->h_goff[g],
                                    nwin, k, mask0, table, idx->home, head, K, d_n);
         }
-    C_HIP(hipGetLastError());
+    PA_HIP(hipGetLastError());
     // (positions are < 2^32 - 1, so NONE sorts the windows without a k-mer to the end)
     rocprim::double_buffer<uint32_t> kb(K, K2), vb(V, V2);
-    size_t tmp_bytes = 0;
-    C_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, kb, vb, total, 0, 32, st));
-    C_HIP(pa::dev_malloc(&tmp, std::max<size_t>(tmp_bytes, 16)));
-    C_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, total, 0, 32, st));
+    PA_HIP(pa::with_temp(b, [&](void *tmp, size_t &tmp_bytes) {
+        return rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, total, 0, 32, st);
+    }));
     unsigned long long nv = 0;
-    C_HIP(hipMemcpyAsync(&nv, d_n, 8, hipMemcpyDeviceToHost, st));
-    C_HIP(hipStreamSynchronize(st));
+    PA_HIP(hipMemcpyAsync(&nv, d_n, 8, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     uint64_t n_pairs = 0;
     if (nv) {
         uint32_t *flag = kb.alternate(), *rank = vb.alternate();
         hipLaunchKernelGGL(k_view_flags, dim3((unsigned)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                            kb.current(), vb.current(), (uint64_t)nv, idx->goff, G, flag);
-        C_HIP(hipGetLastError());
-        size_t tmp2_bytes = 0;
-        C_HIP(rocprim::exclusive_scan(nullptr, tmp2_bytes, flag, rank, 0u, (size_t)nv, rocprim::plus<uint32_t>(), st));
-        C_HIP(pa::dev_malloc(&tmp2, std::max<size_t>(tmp2_bytes, 16)));
-        C_HIP(rocprim::exclusive_scan(tmp2, tmp2_bytes, flag, rank, 0u, (size_t)nv, rocprim::plus<uint32_t>(), st));
+        PA_HIP(hipGetLastError());
+        PA_HIP(pa::with_temp(b, [&](void *tmp, size_t &tmp_bytes) {
+            return rocprim::exclusive_scan(tmp, tmp_bytes, flag, rank, 0u, (size_t)nv, rocprim::plus<uint32_t>(), st);
+        }));
         uint32_t last_rank = 0, last_flag = 0;
-        C_HIP(hipMemcpyAsync(&last_rank, rank + (nv - 1), 4, hipMemcpyDeviceToHost, st));
-        C_HIP(hipMemcpyAsync(&last_flag, flag + (nv - 1), 4, hipMemcpyDeviceToHost, st));
-        C_HIP(hipStreamSynchronize(st));
+        PA_HIP(hipMemcpyAsync(&last_rank, rank + (nv - 1), 4, hipMemcpyDeviceToHost, st));
+        PA_HIP(hipMemcpyAsync(&last_flag, flag + (nv - 1), 4, hipMemcpyDeviceToHost, st));
+        PA_HIP(hipStreamSynchronize(st));
         n_pairs = (uint64_t)last_rank + last_flag;
-        C_HIP(pa::dev_malloc(&first, std::max<uint64_t>(n_pairs, 1) * 4));
+        PA_HIP(b.get(&first, std::max<uint64_t>(n_pairs, 1) * 4));
         // (every occupied slot is some window's k-mer: its fp is overwritten by its entry)
         hipLaunchKernelGGL(k_view_scatter<NW>, dim3((unsigned)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                            kb.current(), vb.current(), flag, rank, (uint64_t)nv, idx->codes, k, mask0, table, idx->home,
                            first, n_pairs, head, d_n + 1);
-        C_HIP(hipGetLastError());
+        PA_HIP(hipGetLastError());
         unsigned long long errs = 0;
-        C_HIP(hipMemcpyAsync(&errs, d_n + 1, 8, hipMemcpyDeviceToHost, st));
-        C_HIP(hipStreamSynchronize(st));
+        PA_HIP(hipMemcpyAsync(&errs, d_n + 1, 8, hipMemcpyDeviceToHost, st));
+        PA_HIP(hipStreamSynchronize(st));
         if (errs) {
             pa::set_error("pa_index_prepare_coverage: a genome window's k-mer is missing from the table");
-            cleanup();
             return PA_EINTERNAL;
         }
     }
-    keep = true;
-    cleanup();
-    idx->cov_head = head;
-    idx->cov_first = first;
+    idx->cov_head = b.release(head);  // the view outlives the call: the index owns it now
+    idx->cov_first = b.release(first);
     idx->cov_pairs = n_pairs;
     idx->cov_bytes = std::max<uint64_t>(idx->cap, 1) * 4 + (first ? std::max<uint64_t>(n_pairs, 1) * 4 : 0);
     idx->device_bytes += idx->cov_bytes;
@@ -510,48 +485,32 @@ pa_status index_prepare_coverage(pa_index *idx, hipStream_t st) {
         idx->cov_ready = 1;
         return PA_OK;
     }
-    switch (idx->nw) {
-        case 1: return view_build<1>(idx, st);
-        case 2: return view_build<2>(idx, st);
-        case 3: return view_build<3>(idx, st);
-        case 4: return view_build<4>(idx, st);
-        case 5: return view_build<5>(idx, st);
-        case 6: return view_build<6>(idx, st);
-        case 7: return view_build<7>(idx, st);
-        case 8: return view_build<8>(idx, st);
-        default: set_error("unsupported k"); return PA_EUNSUPPORTED;
+    if (idx->nw < 1 || idx->nw > 8) {
+        set_error("unsupported k");
+        return PA_EUNSUPPORTED;
     }
+    return with_nw(idx->nw, [&](auto w) { return view_build<w()>(idx, st); });
 }
 
 pa_status coverage_create(const pa_index *idx, pa_coverage **out) {
+    ErrOp op("pa_coverage_create");
     const uint32_t G = idx->n_genomes;
-    pa_coverage *c = new (std::nothrow) pa_coverage();
+    std::unique_ptr<pa_coverage, void (*)(pa_coverage *)> c(new (std::nothrow) pa_coverage(), coverage_free);
     if (!c) {
         set_error("out of host memory");
         return PA_ENOMEM;
     }
-    c->device = idx->device;
-    c->idx = idx;
-    c->epoch = idx->epoch;
-    c->n_genomes = G;
-    c->h_foff.assign(G + 1, 0);
-    for (uint32_t g = 0; g < G; g++)
-        c->h_foff[g + 1] = c->h_foff[g] + (idx->both_strands ? idx->h_fwd_len[g] : idx->h_goff[g + 1] - idx->h_goff[g]);
+    acc_bind(*c, idx);
+    c->h_foff = forward_offsets(idx);
     c->entries = c->h_foff[G] + G;
-    hipError_t e = pa::dev_malloc(&c->foff, (uint64_t)(G + 1) * 8);
-    if (e == hipSuccess) e = pa::dev_malloc(&c->diff, std::max<uint64_t>(2 * c->entries, 1) * 4);
-    if (e == hipSuccess) e = hipMemcpy(c->foff, c->h_foff.data(), (uint64_t)(G + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(c->diff, 0, std::max<uint64_t>(2 * c->entries, 1) * 4);
+    PA_HIP(pa::dev_malloc(&c->foff, (uint64_t)(G + 1) * 8));
+    PA_HIP(pa::dev_malloc(&c->diff, std::max<uint64_t>(2 * c->entries, 1) * 4));
+    PA_HIP(hipMemcpy(c->foff, c->h_foff.data(), (uint64_t)(G + 1) * 8, hipMemcpyHostToDevice));
+    PA_HIP(hipMemset(c->diff, 0, std::max<uint64_t>(2 * c->entries, 1) * 4));
     // (a device memset returns before it is done, and the first add may come on a
     // stream that does not wait for the null stream: the zeroes are there on return)
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error(std::string("pa_coverage_create: ") + hipGetErrorString(e));
-        coverage_free(c);
-        return e == hipErrorOutOfMemory ? PA_ENOMEM : PA_EDEVICE;
-    }
-    *out = c;
+    PA_HIP(hipStreamSynchronize(nullptr));
+    *out = c.release();
     return PA_OK;
 }
 
@@ -570,40 +529,28 @@ pa_status coverage_reset(pa_coverage *cov, hipStream_t st) {
     return PA_OK;
 }
 
-void placed_free(PlacedDev &pd) {
-    assign_free(pd.as);
-    pa::dev_free(pd.starts);
-    pa::dev_free(pd.agree);
-    pd = PlacedDev{};
-}
-
-pa_status place_device(pa_index *idx, const pa_reads *r, const DevParams &p, const char *what, pa_coverage *acc,
-                       uint64_t list_cap, bool want_starts, bool want_agree, PlacedDev &out, hipStream_t st) {
+pa_status place_device(pa_index *idx, const pa_reads *r, const DevParams &p, pa_coverage *acc,
+                       uint64_t list_cap, bool want_starts, bool want_agree, PlacedDev &out, Bufs &b, hipStream_t st) {
     out = PlacedDev{};
     const uint64_t n = r->n;
     PA_TRY(index_prepare_coverage(idx, st));
     if (n == 0) return PA_OK;
     int64_t *d_ws = nullptr;
     unsigned long long *d_err = nullptr;
-    auto cleanup = [&] {
-        (void)hipStreamSynchronize(st);
-        placed_free(out);
-        pa::dev_free(d_ws); pa::dev_free(d_err);
-    };
     // classification, list offsets and lists: the assign pass, left on the device
-    PA_TRY(assign_pass_device(idx, r, p, list_cap, out.as, st));
+    PA_TRY(assign_pass_device(idx, r, p, list_cap, out.as, b, st));
     const uint64_t total = out.as.total;
     if (total == 0 || !out.as.lists) return PA_OK;  // (nothing listed, or the capacity is short: nothing to place)
-    C_HIP(pa::dev_malloc(&d_err, 16));
-    C_HIP(hipMemsetAsync(d_err, 0, 16, st));
-    if (want_starts) C_HIP(pa::dev_malloc(&out.starts, total * 8));
-    if (want_agree) C_HIP(pa::dev_malloc(&out.agree, total));
+    PA_HIP(b.get(&d_err, 16));
+    PA_HIP(hipMemsetAsync(d_err, 0, 16, st));
+    if (want_starts) PA_HIP(b.get(&out.starts, total * 8));
+    if (want_agree) PA_HIP(b.get(&out.agree, total));
     const uint32_t wmax = r->max_len >= (uint64_t)idx->k ? (uint32_t)(r->max_len - idx->k + 1) : 1;
     const uint32_t rounds = std::max<uint32_t>(1, (wmax + 63) / 64);
     // waves to fill the device (256 CUs x 16) while the lanes' diagonals stay within 64 MiB
     uint64_t blocks = std::min<uint64_t>((total + 3) / 4, 1024);
     while (blocks > 1 && blocks * 4 * rounds * 64 * 8 > (64ull << 20)) blocks /= 2;
-    C_HIP(pa::dev_malloc(&d_ws, blocks * 4 * rounds * 64 * 8));
+    PA_HIP(b.get(&d_ws, blocks * 4 * rounds * 64 * 8));
     PlaceArgs a{};
     a.table = idx->table;
     a.cap = idx->cap;
@@ -632,29 +579,16 @@ pa_status place_device(pa_index *idx, const pa_reads *r, const DevParams &p, con
     a.ws = d_ws;
     a.rounds = rounds;
     a.err = d_err;
-    switch (idx->nw) {
-        case 1: launch_place<1>(a, (unsigned)blocks, st); break;
-        case 2: launch_place<2>(a, (unsigned)blocks, st); break;
-        case 3: launch_place<3>(a, (unsigned)blocks, st); break;
-        case 4: launch_place<4>(a, (unsigned)blocks, st); break;
-        case 5: launch_place<5>(a, (unsigned)blocks, st); break;
-        case 6: launch_place<6>(a, (unsigned)blocks, st); break;
-        case 7: launch_place<7>(a, (unsigned)blocks, st); break;
-        default: launch_place<8>(a, (unsigned)blocks, st); break;
-    }
-    C_HIP(hipGetLastError());
+    with_nw(idx->nw, [&](auto w) { launch_place<w()>(a, (unsigned)blocks, st); });
+    PA_HIP(hipGetLastError());
     if (acc) acc->depth_valid = 0;
     unsigned long long errs[2] = {0, 0};
-    C_HIP(hipMemcpyAsync(errs, d_err, 16, hipMemcpyDeviceToHost, st));
-    C_HIP(hipStreamSynchronize(st));
-    pa::dev_free(d_ws);
-    pa::dev_free(d_err);
-    d_ws = nullptr;
-    d_err = nullptr;
+    PA_HIP(hipMemcpyAsync(errs, d_err, 16, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
+    b.free(d_ws);  // (up to 64 MiB: not held through the caller's copies)
     if (errs[0] || errs[1]) {
-        set_error(std::string(what) + ": " + std::to_string(errs[0]) + " listed genomes without a voting window, " +
+        set_error(std::string(err_op()) + ": " + std::to_string(errs[0]) + " listed genomes without a voting window, " +
                   std::to_string(errs[1]) + " positions-view entries out of range (invariant violated)");
-        cleanup();
         return PA_EINTERNAL;
     }
     out.placed = true;
@@ -669,77 +603,62 @@ pa_status coverage_place(pa_index *idx, const pa_reads *r, const DevParams &p, p
     if (list_off) list_off[0] = 0;
     if (list_total) *list_total = 0;
     const bool want_lists = lists || starts;
+    ErrOp op(what);
+    Bufs b(st);
     PlacedDev pd;
-    auto cleanup = [&] {
-        (void)hipStreamSynchronize(st);
-        placed_free(pd);
-    };
     // (no lists for the *list_total query, or when the caller's capacity is short)
-    PA_TRY(place_device(idx, r, p, what, acc, acc ? ~0ull : (want_lists ? list_cap : 0), starts != nullptr, false, pd,
-                        st));
+    PA_TRY(place_device(idx, r, p, acc, acc ? ~0ull : (want_lists ? list_cap : 0), starts != nullptr, false, pd,
+                        b, st));
     if (n == 0) return PA_OK;
     const uint64_t total = pd.as.total;
     if (acc) acc->reads_added += n;
-    if (type) C_HIP(hipMemcpyAsync(type, pd.as.type, n, hipMemcpyDeviceToHost, st));
-    if (list_off) C_HIP(hipMemcpyAsync(list_off, pd.as.off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-    C_HIP(hipStreamSynchronize(st));
+    if (type) PA_HIP(hipMemcpyAsync(type, pd.as.type, n, hipMemcpyDeviceToHost, st));
+    if (list_off) PA_HIP(hipMemcpyAsync(list_off, pd.as.off, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     if (list_total) *list_total = total;
     if (want_lists && list_cap < total) {
         set_error(std::string(what) + ": list_cap smaller than the required list length");
-        cleanup();
         return PA_EINVAL;
     }
     if (pd.placed) {
-        if (lists) C_HIP(hipMemcpyAsync(lists, pd.as.lists, total * 4, hipMemcpyDeviceToHost, st));
-        if (starts) C_HIP(hipMemcpyAsync(starts, pd.starts, total * 8, hipMemcpyDeviceToHost, st));
-        C_HIP(hipStreamSynchronize(st));
+        if (lists) PA_HIP(hipMemcpyAsync(lists, pd.as.lists, total * 4, hipMemcpyDeviceToHost, st));
+        if (starts) PA_HIP(hipMemcpyAsync(starts, pd.starts, total * 8, hipMemcpyDeviceToHost, st));
+        PA_HIP(hipStreamSynchronize(st));
     }
-    cleanup();
     return PA_OK;
 }
 
 // The scanned accumulator (kept until the next add or reset).
 static pa_status coverage_scan(pa_coverage *cov, hipStream_t st) {
-    const char *what = "pa_coverage";
+    ErrOp op("pa_coverage");
     if (cov->depth_valid) return PA_OK;
     const uint64_t n = 2 * cov->entries;
-    void *tmp = nullptr;
-    auto cleanup = [&] {
-        (void)hipStreamSynchronize(st);
-        pa::dev_free(tmp);
-    };
-    if (!cov->depth) C_HIP(pa::dev_malloc(&cov->depth, std::max<uint64_t>(n, 1) * 4));
-    if (n) {
-        size_t tmp_bytes = 0;
-        C_HIP(rocprim::inclusive_scan(nullptr, tmp_bytes, cov->diff, cov->depth, (size_t)n, rocprim::plus<uint32_t>(),
-                                      st));
-        C_HIP(pa::dev_malloc(&tmp, std::max<size_t>(tmp_bytes, 16)));
-        C_HIP(rocprim::inclusive_scan(tmp, tmp_bytes, cov->diff, cov->depth, (size_t)n, rocprim::plus<uint32_t>(), st));
-    }
-    cleanup();
+    Bufs b(st);
+    if (!cov->depth) PA_HIP(pa::dev_malloc(&cov->depth, std::max<uint64_t>(n, 1) * 4));  // (the accumulator's: kept)
+    if (n)
+        PA_HIP(with_temp(b, [&](void *tmp, size_t &tmp_bytes) {
+            return rocprim::inclusive_scan(tmp, tmp_bytes, cov->diff, cov->depth, (size_t)n, rocprim::plus<uint32_t>(),
+                                           st);
+        }));
     cov->depth_valid = 1;
     return PA_OK;
 }
 
 pa_status coverage_summary(pa_coverage *cov, uint32_t min_coverage, uint64_t *cov_u, uint64_t *cov_a, uint64_t *sum_u,
                            uint64_t *sum_a, hipStream_t st) {
-    const char *what = "pa_coverage_summary";
+    ErrOp op("pa_coverage_summary");
     const uint32_t G = cov->n_genomes;
     if (G == 0) return PA_OK;
     PA_TRY(coverage_scan(cov, st));
+    Bufs b(st);
     unsigned long long *d_out = nullptr;
-    auto cleanup = [&] {
-        (void)hipStreamSynchronize(st);
-        pa::dev_free(d_out);
-    };
-    C_HIP(pa::dev_malloc(&d_out, (uint64_t)4 * G * 8));
+    PA_HIP(b.get(&d_out, (uint64_t)4 * G * 8));
     hipLaunchKernelGGL(k_cover_summary, dim3(2 * G), dim3(kBlock), 0, st, cov->depth, cov->entries, cov->foff, G,
                        min_coverage, d_out);
-    C_HIP(hipGetLastError());
+    PA_HIP(hipGetLastError());
     std::vector<unsigned long long> h((size_t)4 * G);
-    C_HIP(hipMemcpyAsync(h.data(), d_out, (uint64_t)4 * G * 8, hipMemcpyDeviceToHost, st));
-    C_HIP(hipStreamSynchronize(st));
-    cleanup();
+    PA_HIP(hipMemcpyAsync(h.data(), d_out, (uint64_t)4 * G * 8, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     uint64_t *outs[4] = {cov_u, cov_a, sum_u, sum_a};
     for (int i = 0; i < 4; i++)
         if (outs[i])

@@ -310,58 +310,43 @@ pa_status dump_t(const pa_index *idx, const uint8_t *keep, unsigned long long *f
                  std::vector<uint64_t> &h_t, std::vector<uint64_t> &h_flags, uint64_t &n_valid) {
     T *K = nullptr, *K2 = nullptr, *V = nullptr, *V2 = nullptr;
     unsigned long long *d_n = nullptr, *d_flags = nullptr;
-    void *tmp = nullptr;
-    auto cleanup = [&] {
-        pa::dev_free(K); pa::dev_free(K2); pa::dev_free(V); pa::dev_free(V2); pa::dev_free(d_n); pa::dev_free(d_flags); pa::dev_free(tmp);
-    };
-#define D_HIP(call)                                                                                       \
-    do {                                                                                                  \
-        hipError_t e_ = (call);                                                                           \
-        if (e_ != hipSuccess) {                                                                           \
-            pa::set_error(std::string("pa_index_dumpref: ") + hipGetErrorString(e_) + " (" #call ")");  \
-            cleanup();                                                                                    \
-            return e_ == hipErrorOutOfMemory ? PA_ENOMEM : PA_EDEVICE;                                    \
-        }                                                                                                 \
-    } while (0)
+    pa::Bufs b(st);
     const unsigned fg = grid_for(total) > 65536 ? 65536 : grid_for(total);
-    D_HIP(pa::dev_malloc(&K, total * sizeof(T)));
-    D_HIP(pa::dev_malloc(&K2, total * sizeof(T)));
-    D_HIP(pa::dev_malloc(&V, total * sizeof(T)));
-    D_HIP(pa::dev_malloc(&V2, total * sizeof(T)));
-    D_HIP(pa::dev_malloc(&d_n, 8));
-    D_HIP(hipMemsetAsync(d_n, 0, 8, st));
+    PA_HIP(b.get(&K, total * sizeof(T)));
+    PA_HIP(b.get(&K2, total * sizeof(T)));
+    PA_HIP(b.get(&V, total * sizeof(T)));
+    PA_HIP(b.get(&V2, total * sizeof(T)));
+    PA_HIP(b.get(&d_n, 8));
+    PA_HIP(hipMemsetAsync(d_n, 0, 8, st));
     hipLaunchKernelGGL(k_fill<T>, dim3(fg), dim3(kBlock), 0, st, K, total, (T)total);
     hipLaunchKernelGGL(k_iota<T>, dim3(fg), dim3(kBlock), 0, st, V, total);
     launch_keys<NW, T>(idx, keep, fp, K, d_n, st);
-    D_HIP(hipGetLastError());
+    PA_HIP(hipGetLastError());
     unsigned end_bit = 1;
     while (end_bit < 8 * sizeof(T) && (total >> end_bit)) end_bit++;
     rocprim::double_buffer<T> kb(K, K2), vb(V, V2);
-    size_t tmp_bytes = 0;
-    D_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, kb, vb, total, 0, end_bit, st));
-    D_HIP(pa::dev_malloc(&tmp, std::max<size_t>(tmp_bytes, 16)));
-    D_HIP(rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, total, 0, end_bit, st));
+    PA_HIP(pa::with_temp(b, [&](void *tmp, size_t &tmp_bytes) {
+        return rocprim::radix_sort_pairs(tmp, tmp_bytes, kb, vb, total, 0, end_bit, st);
+    }));
     unsigned long long nv = 0;
-    D_HIP(hipMemcpyAsync(&nv, d_n, 8, hipMemcpyDeviceToHost, st));
-    D_HIP(hipStreamSynchronize(st));
+    PA_HIP(hipMemcpyAsync(&nv, d_n, 8, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     n_valid = nv;
     const uint64_t nwords = (nv + 63) / 64;
-    D_HIP(pa::dev_malloc(&d_flags, std::max<uint64_t>(nwords, 1) * 8));
+    PA_HIP(b.get(&d_flags, std::max<uint64_t>(nwords, 1) * 8));
     if (nv) {
         hipLaunchKernelGGL(k_group_flags<T>, dim3((unsigned)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                            kb.current(), nv, d_flags);
-        D_HIP(hipGetLastError());
+        PA_HIP(hipGetLastError());
     }
     h_flags.assign(std::max<uint64_t>(nwords, 1), 0);
     h_t.resize(std::max<uint64_t>(nv, 1));
     std::vector<T> tv(std::max<uint64_t>(nv, 1));
     if (nv) {
-        D_HIP(hipMemcpyAsync(h_flags.data(), d_flags, nwords * 8, hipMemcpyDeviceToHost, st));
-        D_HIP(hipMemcpyAsync(tv.data(), vb.current(), nv * sizeof(T), hipMemcpyDeviceToHost, st));
+        PA_HIP(hipMemcpyAsync(h_flags.data(), d_flags, nwords * 8, hipMemcpyDeviceToHost, st));
+        PA_HIP(hipMemcpyAsync(tv.data(), vb.current(), nv * sizeof(T), hipMemcpyDeviceToHost, st));
     }
-    D_HIP(hipStreamSynchronize(st));
-#undef D_HIP
-    cleanup();
+    PA_HIP(hipStreamSynchronize(st));
     for (uint64_t i = 0; i < nv; i++) h_t[i] = tv[i];
     return PA_OK;
 }
@@ -370,24 +355,15 @@ template <int NW>
 pa_status dump_nw(const pa_index *idx, const uint8_t *keep, hipStream_t st, std::vector<uint64_t> &h_t,
                   std::vector<uint64_t> &h_flags, uint64_t &n_valid) {
     const uint64_t total = idx->h_goff[idx->n_genomes];
+    pa::Bufs b(st);
     unsigned long long *fp = nullptr;
-    PA_HIP(pa::dev_malloc(&fp, idx->cap * 8));
+    PA_HIP(b.get(&fp, idx->cap * 8));
     const unsigned fg = grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap);
     hipLaunchKernelGGL(k_fill<unsigned long long>, dim3(fg), dim3(kBlock), 0, st, fp, idx->cap, ~0ull);
     launch_first<NW>(idx, fp, st);
-    hipError_t e = hipGetLastError();
-    pa_status rc = PA_OK;
-    if (e != hipSuccess) {
-        pa::set_error(std::string("pa_index_dumpref: ") + hipGetErrorString(e));
-        rc = PA_EDEVICE;
-    } else if (total < 0xFFFFFFFFull) {
-        rc = dump_t<uint32_t, NW>(idx, keep, fp, total, st, h_t, h_flags, n_valid);
-    } else {
-        rc = dump_t<uint64_t, NW>(idx, keep, fp, total, st, h_t, h_flags, n_valid);
-    }
-    hipStreamSynchronize(st);
-    pa::dev_free(fp);
-    return rc;
+    PA_HIP(hipGetLastError());
+    if (total < 0xFFFFFFFFull) return dump_t<uint32_t, NW>(idx, keep, fp, total, st, h_t, h_flags, n_valid);
+    return dump_t<uint64_t, NW>(idx, keep, fp, total, st, h_t, h_flags, n_valid);
 }
 
 }  // namespace
@@ -397,6 +373,7 @@ namespace pa {
 pa_status index_dumpref(const pa_index *idx, const uint8_t *keep, const uint32_t *desc_of, uint32_t n_desc,
                         const char *const *desc_json, int fd, int threads, uint64_t *desc_unique, uint64_t *desc_multi,
                         uint64_t *desc_order, uint32_t *desc_last_genome, uint64_t *n_kmers_out, hipStream_t st) {
+    ErrOp op("pa_index_dumpref");
     const uint32_t G = idx->n_genomes;
     for (uint32_t d = 0; d < n_desc; d++) {
         desc_unique[d] = desc_multi[d] = 0;
@@ -411,19 +388,11 @@ pa_status index_dumpref(const pa_index *idx, const uint8_t *keep, const uint32_t
     std::vector<uint64_t> h_t, h_flags;
     uint64_t nv = 0;
     if (idx->k > 0 && idx->n_kmers > 0) {
-        pa_status rc = PA_EUNSUPPORTED;
-        switch (idx->nw) {
-            case 1: rc = dump_nw<1>(idx, keep, st, h_t, h_flags, nv); break;
-            case 2: rc = dump_nw<2>(idx, keep, st, h_t, h_flags, nv); break;
-            case 3: rc = dump_nw<3>(idx, keep, st, h_t, h_flags, nv); break;
-            case 4: rc = dump_nw<4>(idx, keep, st, h_t, h_flags, nv); break;
-            case 5: rc = dump_nw<5>(idx, keep, st, h_t, h_flags, nv); break;
-            case 6: rc = dump_nw<6>(idx, keep, st, h_t, h_flags, nv); break;
-            case 7: rc = dump_nw<7>(idx, keep, st, h_t, h_flags, nv); break;
-            case 8: rc = dump_nw<8>(idx, keep, st, h_t, h_flags, nv); break;
-            default: set_error("unsupported k");
+        if (idx->nw < 1 || idx->nw > 8) {
+            set_error("unsupported k");
+            return PA_EUNSUPPORTED;
         }
-        if (rc != PA_OK) return rc;
+        PA_TRY(with_nw(idx->nw, [&](auto w) { return dump_nw<w()>(idx, keep, st, h_t, h_flags, nv); }));
     }
     if (nv == 0) {
         if (n_kmers_out) *n_kmers_out = 0;

@@ -36,6 +36,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <functional>
 #include <chrono>
 #include <cstddef>
 #include <cstdio>
@@ -825,6 +826,7 @@ pa_status align_fastq_prefetched(pa_index *idx, pa_fastq_prefetch *pf, const Dev
 pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm, uint64_t base, pa_result *acc,
                            int threads, uint64_t window, hipStream_t st, uint64_t *n_reads, uint64_t offset,
                            uint64_t length, std::vector<uint64_t> *ids_out) {
+    ErrOp op("pa_align_fastq_file");
     // PA_STREAM_TIMING=1: where the time goes (stderr)
     const bool timing = env_on("PA_STREAM_TIMING");
     auto now = [] { return std::chrono::steady_clock::now(); };
@@ -884,65 +886,62 @@ pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm
         if (src.gz) pa::gz_close(src.gz);
         if (src.fd >= 0) close(src.fd);
     };
-#define F_HIP(call)                                                                                      \
-    do {                                                                                                 \
-        hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess) {                                                                          \
-            set_error(std::string("HIP error in pa_align_fastq_file: ") + hipGetErrorString(e_) + " (" #call ")"); \
-            cleanup();                                                                                   \
-            return e_ == hipErrorOutOfMemory ? PA_ENOMEM : PA_EDEVICE;                                   \
-        }                                                                                                \
-    } while (0)
+    uint64_t records = 0, got_next = 0;  // (got_next, read_ok: the reader thread's; it is joined by cleanup)
+    bool read_ok = true;
+    struct AtReturn {  // every return goes through cleanup, timed
+        std::function<void()> f;
+        ~AtReturn() { f(); }
+    } at_return{[&] {
+        const auto t_c = now();
+        cleanup();
+        if (timing)
+            fprintf(stderr, "[pa_stream] %llu records: alloc %.1f ms, index prepare %.1f ms, waits: reader %.1f, window "
+                            "meta %.1f, records %.1f ms; cleanup %.1f ms; total %.1f ms\n",
+                    (unsigned long long)records, t_alloc, t_prepare, t_wait_read, t_wait_meta, t_wait_rec,
+                    ms(t_c, now()), ms(t_start, now()));
+    }};
     for (int i = 0; i < 2; i++) {
-        F_HIP(hipHostMalloc((void **)&H[i], W, hipHostMallocDefault));
-        F_HIP(pa::dev_malloc(&D[i], dbytes));
-        F_HIP(hipEventCreateWithFlags(&ev_h2d[i], hipEventDisableTiming));
-        F_HIP(hipEventCreateWithFlags(&ev_carry[i], hipEventDisableTiming));
+        PA_HIP(hipHostMalloc((void **)&H[i], W, hipHostMallocDefault));
+        PA_HIP(pa::dev_malloc(&D[i], dbytes));
+        PA_HIP(hipEventCreateWithFlags(&ev_h2d[i], hipEventDisableTiming));
+        PA_HIP(hipEventCreateWithFlags(&ev_carry[i], hipEventDisableTiming));
     }
-    F_HIP(B.alloc(kCarryMax + W, est_rec, st));
-    F_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    PA_HIP(B.alloc(kCarryMax + W, est_rec, st));
+    PA_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
     t_alloc = ms(t_start, now());
     // the index's align-side view and the align queues, while window 0 is read
-    uint64_t got_next = 0;
-    bool read_ok = true;
     reader = std::thread([&] { read_ok = src.read(H[0], W, got_next); });
     auto tw = now();
-    rc = index_prepare(idx, st);
-    if (rc == PA_OK) rc = reserve_queues(idx, B.max_rec);
-    if (rc != PA_OK) {
-        cleanup();
-        return rc;
-    }
+    PA_TRY(index_prepare(idx, st));
+    PA_TRY(reserve_queues(idx, B.max_rec));
     t_prepare = ms(tw, now());
     tw = now();
     reader.join();
     t_wait_read += ms(tw, now());
     if (!read_ok) {  // (a corrupt .gz: the exact path raises the reference's error)
         set_error(std::string("read error in ") + path);
-        const bool gz = src.gz != nullptr;
-        cleanup();
-        return gz ? PA_ENOTCANON : PA_EIO;
+        return src.gz ? PA_ENOTCANON : PA_EIO;
     }
-    uint64_t carry = 0, records = 0, prev_end = 0;
+    uint64_t carry = 0, prev_end = 0;
     int cur = 0;
     bool last = src.eof, fail_grammar = false;
     uint64_t got = got_next;
-    F_HIP(hipMemcpyAsync(D[0] + kCarryMax, H[0], got, hipMemcpyHostToDevice, cs));
-    F_HIP(hipEventRecord(ev_h2d[0], cs));
+    PA_HIP(hipMemcpyAsync(D[0] + kCarryMax, H[0], got, hipMemcpyHostToDevice, cs));
+    PA_HIP(hipEventRecord(ev_h2d[0], cs));
     for (uint64_t win = 0;; win++) {
         // the host reads window win + 1 into the other pinned buffer meanwhile
         const int nxt = cur ^ 1;
         bool next_started = false;
         if (!last) {
-            if (win > 0) F_HIP(hipEventSynchronize(ev_h2d[nxt]));  // its previous copy is done
+            if (win > 0) PA_HIP(hipEventSynchronize(ev_h2d[nxt]));  // its previous copy is done
             reader = std::thread([&, nxt] { read_ok = src.read(H[nxt], W, got_next); });
             next_started = true;
         }
         // this window's text: [lo, hi) of D[cur], the carried tail in front of it
         const uint64_t lo = kCarryMax - carry, hi = kCarryMax + got;
-        F_HIP(hipStreamWaitEvent(st, ev_h2d[cur], 0));
-        if (carry) F_HIP(hipMemcpyAsync(D[cur] + lo, D[nxt] + prev_end, carry, hipMemcpyDeviceToDevice, st));
-        F_HIP(hipEventRecord(ev_carry[cur], st));
+        PA_HIP(hipStreamWaitEvent(st, ev_h2d[cur], 0));
+        if (carry) PA_HIP(hipMemcpyAsync(D[cur] + lo, D[nxt] + prev_end, carry, hipMemcpyDeviceToDevice, st));
+        PA_HIP(hipEventRecord(ev_carry[cur], st));
         if (hi == lo) break;  // (an empty last window: nothing after the previous records)
         WindowOut w;
         rc = parse_align_window(B, D[cur], lo, hi, last, idx, prm, base + records, acc, st, w, &t_wait_meta,
@@ -970,13 +969,12 @@ pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm
             }
             got = got_next;
             last = src.eof;
-            F_HIP(hipStreamWaitEvent(cs, ev_carry[cur], 0));
-            F_HIP(hipMemcpyAsync(D[nxt] + kCarryMax, H[nxt], got, hipMemcpyHostToDevice, cs));
-            F_HIP(hipEventRecord(ev_h2d[nxt], cs));
+            PA_HIP(hipStreamWaitEvent(cs, ev_carry[cur], 0));
+            PA_HIP(hipMemcpyAsync(D[nxt] + kCarryMax, H[nxt], got, hipMemcpyHostToDevice, cs));
+            PA_HIP(hipEventRecord(ev_h2d[nxt], cs));
         }
         cur = nxt;
     }
-#undef F_HIP
     if (reader.joinable()) reader.join();
     if (rc == PA_OK && records == 0) fail_grammar = true;  // no records: the exact parser raises
     if (rc == PA_OK && fail_grammar) {
@@ -985,38 +983,26 @@ pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm
     }
     if (rc == PA_OK && n_reads) *n_reads = records;
     if (rc == PA_OK && ids_out) {  // the range's id hashes (pa_idsets_disjoint: duplicates across ranges)
+        ErrOp ids_op("pa_align_fastq_range: id set export");
+        Bufs b(st);
         unsigned long long *d_out = nullptr, *d_n = nullptr;
         unsigned long long h_n = 0;
-        hipError_t e = pa::dev_malloc(&d_out, std::max<uint64_t>(records, 1) * 8);
-        if (e == hipSuccess) e = pa::dev_malloc(&d_n, 8);
-        if (e == hipSuccess) e = hipMemsetAsync(d_n, 0, 8, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_ids_compact, dim3((unsigned)std::min<uint64_t>((B.ids_cap + 255) / 256, 65536)),
-                               dim3(256), 0, st, B.ids, B.ids_cap, d_out, std::max<uint64_t>(records, 1), d_n);
-            e = hipGetLastError();
+        PA_HIP(b.get(&d_out, std::max<uint64_t>(records, 1) * 8));
+        PA_HIP(b.get(&d_n, 8));
+        PA_HIP(hipMemsetAsync(d_n, 0, 8, st));
+        hipLaunchKernelGGL(k_ids_compact, dim3((unsigned)std::min<uint64_t>((B.ids_cap + 255) / 256, 65536)),
+                           dim3(256), 0, st, B.ids, B.ids_cap, d_out, std::max<uint64_t>(records, 1), d_n);
+        PA_HIP(hipGetLastError());
+        PA_HIP(hipMemcpyAsync(&h_n, d_n, 8, hipMemcpyDeviceToHost, st));
+        PA_HIP(hipStreamSynchronize(st));
+        if (h_n != records) {  // (one hash per record: the set holds them all)
+            set_error("pa_align_fastq_range: id set export: the set holds another number of ids than records");
+            return PA_EDEVICE;
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(&h_n, d_n, 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess && h_n != records) e = hipErrorUnknown;  // (one hash per record: the set holds them all)
-        if (e == hipSuccess) {
-            ids_out->resize(h_n);
-            e = hipMemcpyAsync(ids_out->data(), d_out, h_n * 8, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-        }
-        pa::dev_free(d_out);
-        pa::dev_free(d_n);
-        if (e != hipSuccess) {
-            set_error(std::string("pa_align_fastq_range: id set export: ") + hipGetErrorString(e));
-            rc = PA_EDEVICE;
-        }
+        ids_out->resize(h_n);
+        PA_HIP(hipMemcpyAsync(ids_out->data(), d_out, h_n * 8, hipMemcpyDeviceToHost, st));
+        PA_HIP(hipStreamSynchronize(st));
     }
-    const auto t_c = now();
-    cleanup();
-    if (timing)
-        fprintf(stderr, "[pa_stream] %llu records: alloc %.1f ms, index prepare %.1f ms, waits: reader %.1f, window "
-                        "meta %.1f, records %.1f ms; cleanup %.1f ms; total %.1f ms\n",
-                (unsigned long long)records, t_alloc, t_prepare, t_wait_read, t_wait_meta, t_wait_rec, ms(t_c, now()),
-                ms(t_start, now()));
     return rc;
 }
 
@@ -1034,34 +1020,33 @@ pa_status idsets_disjoint(const std::vector<const std::vector<uint64_t> *> &sets
     PA_HIP(hipSetDevice(device));
     uint64_t cap = 1024;
     while (cap < 2 * total) cap <<= 1;
+    ErrOp op("pa_idsets_disjoint");
     unsigned long long *set = nullptr, *in = nullptr;
     unsigned int *dup = nullptr, h_dup = 0;
-    hipStream_t st = nullptr;
-    hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (e == hipSuccess) e = pa::dev_malloc(&set, cap * 8);
-    if (e == hipSuccess) e = pa::dev_malloc(&in, total * 8);
-    if (e == hipSuccess) e = pa::dev_malloc(&dup, 4);
-    if (e == hipSuccess) e = hipMemsetAsync(set, 0, cap * 8, st);
-    if (e == hipSuccess) e = hipMemsetAsync(dup, 0, 4, st);
+    struct Stream {  // (destroyed after the buffers on it are freed: declared first)
+        hipStream_t st = nullptr;
+        ~Stream() {
+            if (st) hipStreamDestroy(st);
+        }
+    } own;
+    PA_HIP(hipStreamCreateWithFlags(&own.st, hipStreamNonBlocking));
+    const hipStream_t st = own.st;
+    Bufs b(st);
+    PA_HIP(b.get(&set, cap * 8));
+    PA_HIP(b.get(&in, total * 8));
+    PA_HIP(b.get(&dup, 4));
+    PA_HIP(hipMemsetAsync(set, 0, cap * 8, st));
+    PA_HIP(hipMemsetAsync(dup, 0, 4, st));
     uint64_t at = 0;
     for (auto *v : sets) {
-        if (e == hipSuccess && !v->empty())
-            e = hipMemcpyAsync(in + at, v->data(), v->size() * 8, hipMemcpyHostToDevice, st);
+        if (!v->empty()) PA_HIP(hipMemcpyAsync(in + at, v->data(), v->size() * 8, hipMemcpyHostToDevice, st));
         at += v->size();
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_ids_union, dim3((unsigned)std::min<uint64_t>((total + 255) / 256, 65536)), dim3(256), 0, st,
-                           in, total, set, cap, dup);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_dup, dup, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (st) hipStreamSynchronize(st);
-    pa::dev_free(set);
-    pa::dev_free(in);
-    pa::dev_free(dup);
-    if (st) hipStreamDestroy(st);
-    PA_HIP(e);
+    hipLaunchKernelGGL(k_ids_union, dim3((unsigned)std::min<uint64_t>((total + 255) / 256, 65536)), dim3(256), 0, st,
+                       in, total, set, cap, dup);
+    PA_HIP(hipGetLastError());
+    PA_HIP(hipMemcpyAsync(&h_dup, dup, 4, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     *disjoint = h_dup == 0;
     return PA_OK;
 }

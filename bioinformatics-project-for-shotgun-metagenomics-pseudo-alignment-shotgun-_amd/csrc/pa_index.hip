@@ -1703,23 +1703,11 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
     uint32_t *lists = nullptr, *cs_id = nullptr, *err = nullptr, *lpos = nullptr;
     uint64_t *off = nullptr, *cs_key = nullptr, *cs_rep = nullptr, *rep_of = nullptr;
     unsigned long long *cnt = nullptr;  // [0] n_kmers [1] bump [2] n_multi [3] n_cls [4] bump2
-    pa_status rc = PA_OK;
-    auto cleanup = [&]() {
-        pa::dev_free(off); pa::dev_free(lists); pa::dev_free(lpos);
-        pa::dev_free(cs_key); pa::dev_free(cs_rep); pa::dev_free(cs_id); pa::dev_free(rep_of); pa::dev_free(cnt); pa::dev_free(err);
-    };
-#define B_HIP(call)                                                                                 \
-    do {                                                                                            \
-        hipError_t e_ = (call);                                                                     \
-        if (e_ != hipSuccess) {                                                                     \
-            pa::set_error(std::string("HIP error in index build: ") + hipGetErrorString(e_) + " (" #call ")"); \
-            cleanup();                                                                              \
-            return e_ == hipErrorOutOfMemory ? PA_ENOMEM : PA_EDEVICE;                              \
-        }                                                                                           \
-    } while (0)
-    B_HIP(pa::dev_malloc(&off, cap * 8));
-    B_HIP(pa::dev_malloc(&cnt, 8 * 8));
-    B_HIP(pa::dev_malloc(&err, 4));
+    pa::ErrOp op("index build");
+    pa::Bufs b(st);
+    PA_HIP(b.get(&off, cap * 8));
+    PA_HIP(b.get(&cnt, 8 * 8));
+    PA_HIP(b.get(&err, 4));
     // each window's place in its slot's genome list, taken in pass 1 (4 B per
     // base, while it fits an eighth of the free memory; PA_BUILD_LPOS=0: pass
     // 2 takes the places by CAS, as for keys of more than one word)
@@ -1733,9 +1721,10 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
             (void)hipGetLastError();
             lpos = nullptr;
         }
+        b.adopt(lpos);
     }
-    B_HIP(hipMemsetAsync(cnt, 0, 8 * 8, st));
-    B_HIP(hipMemsetAsync(err, 0, 4, st));
+    PA_HIP(hipMemsetAsync(cnt, 0, 8 * 8, st));
+    PA_HIP(hipMemsetAsync(err, 0, 4, st));
     // pass 1
     for (uint32_t g = 0; g < G; g++) {
         uint64_t len = idx->h_goff[g + 1] - idx->h_goff[g];
@@ -1749,25 +1738,24 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
             hipLaunchKernelGGL(k_build_insert<NW>, dim3(grid_for((nwin + wpt - 1) / wpt)), dim3(kBlock), 0, st,
                                idx->codes, idx->h_goff[g], nwin, k, mask0, g, table, idx->home, cnt + 0, err, wpt);
     }
-    B_HIP(hipGetLastError());
+    PA_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_build_prep<NW>, dim3(grid_for(cap, kBlock) > 65536 ? 65536 : grid_for(cap)), dim3(kBlock), 0,
                        st, table, cap, off, cnt + 1, cnt + 2, lpos != nullptr ? 1 : 0);
-    B_HIP(hipGetLastError());
+    PA_HIP(hipGetLastError());
     unsigned long long h_cnt[8];
     uint32_t h_err = 0;
-    B_HIP(hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
-    B_HIP(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
-    B_HIP(hipStreamSynchronize(st));
+    PA_HIP(hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+    PA_HIP(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     if (h_err) {
         pa::set_error("index build: hash table overflow or insert livelock (internal error)");
-        cleanup();
         return PA_EINTERNAL;
     }
     idx->n_kmers = h_cnt[0];
     const uint64_t list_total = h_cnt[1], n_multi = h_cnt[2];
     idx->n_multi = 0;
     if (n_multi > 0) {
-        B_HIP(pa::dev_malloc(&lists, list_total * 4));
+        PA_HIP(b.get(&lists, list_total * 4));
         for (uint32_t g = 0; g < G; g++) {
             uint64_t len = idx->h_goff[g + 1] - idx->h_goff[g];
             if ((uint64_t)k > len) continue;
@@ -1781,7 +1769,7 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
                                    idx->codes, idx->h_goff[g], nwin, k, mask0, g, table, idx->home, G, off, lists,
                                    wpt);
         }
-        B_HIP(hipGetLastError());
+        PA_HIP(hipGetLastError());
         // distinct genome sets: a hash over the multi slots' genome lists.  A
         // reference has few distinct sets (C2: 342, 2000 genomes in families:
         // ~10^4) however many multi-genome k-mers (10^9 at 8 Gbp), so the hash
@@ -1791,63 +1779,59 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
         unsigned sgrid = grid_for(cap) > 65536 ? 65536 : grid_for(cap);
         int cache_pos = 0;
         for (;;) {
-            B_HIP(pa::dev_malloc(&cs_key, cs_cap * 8));
-            B_HIP(pa::dev_malloc(&cs_rep, cs_cap * 8));
+            PA_HIP(b.get(&cs_key, cs_cap * 8));
+            PA_HIP(b.get(&cs_rep, cs_cap * 8));
             hipLaunchKernelGGL(k_fill_u64, dim3(grid_for(cs_cap) > 65536 ? 65536 : grid_for(cs_cap)), dim3(kBlock), 0,
                                st, cs_key, cs_cap, EMPTY);
             cache_pos = (uint64_t)G + cs_cap < 0xFFF00000ull ? 1 : 0;  // (G + position below pass 2's marks)
             hipLaunchKernelGGL(k_class_insert<NW>, dim3(sgrid), dim3(kBlock), 0, st, table, cap, G, off, lists,
                                cs_key, cs_rep, cs_cap, err, cache_pos);
-            B_HIP(hipGetLastError());
-            B_HIP(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
-            B_HIP(hipStreamSynchronize(st));
+            PA_HIP(hipGetLastError());
+            PA_HIP(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
+            PA_HIP(hipStreamSynchronize(st));
             if (!(h_err & 4u) || cs_cap >= cs_max) break;
-            pa::dev_free(cs_key);
-            pa::dev_free(cs_rep);
-            cs_key = cs_rep = nullptr;
-            B_HIP(hipMemsetAsync(err, 0, 4, st));
+            b.free(cs_key);
+            b.free(cs_rep);
+            PA_HIP(hipMemsetAsync(err, 0, 4, st));
             cs_cap = std::min<uint64_t>(cs_max, 4 * cs_cap);
         }
         if (h_err & 4u) {
             pa::set_error("index build: genome-set table overflow (internal error)");
-            cleanup();
             return PA_EINTERNAL;
         }
-        B_HIP(pa::dev_malloc(&cs_id, cs_cap * 4));
+        PA_HIP(b.get(&cs_id, cs_cap * 4));
         // class ids: at most min(n_multi, cs_cap) classes
         const uint64_t max_cls = std::min<uint64_t>(n_multi, cs_cap);
-        B_HIP(pa::dev_malloc(&idx->class_size, max_cls * 4));
-        B_HIP(pa::dev_malloc(&idx->class_off, max_cls * 8));
-        B_HIP(pa::dev_malloc(&rep_of, max_cls * 8));
+        PA_HIP(pa::dev_malloc(&idx->class_size, max_cls * 4));
+        PA_HIP(pa::dev_malloc(&idx->class_off, max_cls * 8));
+        PA_HIP(b.get(&rep_of, max_cls * 8));
         hipLaunchKernelGGL(k_class_number<NW>, dim3(grid_for(cs_cap) > 65536 ? 65536 : grid_for(cs_cap)), dim3(kBlock),
                            0, st, cs_key, cs_rep, cs_id, cs_cap, (const Slot<NW> *)table, idx->class_size,
                            idx->class_off, rep_of, cnt + 3, cnt + 4);
-        B_HIP(hipGetLastError());
-        B_HIP(hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
-        B_HIP(hipStreamSynchronize(st));
+        PA_HIP(hipGetLastError());
+        PA_HIP(hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+        PA_HIP(hipStreamSynchronize(st));
         const uint64_t n_cls = h_cnt[3], entries = h_cnt[4];
         if ((uint64_t)G + entries >= (uint64_t)PA_TILE_REP) {  // (bit 31 of a class id is the position bit, cls_of)
             pa::set_error("index build: too many distinct genome-set entries for 31-bit class ids");
-            cleanup();
             return PA_EUNSUPPORTED;
         }
-        B_HIP(pa::dev_malloc(&idx->class_genomes, std::max<uint64_t>(entries, 1) * 4));
+        PA_HIP(pa::dev_malloc(&idx->class_genomes, std::max<uint64_t>(entries, 1) * 4));
         hipLaunchKernelGGL(k_class_copy, dim3((unsigned)std::min<uint64_t>(n_cls, 65536)), dim3(kBlock), 0, st, n_cls,
                            rep_of, idx->class_size, idx->class_off, off, lists, idx->class_genomes);
         if (G <= 64) {
-            B_HIP(pa::dev_malloc(&idx->class_mask, std::max<uint64_t>(entries, 1) * 8));
+            PA_HIP(pa::dev_malloc(&idx->class_mask, std::max<uint64_t>(entries, 1) * 8));
             hipLaunchKernelGGL(k_class_masks, dim3((unsigned)std::min<uint64_t>((n_cls + kBlock - 1) / kBlock, 4096)),
                                dim3(kBlock), 0, st, n_cls, idx->class_off, idx->class_genomes, idx->class_mask);
         }
         hipLaunchKernelGGL(k_class_assign<NW>, dim3(sgrid), dim3(kBlock), 0, st, table, cap, off, lists, cs_key,
                            cs_rep, cs_id, cs_cap, idx->class_size, idx->class_off, G, err, cache_pos);
-        B_HIP(hipGetLastError());
-        B_HIP(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
-        B_HIP(hipStreamSynchronize(st));
+        PA_HIP(hipGetLastError());
+        PA_HIP(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
+        PA_HIP(hipStreamSynchronize(st));
         if (h_err) {
             pa::set_error(h_err & 2 ? "index build: genome-set hash collision detected (refusing to merge sets)"
                                     : "index build: class table overflow (internal error)");
-            cleanup();
             return PA_EINTERNAL;
         }
         idx->n_multi = n_cls;
@@ -1857,18 +1841,15 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
     if (kTableOrdered && idx->n_kmers > 0) {
         if (idx->n_kmers >= cap) {  // (the sizing keeps the load <= 0.7: never)
             pa::set_error("index build: hash table full (internal error)");
-            cleanup();
             return PA_EINTERNAL;
         }
         hipLaunchKernelGGL(k_table_order<NW>, dim3(grid_for(cap) > 65536 ? 65536 : grid_for(cap)), dim3(kBlock), 0, st,
                            table, idx->home);
-        B_HIP(hipGetLastError());
+        PA_HIP(hipGetLastError());
     }
     if (idx->tile_n > 0 && (uint64_t)G + idx->class_entries >= PA_TILE_REP) idx->tile_n = 0;  // ids need bit 31
     idx->tiles_pending = idx->tile_n > 0 ? 1 : 0;  // made by build_tiles_nw (index_prepare)
-#undef B_HIP
-    cleanup();
-    return rc;
+    return PA_OK;
 }
 
 // Step 6, the align-side view of the index (k <= 31, references whose
@@ -1929,10 +1910,10 @@ pa_status build_rcnb(pa_index *idx, hipStream_t st, const uint64_t *bb, uint32_t
 }
 
 // The neighbour-bit build's Bloom filter of the keys (~16 bits per key in HBM,
-// the caller frees it): most of a window's 3k neighbours are absent and share
+// held by the caller's Bufs): most of a window's 3k neighbours are absent and share
 // its Bloom line (minimizer-chosen), so a probe costs an L2 hit instead of a
 // table line.  nullptr when it does not fit (or PA_NB_BLOOM=0).
-pa_status make_nb_bloom(pa_index *idx, hipStream_t st, uint64_t **out, uint32_t *out_lg) {
+pa_status make_nb_bloom(pa_index *idx, hipStream_t st, pa::Bufs &b, uint64_t **out, uint32_t *out_lg) {
     *out = nullptr;
     *out_lg = 6;
     uint64_t *bb = nullptr;
@@ -1943,7 +1924,7 @@ pa_status make_nb_bloom(pa_index *idx, hipStream_t st, uint64_t **out, uint32_t 
     size_t fb = 0, tb = 0;
     if (pa::dev_mem_info(&fb, &tb) != hipSuccess) fb = 0;
     while (bb_lg > 6 && (1ull << bb_lg) * 8 > fb / 4) bb_lg--;
-    if ((1ull << bb_lg) * 64 < idx->n_kmers * 8 || pa::dev_malloc(&bb, (1ull << bb_lg) * 8) != hipSuccess) {
+    if ((1ull << bb_lg) * 64 < idx->n_kmers * 8 || b.get(&bb, (1ull << bb_lg) * 8) != hipSuccess) {
         (void)hipGetLastError();
         return PA_OK;
     }
@@ -1964,7 +1945,7 @@ pa_status build_nb(pa_index *idx, hipStream_t st) {
     const int k = (int)idx->k;
     const uint32_t G = idx->n_genomes;
     Slot<1> *table = (Slot<1> *)idx->table;
-#define B_HIP(call) PA_HIP(call)
+    pa::Bufs b(st);
     // one-substitution neighbours: 24 B per base (present | specific) when
     // that leaves a quarter of the free memory, else 12 B (present only:
     // a present neighbour is then probed), else none; PA_NO_NB=1 skips
@@ -2003,18 +1984,18 @@ pa_status build_nb(pa_index *idx, hipStream_t st) {
                     pa::dev_free(idx->tile_nb1);
                     idx->tile_nb = idx->tile_nb1 = nullptr;
                     idx->nb_split = ~0ull;
-                    B_HIP(pa::dev_malloc(&idx->tile_nb, words * wb + 64));
+                    PA_HIP(pa::dev_malloc(&idx->tile_nb, words * wb + 64));
                 }
             } else if (ea != hipSuccess) {
                 (void)hipGetLastError();
-                B_HIP(pa::dev_malloc(&idx->tile_nb, words * wb + 64));
+                PA_HIP(pa::dev_malloc(&idx->tile_nb, words * wb + 64));
             }
             phase_mark(idx->tile_nb1 ? "nb: alloc (two pieces)" : "nb: alloc");
             if (idx->tile_nb1) {
-                B_HIP(hipMemsetAsync(idx->tile_nb, 0, idx->nb_split * wb + 64, st));
-                B_HIP(hipMemsetAsync(idx->tile_nb1, 0, (words - idx->nb_split) * wb + 64, st));
+                PA_HIP(hipMemsetAsync(idx->tile_nb, 0, idx->nb_split * wb + 64, st));
+                PA_HIP(hipMemsetAsync(idx->tile_nb1, 0, (words - idx->nb_split) * wb + 64, st));
             } else {
-                B_HIP(hipMemsetAsync(idx->tile_nb, 0, words * wb + 64, st));
+                PA_HIP(hipMemsetAsync(idx->tile_nb, 0, words * wb + 64, st));
             }
             phase_mark("nb: clear");
             const NbW nbw = nb_words(idx, wb);
@@ -2025,7 +2006,7 @@ pa_status build_nb(pa_index *idx, hipStream_t st) {
             // PA_NB_BLOOM=0 turns it off (A/B)
             uint64_t *bb = nullptr;
             uint32_t bb_lg = 6;
-            PA_TRY(make_nb_bloom(idx, st, &bb, &bb_lg));
+            PA_TRY(make_nb_bloom(idx, st, b, &bb, &bb_lg));
             phase_mark("nb: build Bloom");
             for (int pass = 0; pass < 2; pass++) {
                 if (pass == 0 && kNbFirstOrder)
@@ -2057,15 +2038,11 @@ pa_status build_nb(pa_index *idx, hipStream_t st) {
                 else
                     idx->rcnb_pending = 1;
             }
-            if (bb) {
-                B_HIP(hipStreamSynchronize(st));
-                pa::dev_free(bb);
-            }
+            PA_HIP(b.free(bb));
             idx->nb_spec = full ? 1 : 0;
             idx->device_bytes += n * 3 * wb;
         }
     }
-#undef B_HIP
     idx->nb_pending = 0;
     return PA_OK;
 }
@@ -2081,6 +2058,7 @@ pa_status build_nb2(pa_index *idx, hipStream_t st) {
     if (!(no_nb && no_nb[0] == '1') && pa::dev_mem_info(&free_b, &total_b) == hipSuccess && n * 24 <= free_b / 4 * 3) {
         PA_HIP(pa::dev_malloc(&idx->tile_nb, n * 24 + 64));
         PA_HIP(hipMemsetAsync(idx->tile_nb, 0, n * 24 + 64, st));
+        pa::Bufs b(st);
         uint64_t *bb = nullptr;  // the build-time Bloom filter, 16 bits per key (freed below)
         uint32_t bb_lg = 6;
         if (idx->n_kmers > 0) {
@@ -2088,7 +2066,7 @@ pa_status build_nb2(pa_index *idx, hipStream_t st) {
             size_t fb = 0, tb = 0;
             if (pa::dev_mem_info(&fb, &tb) != hipSuccess) fb = 0;
             while (bb_lg > 6 && (1ull << bb_lg) * 8 > fb / 4) bb_lg--;
-            if ((1ull << bb_lg) * 64 >= idx->n_kmers * 8 && pa::dev_malloc(&bb, (1ull << bb_lg) * 8) == hipSuccess) {
+            if ((1ull << bb_lg) * 64 >= idx->n_kmers * 8 && b.get(&bb, (1ull << bb_lg) * 8) == hipSuccess) {
                 PA_HIP(hipMemsetAsync(bb, 0, (1ull << bb_lg) * 8, st));
                 hipLaunchKernelGGL(k_bloom_build2<2>, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
                                    dim3(kBlock), 0, st, (const Slot<2> *)idx->table, idx->cap, bb, bb_lg);
@@ -2102,10 +2080,7 @@ pa_status build_nb2(pa_index *idx, hipStream_t st) {
                                idx->n_genomes, (unsigned long long *)idx->tile_nb, idx->class_genomes, idx->goff,
                                idx->tpos_local, pass, bb, bb_lg);
         PA_HIP(hipGetLastError());
-        if (bb) {
-            PA_HIP(hipStreamSynchronize(st));
-            pa::dev_free(bb);
-        }
+        PA_HIP(b.free(bb));
         idx->nb_spec = 0;
         idx->device_bytes += n * 24;
         phase_mark("nb: two-word keys");
@@ -2123,6 +2098,7 @@ pa_status build_nb3(pa_index *idx, hipStream_t st) {
     if (!(no_nb && no_nb[0] == '1') && pa::dev_mem_info(&free_b, &total_b) == hipSuccess && bytes <= free_b / 4) {
         PA_HIP(pa::dev_malloc(&idx->tile_nb, bytes));
         PA_HIP(hipMemsetAsync(idx->tile_nb, 0, bytes, st));
+        pa::Bufs b(st);
         uint64_t *bb = nullptr;  // the build-time Bloom filter, 16 bits per key (freed below)
         uint32_t bb_lg = 6;
         if (idx->n_kmers > 0) {
@@ -2130,7 +2106,7 @@ pa_status build_nb3(pa_index *idx, hipStream_t st) {
             size_t fb = 0, tb = 0;
             if (pa::dev_mem_info(&fb, &tb) != hipSuccess) fb = 0;
             while (bb_lg > 6 && (1ull << bb_lg) * 8 > fb / 4) bb_lg--;
-            if ((1ull << bb_lg) * 64 >= idx->n_kmers * 8 && pa::dev_malloc(&bb, (1ull << bb_lg) * 8) == hipSuccess) {
+            if ((1ull << bb_lg) * 64 >= idx->n_kmers * 8 && b.get(&bb, (1ull << bb_lg) * 8) == hipSuccess) {
                 PA_HIP(hipMemsetAsync(bb, 0, (1ull << bb_lg) * 8, st));
                 hipLaunchKernelGGL(k_bloom_build2<3>, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
                                    dim3(kBlock), 0, st, (const Slot<3> *)idx->table, idx->cap, bb, bb_lg);
@@ -2142,10 +2118,7 @@ pa_status build_nb3(pa_index *idx, hipStream_t st) {
                            idx->tile_pk, idx->tile_cls, n, (int)idx->k, (const Slot<3> *)idx->table, idx->home,
                            (uint32_t *)idx->tile_nb, bb, bb_lg);
         PA_HIP(hipGetLastError());
-        if (bb) {
-            PA_HIP(hipStreamSynchronize(st));
-            pa::dev_free(bb);
-        }
+        PA_HIP(b.free(bb));
         idx->nb_spec = 0;
         idx->device_bytes += bytes;
         phase_mark("nb: three-word summaries");
@@ -2161,16 +2134,15 @@ pa_status build_tiles_nw(pa_index *idx, hipStream_t st) {
     const int wpt = build_run();
     const uint64_t mask0 = (2 * k - 64 * (NW - 1)) >= 64 ? ~0ull : ((1ull << (2 * k - 64 * (NW - 1))) - 1);
     Slot<NW> *table = (Slot<NW> *)idx->table;
-#define B_HIP(call) PA_HIP(call)
     if (idx->tile_n > 0) {  // tiles: 6.5 B per base (class, flags, set sizes, 2-bit string), + margin
         size_t free_b = 0, total_b = 0;
         if (pa::dev_mem_info(&free_b, &total_b) != hipSuccess || idx->tile_n * 7 + (2ull << 30) > free_b) idx->tile_n = 0;
     }
     if (idx->tile_n > 0) {  // step 6: genome tiling
         const uint64_t n = idx->tile_n, nwords = n / 32 + 32;  // padded: the walk reads up to 18 words past a position
-        B_HIP(pa::dev_malloc(&idx->tile_cls, n * 4));
-        B_HIP(pa::dev_malloc(&idx->tile_pk, nwords * 8));
-        B_HIP(hipMemsetAsync(idx->tile_cls, 0xFF, n * 4, st));
+        PA_HIP(pa::dev_malloc(&idx->tile_cls, n * 4));
+        PA_HIP(pa::dev_malloc(&idx->tile_pk, nwords * 8));
+        PA_HIP(hipMemsetAsync(idx->tile_cls, 0xFF, n * 4, st));
         hipLaunchKernelGGL(k_tile_pack, dim3(grid_for(nwords) > 65536 ? 65536 : grid_for(nwords)), dim3(kBlock), 0, st,
                            idx->codes, n, idx->tile_pk, nwords);
         {  // every genome's chunks in one launch (k_tile_cls_all)
@@ -2179,18 +2151,16 @@ pa_status build_tiles_nw(pa_index *idx, hipStream_t st) {
                 const uint64_t len = idx->h_goff[g + 1] - idx->h_goff[g];
                 ts[g + 1] = ts[g] + ((uint64_t)k > len ? 0 : (len - k + 1 + wpt - 1) / wpt);
             }
+            pa::Bufs b(st);
             uint64_t *d_ts = nullptr;
-            B_HIP(pa::dev_malloc(&d_ts, (G + 1) * 8));
-            hipError_t e = hipMemcpyAsync(d_ts, ts.data(), (G + 1) * 8, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess && ts[G] > 0) {
+            PA_HIP(b.get(&d_ts, (G + 1) * 8));
+            PA_HIP(hipMemcpyAsync(d_ts, ts.data(), (G + 1) * 8, hipMemcpyHostToDevice, st));
+            if (ts[G] > 0) {
                 hipLaunchKernelGGL(k_tile_cls_all<NW>, dim3(grid_for(ts[G])), dim3(kBlock), 0, st, idx->codes, idx->goff,
                                    d_ts, G, k, mask0, table, idx->home, idx->tile_cls, idx->class_genomes,
                                    idx->tpos_local, wpt);
-                e = hipGetLastError();
+                PA_HIP(hipGetLastError());
             }
-            if (e == hipSuccess) e = hipStreamSynchronize(st);  // (d_ts is freed below)
-            pa::dev_free(d_ts);
-            B_HIP(e);
         }
         phase_mark("tile classes");
         // below 2^33 bases: first occurrences as 33-bit concatenated positions
@@ -2199,7 +2169,7 @@ pa_status build_tiles_nw(pa_index *idx, hipStream_t st) {
         if (idx->tpos_local && idx->h_goff[G] < (1ull << 33) && !(thi && thi[0] == '0')) {
             hipLaunchKernelGGL(k_tpos_concat<NW>, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
                                dim3(kBlock), 0, st, table, idx->cap, G, idx->class_genomes, idx->goff);
-            B_HIP(hipGetLastError());
+            PA_HIP(hipGetLastError());
             idx->tpos_local = 0;
             phase_mark("first occurrences concatenated");
         }
@@ -2213,9 +2183,9 @@ pa_status build_tiles_nw(pa_index *idx, hipStream_t st) {
                 g = g == 0 ? 0 : g - 1;
                 gb[j] = g >= G ? G - 1 : g;
             }
-            B_HIP(pa::dev_malloc(&idx->tile_gblk, nb_ * 4));
-            B_HIP(hipMemcpyAsync(idx->tile_gblk, gb.data(), nb_ * 4, hipMemcpyHostToDevice, st));
-            B_HIP(hipStreamSynchronize(st));
+            PA_HIP(pa::dev_malloc(&idx->tile_gblk, nb_ * 4));
+            PA_HIP(hipMemcpyAsync(idx->tile_gblk, gb.data(), nb_ * 4, hipMemcpyHostToDevice, st));
+            PA_HIP(hipStreamSynchronize(st));
             idx->device_bytes += nb_ * 4;
         }
         // the lane kernels' view: keys of one word (k <= 31) or two (k <= 63)
@@ -2225,7 +2195,7 @@ pa_status build_tiles_nw(pa_index *idx, hipStream_t st) {
                                dim3(256), 0, st, idx->tile_pk, idx->tile_cls, n, k);
         if (lane_view) {
             const uint64_t n_blocks = n / 64 + 8;  // padded: the 250-bp walk reads six blocks from any position
-            B_HIP(pa::dev_malloc(&idx->tile_lw, n_blocks * 32));
+            PA_HIP(pa::dev_malloc(&idx->tile_lw, n_blocks * 32));
             hipLaunchKernelGGL(k_tile_walk, dim3((unsigned)std::min<uint64_t>((n_blocks + 3) / 4, 1u << 20)), dim3(256),
                                0, st, idx->tile_cls, idx->tile_pk, n, G, idx->tile_lw, n_blocks);
             idx->device_bytes += n_blocks * 32;
@@ -2269,8 +2239,8 @@ pa_status build_tiles_nw(pa_index *idx, hipStream_t st) {
                     }
                 }
                 if (ok) {
-                    B_HIP(pa::dev_malloc(&idx->bloom, (1ull << lg) * 8));
-                    B_HIP(hipMemsetAsync(idx->bloom, 0, (1ull << lg) * 8, st));
+                    PA_HIP(pa::dev_malloc(&idx->bloom, (1ull << lg) * 8));
+                    PA_HIP(hipMemsetAsync(idx->bloom, 0, (1ull << lg) * 8, st));
                     if (NW == 1)
                         hipLaunchKernelGGL(k_bloom_build<false>, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
                                            dim3(kBlock), 0, st, (const Slot<1> *)table, idx->cap, idx->bloom, lg, k);
@@ -2294,7 +2264,7 @@ pa_status build_tiles_nw(pa_index *idx, hipStream_t st) {
                 const uint32_t lg = 25;
                 if (NW == 1 && !(nm && nm[0] == '1') && idx->bloom && idx->n_kmers / 9 <= (1ull << lg) / 4 &&
                     pa::dev_malloc(&idx->mm_bits, (1ull << lg) / 8) == hipSuccess) {
-                    B_HIP(hipMemsetAsync(idx->mm_bits, 0, (1ull << lg) / 8, st));
+                    PA_HIP(hipMemsetAsync(idx->mm_bits, 0, (1ull << lg) / 8, st));
                     hipLaunchKernelGGL(k_mm_build, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
                                        dim3(kBlock), 0, st, (const Slot<1> *)table, idx->cap, idx->mm_bits, lg, k);
                     idx->mm_lg = lg;
@@ -2318,11 +2288,10 @@ pa_status build_tiles_nw(pa_index *idx, hipStream_t st) {
                 phase_mark("reverse-complement plane");
             }
         }
-        B_HIP(hipGetLastError());
-        B_HIP(hipStreamSynchronize(st));
+        PA_HIP(hipGetLastError());
+        PA_HIP(hipStreamSynchronize(st));
         idx->device_bytes += n * 4 + nwords * 8;
     }
-#undef B_HIP
     return PA_OK;
 }
 
@@ -2431,15 +2400,11 @@ pa_status index_build_rcnb(pa_index *idx, hipStream_t st) {
     std::unique_ptr<PhaseTimer> own;
     if (!t_phase) own.reset(new PhaseTimer(st));
     PhaseScope ps(t_phase ? t_phase : own.get());
+    Bufs b(st);
     uint64_t *bb = nullptr;
     uint32_t bb_lg = 6;
-    PA_TRY(make_nb_bloom(idx, st, &bb, &bb_lg));
-    const pa_status rc = build_rcnb(idx, st, bb, bb_lg);
-    if (bb) {
-        PA_HIP(hipStreamSynchronize(st));
-        pa::dev_free(bb);
-    }
-    return rc;
+    PA_TRY(make_nb_bloom(idx, st, b, &bb, &bb_lg));
+    return build_rcnb(idx, st, bb, bb_lg);
 }
 
 pa_status index_note_reads(pa_index *idx, uint64_t n, hipStream_t st) {
@@ -2557,25 +2522,20 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
         uint8_t *ascii = nullptr;
         uint64_t *d_fgoff = nullptr;
         unsigned long long *bad = nullptr, h_bad = ~0ull;
-        PA_HIP(pa::dev_malloc(&ascii, fwd_total + kExpandPad));
-        PA_HIP(pa::dev_malloc(&d_fgoff, (n + 1) * 8));
-        PA_HIP(pa::dev_malloc(&bad, 8));
+        Bufs b(st);  // (the staging buffers go before the table is allocated)
+        PA_HIP(b.get(&ascii, fwd_total + kExpandPad));
+        PA_HIP(b.get(&d_fgoff, (n + 1) * 8));
+        PA_HIP(b.get(&bad, 8));
         tm.mark("alloc");
-        hipError_t e = hipMemsetAsync(bad, 0xFF, 8, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_fgoff, fwd_goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(ascii, genomes + text_off, fwd_total, hipMemcpyHostToDevice, st);
+        PA_HIP(hipMemsetAsync(bad, 0xFF, 8, st));
+        PA_HIP(hipMemcpyAsync(d_fgoff, fwd_goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+        PA_HIP(hipMemcpyAsync(ascii, genomes + text_off, fwd_total, hipMemcpyHostToDevice, st));
         tm.mark("upload");
-        if (e == hipSuccess) {
-            const unsigned grid = grid_for((total + kExpandRun - 1) / kExpandRun);
-            hipLaunchKernelGGL(k_encode_strands, dim3(grid > 65536 ? 65536 : grid), dim3(kBlock), 0, st, ascii, d_fgoff,
-                               idx->goff, n, idx->codes, bad);
-            e = hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, st);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        pa::dev_free(ascii);
-        pa::dev_free(d_fgoff);
-        pa::dev_free(bad);
-        PA_HIP(e);
+        const unsigned grid = grid_for((total + kExpandRun - 1) / kExpandRun);
+        hipLaunchKernelGGL(k_encode_strands, dim3(grid > 65536 ? 65536 : grid), dim3(kBlock), 0, st, ascii, d_fgoff,
+                           idx->goff, n, idx->codes, bad);
+        PA_HIP(hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, st));
+        PA_HIP(hipStreamSynchronize(st));
         if (h_bad != ~0ull) {
             set_error("genome text may only contain A, C, G, T and N (byte " + std::to_string(h_bad) + ")");
             return PA_EINVAL;
@@ -2583,21 +2543,17 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
     } else if (total > 0 && !dev_codes) {
         uint8_t *ascii = nullptr;  // ASCII staging buffer, freed before the table is allocated
         unsigned long long *bad = nullptr, h_bad = ~0ull;
-        PA_HIP(pa::dev_malloc(&ascii, total));
-        PA_HIP(pa::dev_malloc(&bad, 8));
+        Bufs b(st);
+        PA_HIP(b.get(&ascii, total));
+        PA_HIP(b.get(&bad, 8));
         tm.mark("alloc");
-        hipError_t e = hipMemsetAsync(bad, 0xFF, 8, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(ascii, genomes + goff[0], total, hipMemcpyHostToDevice, st);
+        PA_HIP(hipMemsetAsync(bad, 0xFF, 8, st));
+        PA_HIP(hipMemcpyAsync(ascii, genomes + goff[0], total, hipMemcpyHostToDevice, st));
         tm.mark("upload");
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_encode, dim3(grid_for(total) > 65536 ? 65536 : grid_for(total)), dim3(kBlock), 0, st,
-                               ascii, idx->codes, total, bad);
-            e = hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, st);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        pa::dev_free(ascii);
-        pa::dev_free(bad);
-        PA_HIP(e);
+        hipLaunchKernelGGL(k_encode, dim3(grid_for(total) > 65536 ? 65536 : grid_for(total)), dim3(kBlock), 0, st,
+                           ascii, idx->codes, total, bad);
+        PA_HIP(hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, st));
+        PA_HIP(hipStreamSynchronize(st));
         if (h_bad != ~0ull) {
             set_error("genome text may only contain A, C, G, T and N (byte " + std::to_string(h_bad) + ")");
             return PA_EINVAL;
@@ -2636,8 +2592,9 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
     }
     if (idx->force_large) cap = 0, free_b = (size_t)0;
     if (cap == 0 && k > 0 && windows > 0) {
+        Bufs b(st);
         uint32_t *reg = nullptr;
-        PA_HIP(pa::dev_malloc(&reg, (4ull << kHllBits)));
+        PA_HIP(b.get(&reg, (4ull << kHllBits)));
         PA_HIP(hipMemsetAsync(reg, 0, (4ull << kHllBits), st));
         const uint64_t mask0 = (2 * k - 64 * (idx->nw - 1)) >= 64 ? ~0ull : ((1ull << (2 * k - 64 * (idx->nw - 1))) - 1);
         for (uint32_t g = 0; g < n; g++) {
@@ -2645,22 +2602,15 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
             if ((uint64_t)k > len) continue;
             const uint64_t nwin = len - k + 1;
             const dim3 grid(grid_for((nwin + kRun - 1) / kRun));
-            switch (idx->nw) {
-                case 1: hipLaunchKernelGGL(k_hll<1>, grid, dim3(kBlock), 0, st, idx->codes, idx->h_goff[g], nwin, (int)k, mask0, reg); break;
-                case 2: hipLaunchKernelGGL(k_hll<2>, grid, dim3(kBlock), 0, st, idx->codes, idx->h_goff[g], nwin, (int)k, mask0, reg); break;
-                case 3: hipLaunchKernelGGL(k_hll<3>, grid, dim3(kBlock), 0, st, idx->codes, idx->h_goff[g], nwin, (int)k, mask0, reg); break;
-                case 4: hipLaunchKernelGGL(k_hll<4>, grid, dim3(kBlock), 0, st, idx->codes, idx->h_goff[g], nwin, (int)k, mask0, reg); break;
-                case 5: hipLaunchKernelGGL(k_hll<5>, grid, dim3(kBlock), 0, st, idx->codes, idx->h_goff[g], nwin, (int)k, mask0, reg); break;
-                case 6: hipLaunchKernelGGL(k_hll<6>, grid, dim3(kBlock), 0, st, idx->codes, idx->h_goff[g], nwin, (int)k, mask0, reg); break;
-                case 7: hipLaunchKernelGGL(k_hll<7>, grid, dim3(kBlock), 0, st, idx->codes, idx->h_goff[g], nwin, (int)k, mask0, reg); break;
-                default: hipLaunchKernelGGL(k_hll<8>, grid, dim3(kBlock), 0, st, idx->codes, idx->h_goff[g], nwin, (int)k, mask0, reg); break;
-            }
+            with_nw(idx->nw, [&](auto w) {
+                hipLaunchKernelGGL(k_hll<w()>, grid, dim3(kBlock), 0, st, idx->codes, idx->h_goff[g], nwin, (int)k, mask0,
+                                   reg);
+            });
         }
         std::vector<uint32_t> h(1u << kHllBits);
-        hipError_t e = hipMemcpyAsync(h.data(), reg, (4ull << kHllBits), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        pa::dev_free(reg);
-        PA_HIP(e);
+        PA_HIP(hipMemcpyAsync(h.data(), reg, (4ull << kHllBits), hipMemcpyDeviceToHost, st));
+        PA_HIP(hipStreamSynchronize(st));
+        b.free(reg);
         const double mm = (double)(1u << kHllBits);
         double z = 0;
         uint32_t zeros = 0;
@@ -2710,17 +2660,10 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
     tm.mark("table");
     if (k <= 0 || windows == 0) return PA_OK;
     pa_status rc = PA_EUNSUPPORTED;
-    switch (idx->nw) {
-        case 1: rc = build_nw<1>(idx, st); break;
-        case 2: rc = build_nw<2>(idx, st); break;
-        case 3: rc = build_nw<3>(idx, st); break;
-        case 4: rc = build_nw<4>(idx, st); break;
-        case 5: rc = build_nw<5>(idx, st); break;
-        case 6: rc = build_nw<6>(idx, st); break;
-        case 7: rc = build_nw<7>(idx, st); break;
-        case 8: rc = build_nw<8>(idx, st); break;
-        default: set_error("unsupported k");
-    }
+    if (idx->nw >= 1 && idx->nw <= 8)
+        rc = with_nw(idx->nw, [&](auto w) { return build_nw<w()>(idx, st); });
+    else
+        set_error("unsupported k");
     tm.mark("insert + sets");
     if (rc != PA_OK || defer_tiles) return rc;
     rc = index_prepare(idx, st);
@@ -2853,30 +2796,16 @@ pa_status index_lookup(const pa_index *idx, const char *kmers, uint64_t n, uint3
     uint8_t *d_k = nullptr;
     int64_t *d_c = nullptr;
     uint32_t *d_s = nullptr;
-    PA_HIP(pa::dev_malloc(&d_k, n * kmer_len));
-    PA_HIP(pa::dev_malloc(&d_c, n * 8));
-    PA_HIP(pa::dev_malloc(&d_s, n * 4));
+    Bufs b(st);
+    PA_HIP(b.get(&d_k, n * kmer_len));
+    PA_HIP(b.get(&d_c, n * 8));
+    PA_HIP(b.get(&d_s, n * 4));
     PA_HIP(hipMemcpyAsync(d_k, kmers, n * kmer_len, hipMemcpyHostToDevice, st));
-    pa_status rc = PA_OK;
-    switch (idx->nw) {
-        case 1: rc = lookup_nw<1>(idx, d_k, n, d_c, d_s, st); break;
-        case 2: rc = lookup_nw<2>(idx, d_k, n, d_c, d_s, st); break;
-        case 3: rc = lookup_nw<3>(idx, d_k, n, d_c, d_s, st); break;
-        case 4: rc = lookup_nw<4>(idx, d_k, n, d_c, d_s, st); break;
-        case 5: rc = lookup_nw<5>(idx, d_k, n, d_c, d_s, st); break;
-        case 6: rc = lookup_nw<6>(idx, d_k, n, d_c, d_s, st); break;
-        case 7: rc = lookup_nw<7>(idx, d_k, n, d_c, d_s, st); break;
-        default: rc = lookup_nw<8>(idx, d_k, n, d_c, d_s, st); break;
-    }
-    if (rc == PA_OK) {
-        PA_HIP(hipMemcpyAsync(cls_out, d_c, n * 8, hipMemcpyDeviceToHost, st));
-        if (size_out) PA_HIP(hipMemcpyAsync(size_out, d_s, n * 4, hipMemcpyDeviceToHost, st));
-        PA_HIP(hipStreamSynchronize(st));
-    }
-    pa::dev_free(d_k);
-    pa::dev_free(d_c);
-    pa::dev_free(d_s);
-    return rc;
+    PA_TRY(with_nw(idx->nw, [&](auto w) { return lookup_nw<w()>(idx, d_k, n, d_c, d_s, st); }));
+    PA_HIP(hipMemcpyAsync(cls_out, d_c, n * 8, hipMemcpyDeviceToHost, st));
+    if (size_out) PA_HIP(hipMemcpyAsync(size_out, d_s, n * 4, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
+    return PA_OK;
 }
 
 pa_status index_extsim_stats(const pa_index *idx, const uint32_t *group_of, uint32_t n_groups, uint64_t *total,
@@ -2890,27 +2819,19 @@ pa_status index_extsim_stats(const pa_index *idx, const uint32_t *group_of, uint
     const uint64_t nm = std::max<uint64_t>(idx->n_multi, 1);
     const uint64_t n_rec = std::max<uint64_t>(idx->class_entries, 1);
     const unsigned cgrid = (unsigned)std::min<uint64_t>(nm, 1024);
-    PA_HIP(pa::dev_malloc(&d_group, (uint64_t)idx->n_genomes * 4));
-    PA_HIP(pa::dev_malloc(&d_tot, n_groups * 8));
-    PA_HIP(pa::dev_malloc(&d_uniq, n_groups * 8));
-    PA_HIP(pa::dev_malloc(&d_inter, ng2 * 8));
-    PA_HIP(pa::dev_malloc(&d_cc, n_rec * 8));
-    PA_HIP(pa::dev_malloc(&scratch, (uint64_t)cgrid * (idx->n_genomes + 1) * 4));
+    Bufs b(st);
+    PA_HIP(b.get(&d_group, (uint64_t)idx->n_genomes * 4));
+    PA_HIP(b.get(&d_tot, n_groups * 8));
+    PA_HIP(b.get(&d_uniq, n_groups * 8));
+    PA_HIP(b.get(&d_inter, ng2 * 8));
+    PA_HIP(b.get(&d_cc, n_rec * 8));
+    PA_HIP(b.get(&scratch, (uint64_t)cgrid * (idx->n_genomes + 1) * 4));
     PA_HIP(hipMemcpyAsync(d_group, group_of, (uint64_t)idx->n_genomes * 4, hipMemcpyHostToDevice, st));
     PA_HIP(hipMemsetAsync(d_tot, 0, n_groups * 8, st));
     PA_HIP(hipMemsetAsync(d_uniq, 0, n_groups * 8, st));
     PA_HIP(hipMemsetAsync(d_inter, 0, ng2 * 8, st));
     PA_HIP(hipMemsetAsync(d_cc, 0, n_rec * 8, st));
-    switch (idx->nw) {
-        case 1: extsim_slots_nw<1>(idx, d_group, n_groups, d_tot, d_uniq, d_cc, st); break;
-        case 2: extsim_slots_nw<2>(idx, d_group, n_groups, d_tot, d_uniq, d_cc, st); break;
-        case 3: extsim_slots_nw<3>(idx, d_group, n_groups, d_tot, d_uniq, d_cc, st); break;
-        case 4: extsim_slots_nw<4>(idx, d_group, n_groups, d_tot, d_uniq, d_cc, st); break;
-        case 5: extsim_slots_nw<5>(idx, d_group, n_groups, d_tot, d_uniq, d_cc, st); break;
-        case 6: extsim_slots_nw<6>(idx, d_group, n_groups, d_tot, d_uniq, d_cc, st); break;
-        case 7: extsim_slots_nw<7>(idx, d_group, n_groups, d_tot, d_uniq, d_cc, st); break;
-        default: extsim_slots_nw<8>(idx, d_group, n_groups, d_tot, d_uniq, d_cc, st); break;
-    }
+    with_nw(idx->nw, [&](auto w) { extsim_slots_nw<w()>(idx, d_group, n_groups, d_tot, d_uniq, d_cc, st); });
     if (idx->n_multi > 0)
         hipLaunchKernelGGL(k_extsim_classes, dim3(cgrid), dim3(kBlock), 0, st, idx->n_multi, idx->class_off,
                            idx->class_size, idx->class_genomes, d_group, n_groups, d_cc, d_tot, d_inter, scratch,
@@ -2920,15 +2841,15 @@ pa_status index_extsim_stats(const pa_index *idx, const uint32_t *group_of, uint
     PA_HIP(hipMemcpyAsync(uniq, d_uniq, n_groups * 8, hipMemcpyDeviceToHost, st));
     PA_HIP(hipMemcpyAsync(inter, d_inter, ng2 * 8, hipMemcpyDeviceToHost, st));
     PA_HIP(hipStreamSynchronize(st));
-    pa::dev_free(d_group); pa::dev_free(d_tot); pa::dev_free(d_uniq); pa::dev_free(d_inter); pa::dev_free(d_cc); pa::dev_free(scratch);
     return PA_OK;
 }
 
 pa_status reads_synthesize(const pa_index *idx, pa_reads *r, uint64_t n, uint32_t len, uint64_t first,
                            uint64_t seed, double sub_rate, double rc_rate, double foreign_rate, hipStream_t st) {
     std::vector<uint32_t> elig;
+    const std::vector<uint64_t> flen = forward_lengths(idx);
     for (uint32_t g = 0; g < idx->n_genomes; g++)
-        if ((idx->both_strands ? idx->h_fwd_len[g] : idx->h_goff[g + 1] - idx->h_goff[g]) >= len) elig.push_back(g);
+        if (flen[g] >= len) elig.push_back(g);
     if (elig.empty()) {
         set_error("pa_reads_synthesize: no genome is at least read_len long");
         return PA_EINVAL;
@@ -2937,11 +2858,12 @@ pa_status reads_synthesize(const pa_index *idx, pa_reads *r, uint64_t n, uint32_
     r->n = n;
     r->n_bases = n * len;
     r->max_len = len;
+    Bufs b(st);
     uint32_t *d_elig = nullptr;
-    PA_HIP(pa::dev_malloc(&r->seq, r->n_bases + kReadPad));
+    PA_HIP(pa::dev_malloc(&r->seq, r->n_bases + kReadPad));  // (r's: the caller frees them with it)
     PA_HIP(pa::dev_malloc(&r->qual, r->n_bases + kReadPad));
     PA_HIP(pa::dev_malloc(&r->off, (n + 1) * 8));
-    PA_HIP(pa::dev_malloc(&d_elig, elig.size() * 4));
+    PA_HIP(b.get(&d_elig, elig.size() * 4));
     PA_HIP(hipMemcpyAsync(d_elig, elig.data(), elig.size() * 4, hipMemcpyHostToDevice, st));
     if (n == 0 || len == 0) {
         PA_HIP(hipMemsetAsync(r->off, 0, (n + 1) * 8, st));
@@ -2956,7 +2878,6 @@ pa_status reads_synthesize(const pa_index *idx, pa_reads *r, uint64_t n, uint32_
     }
     PA_HIP(hipGetLastError());
     PA_HIP(hipStreamSynchronize(st));
-    pa::dev_free(d_elig);
     return PA_OK;
 }
 

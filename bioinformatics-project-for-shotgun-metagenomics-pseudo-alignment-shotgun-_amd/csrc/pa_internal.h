@@ -5,7 +5,9 @@
 #include <stdint.h>
 
 #include <map>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pa.h"
@@ -16,15 +18,29 @@ namespace pa {
 // Last error, thread-local; set by the PA_* macros below.
 void set_error(const std::string &msg);
 
+// The one HIP-error path: the message holds the operation's name (ErrOp, when
+// one is set), HIP's text, file:line and the call; the sticky error is cleared;
+// a failed device allocation is PA_ENOMEM, everything else PA_EDEVICE.  Device
+// scratch is held by scoped owners (Bufs below), so no cleanup runs here.
+pa_status hip_failed(hipError_t e, const char *where);
+#define PA_STR2(x) #x
+#define PA_STR(x) PA_STR2(x)
 #define PA_HIP(call)                                                                              \
     do {                                                                                          \
         hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            ::pa::set_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " __FILE__ ":" + \
-                            std::to_string(__LINE__) + " (" #call ")");                          \
-            return PA_EDEVICE;                                                                    \
-        }                                                                                         \
+        if (e_ != hipSuccess) return ::pa::hip_failed(e_, __FILE__ ":" PA_STR(__LINE__) " (" #call ")"); \
     } while (0)
+
+// The entry point a thread is in, for the messages of the code below it
+// ("pa_pileup_add: HIP error: ..."); nests, the innermost name is used.
+struct ErrOp {
+    const char *prev;
+    explicit ErrOp(const char *name);
+    ~ErrOp();
+    ErrOp(const ErrOp &) = delete;
+    ErrOp &operator=(const ErrOp &) = delete;
+};
+const char *err_op();  // the name in force ("": none), for messages written by hand
 
 #define PA_TRY(call)                         \
     do {                                     \
@@ -71,6 +87,91 @@ struct Workspace {  // grow-only device scratch owned by an index
     void *ptr = nullptr;
     size_t bytes = 0;
 };
+
+// Device buffers of one call, bound to its stream: every return frees them,
+// after one wait for the stream (queued work may still touch them).  The
+// ownership rule of the host code: a buffer taken
+// during a call belongs to a Bufs until the call succeeds and release() hands
+// it to the index or accumulator that keeps it.
+struct Bufs {
+    hipStream_t st;
+    std::vector<void *> p;
+    explicit Bufs(hipStream_t s) : st(s) {}
+    Bufs(const Bufs &) = delete;
+    Bufs &operator=(const Bufs &) = delete;
+    ~Bufs() {
+        if (p.empty()) return;
+        (void)hipStreamSynchronize(st);
+        for (size_t i = p.size(); i-- > 0;) dev_free(p[i]);  // newest first
+    }
+    template <typename T>
+    hipError_t get(T **out, uint64_t bytes) {
+        *out = nullptr;
+        const hipError_t e = dev_malloc(out, bytes < 16 ? 16 : bytes);
+        if (e == hipSuccess) p.push_back((void *)*out);
+        return e;
+    }
+    // A buffer taken elsewhere (dev_malloc_try, an optional allocation): the holder's from now on.
+    void adopt(void *q) {
+        if (q) p.push_back(q);
+    }
+    // Out of the holder, still allocated: the caller (an index, an accumulator) owns it now.
+    template <typename T>
+    T *release(T *q) {
+        drop((const void *)q);
+        return q;
+    }
+    // A large temporary that must go before the next allocation: freed now
+    // (after the stream is done with it; the wait's status is returned), the
+    // caller's pointer cleared.
+    template <typename T>
+    hipError_t free(T *&q) {
+        hipError_t e = hipSuccess;
+        if (q && drop((const void *)q)) {
+            e = hipStreamSynchronize(st);
+            dev_free((void *)q);
+        }
+        q = nullptr;
+        return e;
+    }
+
+   private:
+    bool drop(const void *q) {
+        for (size_t i = p.size(); i-- > 0;)
+            if (p[i] == q) {
+                p.erase(p.begin() + (long)i);
+                return true;
+            }
+        return false;
+    }
+};
+
+// A rocPRIM call's size query, temporary storage (held by b) and run:
+//   PA_HIP(with_temp(b, [&](void *tmp, size_t &bytes) { return rocprim::...(tmp, bytes, ...); }));
+template <typename F>
+inline hipError_t with_temp(Bufs &b, F &&f) {
+    size_t bytes = 0;
+    void *tmp = nullptr;
+    hipError_t e = f(nullptr, bytes);
+    if (e == hipSuccess) e = b.get(&tmp, bytes);
+    if (e == hipSuccess) e = f(tmp, bytes);
+    return e;
+}
+
+// A run-time value as a compile-time constant: f(int_c<N>{}) for the first N
+// of the list that equals n, else for the last one; every call returns the
+// same type, and a value the list does not hold is not instantiated.
+template <int N> using int_c = std::integral_constant<int, N>;
+template <int N0, int... Ns, class F>
+auto with_int(int n, F &&f) {
+    if constexpr (sizeof...(Ns) == 0) return f(int_c<N0>{});
+    else return n == N0 ? f(int_c<N0>{}) : with_int<Ns...>(n, f);
+}
+// ... over the key widths of an index (PA_MAX_K bounds nw at 8)
+template <class F>
+auto with_nw(int nw, F &&f) {
+    return with_int<1, 2, 3, 4, 5, 6, 7, 8>(nw, f);
+}
 
 }  // namespace pa
 
@@ -196,14 +297,38 @@ struct pa_idset {  // id hashes of a FASTQ byte range (pa_align_fastq_range)
     std::vector<uint64_t> h;
 };
 
-// Depth accumulator of one index (pa_cover.hip): difference arrays in forward
-// genome coordinates, |g| + 1 entries per genome and category (genome g's at
-// foff[g] + g), the ambiguous category after the unique one.
-struct pa_coverage {
+namespace pa {
+// What every accumulator of one index starts with.
+struct AccBase {
     int device = 0;
     const pa_index *idx = nullptr;     // the index it was made for, at
     uint64_t epoch = 0;                //   this build of it
     uint32_t n_genomes = 0;
+};
+inline void acc_bind(AccBase &a, const pa_index *idx) {
+    a.device = idx->device, a.idx = idx, a.epoch = idx->epoch, a.n_genomes = idx->n_genomes;
+}
+// false: made for another index, or for this one before a reduce
+inline bool acc_matches(const AccBase &a, const pa_index *idx) { return a.idx == idx && a.epoch == idx->epoch; }
+// The caller's genome coordinates: the forward bases of every genome [G], and the bases before it [G + 1].
+inline std::vector<uint64_t> forward_lengths(const pa_index *idx) {
+    std::vector<uint64_t> len(idx->n_genomes);
+    for (uint32_t g = 0; g < idx->n_genomes; g++)
+        len[g] = idx->both_strands ? idx->h_fwd_len[g] : idx->h_goff[g + 1] - idx->h_goff[g];
+    return len;
+}
+inline std::vector<uint64_t> forward_offsets(const pa_index *idx) {
+    std::vector<uint64_t> off(idx->n_genomes + 1, 0);
+    const std::vector<uint64_t> len = forward_lengths(idx);
+    for (uint32_t g = 0; g < idx->n_genomes; g++) off[g + 1] = off[g] + len[g];
+    return off;
+}
+}  // namespace pa
+
+// Depth accumulator of one index (pa_cover.hip): difference arrays in forward
+// genome coordinates, |g| + 1 entries per genome and category (genome g's at
+// foff[g] + g), the ambiguous category after the unique one.
+struct pa_coverage : pa::AccBase {
     std::vector<uint64_t> h_foff;      // [G+1] forward bases before genome g
     uint64_t *foff = nullptr;          // device copy
     uint64_t entries = 0;              // per category: forward bases + G
@@ -215,11 +340,7 @@ struct pa_coverage {
 
 // Base-count accumulator of one index (pa_pileup.hip): four uint32 counts (A, C,
 // G, T) per forward genome base, position x of genome g at 4 (foff[g] + x).
-struct pa_pileup {
-    int device = 0;
-    const pa_index *idx = nullptr;     // the index it was made for, at
-    uint64_t epoch = 0;                //   this build of it
-    uint32_t n_genomes = 0;
+struct pa_pileup : pa::AccBase {
     int both = 0;
     std::vector<uint64_t> h_foff;      // [G+1] forward bases before genome g
     uint64_t *foff = nullptr;          // device copy
@@ -233,11 +354,7 @@ struct pa_pileup {
 // classes.  The unique reads are counted per genome on the device; the classes
 // of the ambiguous reads, a few thousand at most, are merged on the host batch
 // after batch, keyed by their ascending genome list (the reported order).
-struct pa_abundance {
-    int device = 0;
-    const pa_index *idx = nullptr;     // the index it was made for, at
-    uint64_t epoch = 0;                //   this build of it
-    uint32_t n_genomes = 0;
+struct pa_abundance : pa::AccBase {
     std::vector<double> h_len;         // [G] L_g = |g| - k + 1 (forward windows)
     unsigned long long *counts = nullptr;  // device [4 + G]: reads unique, ambiguous, unmapped, dropped; unique reads of g
     std::map<std::vector<uint32_t>, uint64_t> classes;  // C -> n_C of the ambiguous reads
@@ -314,17 +431,16 @@ pa_status assign_lists(pa_index *idx, const pa_reads *r, const DevParams &p, con
 // The whole pass with everything left on the device (detail_pass_device's
 // sibling): type, qf, hr, len [n], off [n + 1] and total always; lists [total]
 // when total <= list_cap (else null: the caller reports PA_EINVAL or only
-// wanted the total).  Every read covered, or PA_EINTERNAL.  Free with assign_free.
+// wanted the total).  Every read covered, or PA_EINTERNAL.  The buffers belong
+// to the caller's Bufs b: they live as long as it does.
 struct AssignDev {
     uint8_t *type = nullptr;
     uint32_t *qf = nullptr, *hr = nullptr, *len = nullptr, *lists = nullptr;
     uint64_t *off = nullptr;
     uint64_t total = 0;
-    void *block = nullptr;  // (the per-read arrays' allocation)
 };
 pa_status assign_pass_device(pa_index *idx, const pa_reads *r, const DevParams &p, uint64_t list_cap, AssignDev &out,
-                             hipStream_t st);
-void assign_free(AssignDev &d);
+                             Bufs &b, hipStream_t st);
 pa_status align_reads(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *type, uint32_t *qf, uint32_t *hr,
                       uint64_t *list_off, uint32_t *lists, uint64_t list_cap, uint64_t *list_total, hipStream_t st);
 // coverage (pa_cover.hip)
@@ -345,16 +461,15 @@ pa_status coverage_depth(pa_coverage *cov, uint32_t genome, uint64_t first, uint
 // view, the assign pass left on the device, k_place's workspace and launch.
 // as.lists is null and placed false when nothing is listed or as.total >
 // list_cap; else starts / agree (when wanted) hold one value per list entry
-// and, with acc, the depths are accumulated.  Free with placed_free.
+// and, with acc, the depths are accumulated.  Held by the caller's Bufs b.
 struct PlacedDev {
     AssignDev as;
     int64_t *starts = nullptr;  // [as.total] s(read, genome)
     uint8_t *agree = nullptr;   // [as.total] 1: every voting window named that diagonal
     bool placed = false;
 };
-pa_status place_device(pa_index *idx, const pa_reads *r, const DevParams &p, const char *what, pa_coverage *acc,
-                       uint64_t list_cap, bool want_starts, bool want_agree, PlacedDev &out, hipStream_t st);
-void placed_free(PlacedDev &pd);
+pa_status place_device(pa_index *idx, const pa_reads *r, const DevParams &p, pa_coverage *acc,
+                       uint64_t list_cap, bool want_starts, bool want_agree, PlacedDev &out, Bufs &b, hipStream_t st);
 // pileup (pa_pileup.hip)
 pa_status pileup_create(const pa_index *idx, pa_pileup **out);
 pa_status pileup_reset(pa_pileup *p, hipStream_t st);
@@ -408,3 +523,11 @@ void warm_align(hipStream_t st);
 void warm_fastq(hipStream_t st);
 void warm_dump(hipStream_t st);
 }  // namespace pa
+
+// Test hook (pa_mem.cpp; tests/test_gpu_alloc_paths.py), not part of the ABI:
+// the nth call from now of dev_malloc_raw / dev_malloc_try returns
+// hipErrorOutOfMemory without calling HIP (0: off); the calls made so far; the
+// buffers handed out and not yet given back.
+extern "C" void pa_test_alloc_fail_at(int64_t nth);
+extern "C" uint64_t pa_test_alloc_calls(void);
+extern "C" uint64_t pa_test_alloc_live(void);

@@ -164,55 +164,35 @@ pa_status scan_nw(const pa_index *idx, const std::vector<uint64_t> &keys, size_t
     const uint64_t total = idx->h_goff[idx->n_genomes];
     const uint64_t threads = (total + kScanRun - 1) / kScanRun;
     const unsigned grid = (unsigned)std::max<uint64_t>((threads + kBlock - 1) / kBlock, 1);
+    pa::ErrOp op("pa_index_positions");
+    pa::Bufs b(st);
     QEnt<NW> *d_qt = nullptr;
     unsigned long long *d_n = nullptr;
     DevHit *d_hits = nullptr;
     uint64_t cap = 1u << 16;
-    pa_status rc = PA_OK;
-    // (every exit below goes through the one cleanup at the end)
-    if (pa::dev_malloc(&d_qt, qsize * sizeof(QEnt<NW>)) != hipSuccess || pa::dev_malloc(&d_n, 8) != hipSuccess) {
-        pa::set_error("pa_index_positions: out of device memory for the query table");
-        rc = PA_ENOMEM;
-    } else if (hipMemcpyAsync(d_qt, qt.data(), qsize * sizeof(QEnt<NW>), hipMemcpyHostToDevice, st) != hipSuccess) {
-        pa::set_error("pa_index_positions: HIP error copying the query table");
-        rc = PA_EDEVICE;
-    }
-    for (int attempt = 0; rc == PA_OK && attempt < 2; attempt++) {
-        if (pa::dev_malloc(&d_hits, cap * sizeof(DevHit)) != hipSuccess) {
-            d_hits = nullptr;
-            pa::set_error("pa_index_positions: out of device memory for the hits");
-            rc = PA_ENOMEM;
-            break;
-        }
+    PA_HIP(b.get(&d_qt, qsize * sizeof(QEnt<NW>)));
+    PA_HIP(b.get(&d_n, 8));
+    PA_HIP(hipMemcpyAsync(d_qt, qt.data(), qsize * sizeof(QEnt<NW>), hipMemcpyHostToDevice, st));
+    for (int attempt = 0; attempt < 2; attempt++) {
+        PA_HIP(b.get(&d_hits, cap * sizeof(DevHit)));
         unsigned long long n = 0;
-        if (hipMemsetAsync(d_n, 0, 8, st) != hipSuccess) rc = PA_EDEVICE;
-        if (rc == PA_OK && total >= (uint64_t)k && k > 0)
+        PA_HIP(hipMemsetAsync(d_n, 0, 8, st));
+        if (total >= (uint64_t)k && k > 0)
             hipLaunchKernelGGL(k_kmer_scan<NW>, dim3(grid), dim3(kBlock), 0, st, idx->codes, idx->goff,
                                idx->n_genomes, k, mask0_host(k, NW), d_qt, qsize - 1, d_n, d_hits, cap,
                                idx->fwd_len);
-        if (rc == PA_OK && (hipGetLastError() != hipSuccess ||
-                            hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                            hipStreamSynchronize(st) != hipSuccess)) {
-            pa::set_error("pa_index_positions: HIP error in the scan");
-            rc = PA_EDEVICE;
-        }
-        if (rc != PA_OK) break;
+        PA_HIP(hipGetLastError());
+        PA_HIP(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, st));
+        PA_HIP(hipStreamSynchronize(st));
         if (n <= cap) {
             out.resize(n);
-            if (n && hipMemcpy(out.data(), d_hits, n * sizeof(DevHit), hipMemcpyDeviceToHost) != hipSuccess) {
-                pa::set_error("pa_index_positions: HIP error copying the hits");
-                rc = PA_EDEVICE;
-            }
+            if (n) PA_HIP(hipMemcpy(out.data(), d_hits, n * sizeof(DevHit), hipMemcpyDeviceToHost));
             break;
         }
-        pa::dev_free(d_hits);  // more hits than room: once more with room for all of them
-        d_hits = nullptr;
+        b.free(d_hits);  // more hits than room: once more with room for all of them
         cap = n;
     }
-    if (d_hits) pa::dev_free(d_hits);
-    if (d_qt) pa::dev_free(d_qt);
-    if (d_n) pa::dev_free(d_n);
-    return rc;
+    return PA_OK;
 }
 
 }  // namespace
@@ -260,18 +240,7 @@ pa_status index_positions(const pa_index *idx, const char *kmers, uint64_t n, ui
         refs.back().push_back(ent[i].second);
     }
     std::vector<DevHit> dh;
-    pa_status s;
-    switch (nw) {
-        case 1: s = scan_nw<1>(idx, keys, refs.size(), dh, st); break;
-        case 2: s = scan_nw<2>(idx, keys, refs.size(), dh, st); break;
-        case 3: s = scan_nw<3>(idx, keys, refs.size(), dh, st); break;
-        case 4: s = scan_nw<4>(idx, keys, refs.size(), dh, st); break;
-        case 5: s = scan_nw<5>(idx, keys, refs.size(), dh, st); break;
-        case 6: s = scan_nw<6>(idx, keys, refs.size(), dh, st); break;
-        case 7: s = scan_nw<7>(idx, keys, refs.size(), dh, st); break;
-        default: s = scan_nw<8>(idx, keys, refs.size(), dh, st); break;
-    }
-    if (s != PA_OK) return s;
+    PA_TRY(with_nw(nw, [&](auto w_) { return scan_nw<w_()>(idx, keys, refs.size(), dh, st); }));
     std::vector<pa_kmer_hit> outv;
     for (const DevHit &h : dh)
         for (uint32_t e : refs[h.id]) outv.push_back(pa_kmer_hit{(e >> 1) | ((e & 1u) << 31), h.genome, h.pos});

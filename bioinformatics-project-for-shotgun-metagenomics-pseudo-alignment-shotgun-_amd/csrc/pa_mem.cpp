@@ -15,6 +15,7 @@
 //
 // PA_POOL=0 turns the pool off (A/B); PA_POOL_MIN_MB overrides kPoolMin.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <iterator>
 #include <map>
@@ -116,9 +117,31 @@ size_t trim_locked(Pool &P, int dev) {
     return n;
 }
 
+// Test hook (pa_internal.h): allocation calls, buffers out, and the call that is to fail.
+std::atomic<uint64_t> g_calls{0}, g_live{0};
+std::atomic<int64_t> g_fail_in{0};
+
+bool hook_fails() {
+    g_calls++;
+    return g_fail_in.load() > 0 && g_fail_in.fetch_sub(1) == 1;
+}
+
+hipError_t counted(hipError_t e) {
+    if (e == hipSuccess) g_live++;
+    return e;
+}
+
+hipError_t malloc_any(void **p, size_t n);
+
 }  // namespace
 
 hipError_t dev_malloc_raw(void **p, size_t n) {
+    if (hook_fails()) return hipErrorOutOfMemory;
+    return counted(malloc_any(p, n));
+}
+
+namespace {
+hipError_t malloc_any(void **p, size_t n) {
     Pool &P = pool();
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -159,12 +182,12 @@ hipError_t dev_malloc_raw(void **p, size_t n) {
     return hipSuccess;
 }
 
-hipError_t dev_malloc_try(void **p, size_t n) {
+hipError_t malloc_try(void **p, size_t n) {
     Pool &P = pool();
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
-    if (!P.on || n < P.min_bytes) return dev_malloc_raw(p, n);
+    if (!P.on || n < P.min_bytes) return malloc_any(p, n);
     const size_t len = (n + kGranule - 1) / kGranule * kGranule;
     std::lock_guard<std::mutex> g(P.mu);
     size_t si = 0, off = 0;
@@ -189,6 +212,12 @@ hipError_t dev_malloc_try(void **p, size_t n) {
     P.live[*p] = Live{si, off, len};
     return hipSuccess;
 }
+}  // namespace
+
+hipError_t dev_malloc_try(void **p, size_t n) {
+    if (hook_fails()) return hipErrorOutOfMemory;
+    return counted(malloc_try(p, n));
+}
 
 // A pooled range is reusable only once no queued work can still touch it:
 // hipFree waits for the device, so the pool does too before the range goes
@@ -198,6 +227,7 @@ hipError_t dev_malloc_try(void **p, size_t n) {
 // waiting, so no other thread can take it meanwhile.
 hipError_t dev_free(void *p) {
     if (!p) return hipSuccess;
+    g_live--;
     Pool &P = pool();
     int sdev = -1;
     {
@@ -274,6 +304,10 @@ size_t dev_trim(int dev) {
 }
 
 }  // namespace pa
+
+extern "C" void pa_test_alloc_fail_at(int64_t nth) { pa::g_fail_in = nth > 0 ? nth : 0; }
+extern "C" uint64_t pa_test_alloc_calls(void) { return pa::g_calls; }
+extern "C" uint64_t pa_test_alloc_live(void) { return pa::g_live; }
 
 extern "C" pa_status pa_mem_trim(int device, uint64_t *released) {
     const size_t n = pa::dev_trim(device);

@@ -197,23 +197,12 @@ __global__ __launch_bounds__(kBlock) void k_pileup_call(const uint4 *__restrict_
     }
 }
 
-#define P_HIP(call)                                                                                  \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            (void)hipGetLastError();                                                                 \
-            pa::set_error(std::string(what) + ": " + hipGetErrorString(e_) + " (" #call ")");       \
-            cleanup();                                                                               \
-            return e_ == hipErrorOutOfMemory ? PA_ENOMEM : PA_EDEVICE;                               \
-        }                                                                                            \
-    } while (0)
-
 }  // namespace
 
 namespace pa {
 
 pa_status pileup_create(const pa_index *idx, pa_pileup **out) {
-    const char *what = "pa_pileup_create";
+    ErrOp op("pa_pileup_create");
     const uint32_t G = idx->n_genomes;
     const uint64_t total = idx->h_goff.empty() ? 0 : idx->h_goff[G];
     if (total >= 0xFFFFFFFFull) {
@@ -221,37 +210,31 @@ pa_status pileup_create(const pa_index *idx, pa_pileup **out) {
                   "2 |g| + 1 per genome)");
         return PA_EUNSUPPORTED;
     }
-    pa_pileup *p = new (std::nothrow) pa_pileup();
+    std::unique_ptr<pa_pileup, void (*)(pa_pileup *)> p(new (std::nothrow) pa_pileup(), pileup_free);
     if (!p) {
         set_error("out of host memory");
         return PA_ENOMEM;
     }
-    auto cleanup = [&] { pileup_free(p); };
-    p->device = idx->device;
-    p->idx = idx;
-    p->epoch = idx->epoch;
-    p->n_genomes = G;
+    acc_bind(*p, idx);
     p->both = idx->both_strands;
-    p->h_foff.assign(G + 1, 0);
-    for (uint32_t g = 0; g < G; g++)
-        p->h_foff[g + 1] = p->h_foff[g] + (idx->both_strands ? idx->h_fwd_len[g] : idx->h_goff[g + 1] - idx->h_goff[g]);
+    p->h_foff = forward_offsets(idx);
     const uint64_t F = p->h_foff[G];
-    P_HIP(pa::dev_malloc(&p->foff, (uint64_t)(G + 1) * 8));
-    P_HIP(pa::dev_malloc(&p->counts, std::max<uint64_t>(F, 1) * 16));
-    P_HIP(pa::dev_malloc(&p->ref, std::max<uint64_t>(F, 1)));
-    P_HIP(pa::dev_malloc(&p->stats, 3 * 8));
-    P_HIP(hipMemcpy(p->foff, p->h_foff.data(), (uint64_t)(G + 1) * 8, hipMemcpyHostToDevice));
-    P_HIP(hipMemset(p->counts, 0, std::max<uint64_t>(F, 1) * 16));
-    P_HIP(hipMemset(p->stats, 0, 3 * 8));
+    PA_HIP(pa::dev_malloc(&p->foff, (uint64_t)(G + 1) * 8));
+    PA_HIP(pa::dev_malloc(&p->counts, std::max<uint64_t>(F, 1) * 16));
+    PA_HIP(pa::dev_malloc(&p->ref, std::max<uint64_t>(F, 1)));
+    PA_HIP(pa::dev_malloc(&p->stats, 3 * 8));
+    PA_HIP(hipMemcpy(p->foff, p->h_foff.data(), (uint64_t)(G + 1) * 8, hipMemcpyHostToDevice));
+    PA_HIP(hipMemset(p->counts, 0, std::max<uint64_t>(F, 1) * 16));
+    PA_HIP(hipMemset(p->stats, 0, 3 * 8));
     // the forward text's codes: the first |g| codes of every region
     for (uint32_t g = 0; g < G; g++) {
         const uint64_t n = p->h_foff[g + 1] - p->h_foff[g];
-        if (n) P_HIP(hipMemcpy(p->ref + p->h_foff[g], idx->codes + idx->h_goff[g], n, hipMemcpyDeviceToDevice));
+        if (n) PA_HIP(hipMemcpy(p->ref + p->h_foff[g], idx->codes + idx->h_goff[g], n, hipMemcpyDeviceToDevice));
     }
     // (device memsets and copies return before they are done, and the first add may
     // come on a stream that does not wait for the null stream: all there on return)
-    P_HIP(hipStreamSynchronize(nullptr));
-    *out = p;
+    PA_HIP(hipStreamSynchronize(nullptr));
+    *out = p.release();
     return PA_OK;
 }
 
@@ -273,13 +256,10 @@ pa_status pileup_reset(pa_pileup *p, hipStream_t st) {
 
 pa_status pileup_add(pa_index *idx, const pa_reads *r, const DevParams &prm, uint32_t min_base_quality, pa_pileup *acc,
                      hipStream_t st) {
-    const char *what = "pa_pileup_add";
+    ErrOp op("pa_pileup_add");
+    Bufs b(st);
     PlacedDev pd;
-    auto cleanup = [&] {
-        (void)hipStreamSynchronize(st);
-        placed_free(pd);
-    };
-    PA_TRY(place_device(idx, r, prm, what, nullptr, ~0ull, true, true, pd, st));
+    PA_TRY(place_device(idx, r, prm, nullptr, ~0ull, true, true, pd, b, st));
     const uint64_t n = r->n;
     if (n == 0) return PA_OK;
     if (pd.placed) {
@@ -305,10 +285,9 @@ pa_status pileup_add(pa_index *idx, const pa_reads *r, const DevParams &prm, uin
         // a wave per read, the waves striding over the batch: one stats update per wave
         const unsigned blocks = (unsigned)std::min<uint64_t>((n + 3) / 4, 8192);
         hipLaunchKernelGGL(k_pileup, dim3(blocks), dim3(kBlock), 0, st, a);
-        P_HIP(hipGetLastError());
-        P_HIP(hipStreamSynchronize(st));
+        PA_HIP(hipGetLastError());
+        PA_HIP(hipStreamSynchronize(st));
     }
-    cleanup();
     acc->reads_added += n;
     return PA_OK;
 }
@@ -333,7 +312,7 @@ pa_status pileup_counts(const pa_pileup *p, uint32_t genome, uint64_t first, uin
 
 pa_status pileup_variants(const pa_pileup *p, uint32_t min_depth, uint32_t min_alt_count, uint32_t min_alt_permille,
                           pa_variant *out, uint64_t cap, uint64_t *n, hipStream_t st) {
-    const char *what = "pa_pileup_variants";
+    ErrOp op("pa_pileup_variants");
     static_assert(sizeof(pa_variant) == 40, "pa_variant is 40 bytes");
     *n = 0;
     const uint64_t F = p->h_foff[p->n_genomes];
@@ -341,44 +320,33 @@ pa_status pileup_variants(const pa_pileup *p, uint32_t min_depth, uint32_t min_a
     const unsigned grid = (unsigned)((F + (uint64_t)kTiles * kBlock - 1) / ((uint64_t)kTiles * kBlock));
     unsigned long long *d_n = nullptr, *d_off = nullptr;
     pa_variant *d_out = nullptr;
-    void *tmp = nullptr;
-    auto cleanup = [&] {
-        (void)hipStreamSynchronize(st);
-        pa::dev_free(d_n); pa::dev_free(d_off); pa::dev_free(d_out); pa::dev_free(tmp);
-    };
-    P_HIP(pa::dev_malloc(&d_n, ((uint64_t)grid + 1) * 8));
-    P_HIP(pa::dev_malloc(&d_off, ((uint64_t)grid + 1) * 8));
-    P_HIP(hipMemsetAsync(d_n + grid, 0, 8, st));
+    Bufs b(st);
+    PA_HIP(b.get(&d_n, ((uint64_t)grid + 1) * 8));
+    PA_HIP(b.get(&d_off, ((uint64_t)grid + 1) * 8));
+    PA_HIP(hipMemsetAsync(d_n + grid, 0, 8, st));
     const uint4 *counts = (const uint4 *)p->counts;
     hipLaunchKernelGGL(k_pileup_call<false>, dim3(grid), dim3(kBlock), 0, st, counts, p->ref, p->foff, p->n_genomes, F,
                        min_depth, min_alt_count, min_alt_permille, d_n, (pa_variant *)nullptr, (uint64_t)0);
-    P_HIP(hipGetLastError());
-    size_t tmp_bytes = 0;
-    P_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_n, d_off, 0ull, (size_t)grid + 1,
-                                  rocprim::plus<unsigned long long>(), st));
-    P_HIP(pa::dev_malloc(&tmp, std::max<size_t>(tmp_bytes, 16)));
-    P_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, d_n, d_off, 0ull, (size_t)grid + 1,
-                                  rocprim::plus<unsigned long long>(), st));
+    PA_HIP(hipGetLastError());
+    PA_HIP(with_temp(b, [&](void *tmp, size_t &tmp_bytes) {
+        return rocprim::exclusive_scan(tmp, tmp_bytes, d_n, d_off, 0ull, (size_t)grid + 1,
+                                       rocprim::plus<unsigned long long>(), st);
+    }));
     unsigned long long total = 0;
-    P_HIP(hipMemcpyAsync(&total, d_off + grid, 8, hipMemcpyDeviceToHost, st));
-    P_HIP(hipStreamSynchronize(st));
+    PA_HIP(hipMemcpyAsync(&total, d_off + grid, 8, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     *n = total;
     if (total > cap) {
         set_error("pa_pileup_variants: cap smaller than the number of records");
-        cleanup();
         return PA_EINVAL;
     }
-    if (total == 0) {
-        cleanup();
-        return PA_OK;
-    }
-    P_HIP(pa::dev_malloc(&d_out, total * sizeof(pa_variant)));
+    if (total == 0) return PA_OK;
+    PA_HIP(b.get(&d_out, total * sizeof(pa_variant)));
     hipLaunchKernelGGL(k_pileup_call<true>, dim3(grid), dim3(kBlock), 0, st, counts, p->ref, p->foff, p->n_genomes, F,
                        min_depth, min_alt_count, min_alt_permille, d_off, d_out, (uint64_t)total);
-    P_HIP(hipGetLastError());
-    P_HIP(hipMemcpyAsync(out, d_out, total * sizeof(pa_variant), hipMemcpyDeviceToHost, st));
-    P_HIP(hipStreamSynchronize(st));
-    cleanup();
+    PA_HIP(hipGetLastError());
+    PA_HIP(hipMemcpyAsync(out, d_out, total * sizeof(pa_variant), hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
     return PA_OK;
 }
 

@@ -214,6 +214,9 @@ def lib():
         "pa_profile_read": (I32, [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.POINTER(U64)]),
         "pa_profile_read_kernels": (I32, [P, P, P]),
         "pa_mem_trim": (I32, [I32, ctypes.POINTER(U64)]),
+        "pa_test_alloc_fail_at": (None, [I64]),
+        "pa_test_alloc_calls": (U64, []),
+        "pa_test_alloc_live": (U64, []),
         "pa_parse_text": (I32, [I32, P, U64, I32, I32, PP]),
         "pa_parse_file": (I32, [I32, ctypes.c_char_p, I32, PP]),
         "pa_gz_inflate_file": (I32, [ctypes.c_char_p, I32, P, U64, ctypes.POINTER(U64)]),
@@ -282,6 +285,21 @@ def mem_trim(device: int = -1) -> int:
     n = U64(0)
     _check(lib().pa_mem_trim(int(device), ctypes.byref(n)))
     return int(n.value)
+
+
+def test_alloc_fail_at(nth: int) -> None:
+    """Test hook: the nth device allocation from now fails with out-of-memory (0: off)."""
+    lib().pa_test_alloc_fail_at(nth)
+
+
+def test_alloc_calls() -> int:
+    """Test hook: device allocation calls made so far."""
+    return int(lib().pa_test_alloc_calls())
+
+
+def test_alloc_live() -> int:
+    """Test hook: device buffers handed out and not yet given back."""
+    return int(lib().pa_test_alloc_live())
 
 
 def gz_inflate_file(path: str, cap: int, threads: Optional[int] = None) -> bytes:
