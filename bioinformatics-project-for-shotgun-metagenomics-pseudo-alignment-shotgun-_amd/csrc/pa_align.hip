@@ -477,11 +477,15 @@ __device__ __forceinline__ uint32_t block_max(uint32_t v, uint32_t *red) {
 // table probe, the distinct k-mers' hash (slot -> first window).  Returns 0
 // when no k-mer of the read is retained (else the threads that retained one);
 // qf / hr get the filtered and the redundant windows' counts.
-template <int NW>
+// PAIR (k_align_pair_exact): the windows of two mates in one loop, mate 1's
+// at the numbers 0 .. W1 - 1 and mate 2's (seq2 / qual2 + off2) at W1 .. W - 1, so
+// that dh_min orders first appearance mate 1 first; no window spans the mates.
+template <int NW, bool PAIR = false>
 __device__ __forceinline__ uint32_t exact_windows(const AlignArgs &a, const ExactArgs &x, const ExactWs &ws,
                                                   const Slot<NW> *table, uint32_t G, int k, uint64_t mask0,
                                                   bool has_mkq, bool has_mg, uint64_t off, uint32_t W, uint32_t *red,
-                                                  uint32_t &qf_out, uint32_t &hr_out) {
+                                                  uint32_t &qf_out, uint32_t &hr_out, const uint8_t *seq2 = nullptr,
+                                                  const uint8_t *qual2 = nullptr, uint64_t off2 = 0, uint32_t W1 = 0) {
     for (uint32_t i = threadIdx.x; i < x.dh; i += kBlock) {
         st_agent(&ws.dh_key[i], EMPTY);
         st_agent(&ws.dh_min[i], NONE);
@@ -494,9 +498,14 @@ __device__ __forceinline__ uint32_t exact_windows(const AlignArgs &a, const Exac
     uint32_t qf = 0, hr = 0, any = 0;
     for (uint32_t w = threadIdx.x; w < W; w += kBlock) {
         ws.wslot[w] = EMPTY;
+        const uint8_t *seq = a.seq, *qual = a.qual;
+        uint64_t at = off + w;  // the window's first base
+        if constexpr (PAIR) {
+            if (w >= W1) seq = seq2, qual = qual2, at = off2 + (w - W1);
+        }
         if (has_mkq) {
             uint32_t s = 0;
-            for (int i = 0; i < k; i++) s += a.qual[off + w + i];
+            for (int i = 0; i < k; i++) s += qual[at + i];
             if ((int64_t)s < (int64_t)a.prm.mkq * k) {
                 qf++;
                 continue;
@@ -507,7 +516,7 @@ __device__ __forceinline__ uint32_t exact_windows(const AlignArgs &a, const Exac
         for (int j = 0; j < NW; j++) key.w[j] = 0;
         bool clean = true;
         for (int i = 0; i < k; i++) {
-            uint32_t c = base_code(a.seq[off + w + i]);
+            uint32_t c = base_code(seq[at + i]);
             clean &= c < 4;
             key_push(key, c & 3, mask0);
         }
@@ -604,7 +613,142 @@ __device__ __forceinline__ void exact_restore(const ExactWs &ws, uint32_t nt, ui
     __syncthreads();
 }
 
+// exact_decide: the reference's decision over the totals (src/kmer.py:444-480)
+// and genomes_mapped_to -- to the counters (x.detail 0, read number read_idx) or
+// to lists[list_off[r] ..) (x.detail 2).  Shared by k_align_exact and
+// k_align_pair_exact; rank_key is the caller's LDS (kRankLds entries).
 constexpr uint32_t kRankLds = 2048;  // genomes of a read's list ranked in LDS (16 KB); more: over the scratch
+__device__ __forceinline__ uint8_t exact_decide(const AlignArgs &a, const ExactArgs &x, const ExactWs &ws, uint64_t r,
+                                                uint64_t read_idx, uint32_t nt, uint32_t *red, uint32_t &n_rank,
+                                                uint64_t *rank_key, uint32_t &list_len) {
+    // ---- decision (src/kmer.py:444-480)
+    uint32_t nspec = 0, maxcnt = 0;
+    for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
+        uint32_t c = ld_agent(&ws.g_spec[ws.touched[t]]);
+        nspec += c > 0;
+        maxcnt = max(maxcnt, c);
+    }
+    nspec = block_sum(nspec, red);
+    maxcnt = block_max(maxcnt, red);
+    uint8_t type = PA_AMBIGUOUSLY_MAPPED;
+    uint32_t gstar = NONE;
+    bool unique = false, demote = false;
+    uint32_t tstar = 0;
+    if (nspec > 0) {
+        // top = first-inserted genome among those with the max count
+        uint32_t best = 0;  // encodes (NONE - first window) to take a max
+        for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
+            uint32_t g = ws.touched[t];
+            if (ld_agent(&ws.g_spec[g]) == maxcnt) best = max(best, NONE - ld_agent(&ws.g_specmin[g]));
+        }
+        best = block_max(best, red);
+        uint32_t sec = 0, gs = 0;
+        for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
+            uint32_t g = ws.touched[t];
+            uint32_t c = ld_agent(&ws.g_spec[g]);
+            if (c == maxcnt && NONE - ld_agent(&ws.g_specmin[g]) == best)
+                gs = g + 1;
+            else
+                sec = max(sec, c);
+        }
+        gstar = block_max(gs, red) - 1;
+        sec = block_max(sec, red);
+        unique = nspec == 1 || (int64_t)maxcnt >= (int64_t)sec + a.prm.m;
+        if (unique && a.prm.p >= 0) {
+            tstar = ld_agent(&ws.g_tot[gstar]);
+            uint32_t mx = 0;
+            for (uint32_t t = threadIdx.x; t < nt; t += kBlock)
+                mx = max(mx, ld_agent(&ws.g_tot[ws.touched[t]]));
+            mx = block_max(mx, red);
+            demote = (int64_t)mx - (int64_t)tstar > a.prm.p;
+        }
+    }
+    // ---- emit genomes_mapped_to with list positions
+    if (unique && !demote) {
+        type = PA_UNIQUELY_MAPPED;
+        list_len = 1;
+        if (threadIdx.x == 0) {
+            if (x.detail == 2) x.lists[x.list_off[r]] = gstar;
+            if (!x.detail) {
+                atomicAdd(&a.uniq[gstar], 1ull);
+                atomicMin(&a.first[gstar], (unsigned long long)first_key(read_idx, 0));
+            }
+        }
+    } else if (unique && demote) {
+        // the listed genomes' order keys (first window << 32 | genome)
+        // staged in LDS once, so that each one's rank is counted over
+        // LDS rather than over the scratch in global memory (2 nt loads
+        // per genome: ~1 ms for the reads of C5's families)
+        if (threadIdx.x == 0) n_rank = 0;
+        __syncthreads();
+        uint32_t nq = 0;
+        for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
+            const uint32_t g = ws.touched[t];
+            if (ld_agent(&ws.g_tot[g]) < tstar) continue;
+            nq++;
+            const uint32_t i = atomicAdd(&n_rank, 1u);
+            if (i < kRankLds) rank_key[i] = ((uint64_t)ld_agent(&ws.g_totmin[g]) << 32) | g;
+        }
+        nq = block_sum(nq, red);  // (its barriers also publish rank_key)
+        list_len = 1 + nq;
+        for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
+            const uint32_t g = ws.touched[t];
+            const uint32_t tg = ld_agent(&ws.g_tot[g]);
+            if (tg < tstar) continue;
+            const uint64_t me = ((uint64_t)ld_agent(&ws.g_totmin[g]) << 32) | g;
+            uint32_t rank = 1;
+            if (nq <= kRankLds) {
+                for (uint32_t u = 0; u < nq; u++) rank += rank_key[u] < me;
+            } else {
+                for (uint32_t u = 0; u < nt; u++) {
+                    const uint32_t h = ws.touched[u];
+                    if (ld_agent(&ws.g_tot[h]) >= tstar &&
+                        (((uint64_t)ld_agent(&ws.g_totmin[h]) << 32) | h) < me)
+                        rank++;
+                }
+            }
+            if (x.detail == 2) x.lists[x.list_off[r] + rank] = g;
+            if (!x.detail) {
+                atomicAdd(&a.amb[g], g == gstar ? 2ull : 1ull);
+                atomicMin(&a.first[g], (unsigned long long)first_key(read_idx, g == gstar ? 0 : rank));
+            }
+        }
+        if (threadIdx.x == 0 && x.detail == 2) x.lists[x.list_off[r]] = gstar;
+    } else if (nspec > 0) {
+        list_len = nspec;
+        // (the genomes with specific k-mers: their first windows staged in LDS, as above)
+        if (threadIdx.x == 0) n_rank = 0;
+        __syncthreads();
+        for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
+            const uint32_t g = ws.touched[t];
+            if (ld_agent(&ws.g_spec[g]) == 0) continue;
+            const uint32_t i = atomicAdd(&n_rank, 1u);
+            if (i < kRankLds) rank_key[i] = ld_agent(&ws.g_specmin[g]);
+        }
+        __syncthreads();
+        for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
+            const uint32_t g = ws.touched[t];
+            if (ld_agent(&ws.g_spec[g]) == 0) continue;
+            const uint32_t mw = ld_agent(&ws.g_specmin[g]);
+            uint32_t rank = 0;
+            if (nspec <= kRankLds) {
+                for (uint32_t u = 0; u < nspec; u++) rank += rank_key[u] < mw;
+            } else {
+                for (uint32_t u = 0; u < nt; u++) {
+                    const uint32_t h = ws.touched[u];
+                    if (ld_agent(&ws.g_spec[h]) > 0 && ld_agent(&ws.g_specmin[h]) < mw) rank++;
+                }
+            }
+            if (x.detail == 2) x.lists[x.list_off[r] + rank] = g;
+            if (!x.detail) {
+                atomicAdd(&a.amb[g], 1ull);
+                atomicMin(&a.first[g], (unsigned long long)first_key(read_idx, rank));
+            }
+        }
+    }
+    return type;
+}
+
 template <int NW>
 __global__ __launch_bounds__(kBlock) void k_align_exact(ExactArgs x) {
     const AlignArgs &a = x.a;
@@ -661,131 +805,7 @@ __global__ __launch_bounds__(kBlock) void k_align_exact(ExactArgs x) {
         if (any) {
             exact_totals(a, x, ws, G, W, n_touched, n_cls);
             const uint32_t nt = n_touched;
-            // ---- decision (src/kmer.py:444-480)
-            uint32_t nspec = 0, maxcnt = 0;
-            for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
-                uint32_t c = ld_agent(&ws.g_spec[ws.touched[t]]);
-                nspec += c > 0;
-                maxcnt = max(maxcnt, c);
-            }
-            nspec = block_sum(nspec, red);
-            maxcnt = block_max(maxcnt, red);
-            type = PA_AMBIGUOUSLY_MAPPED;
-            uint32_t gstar = NONE;
-            bool unique = false, demote = false;
-            uint32_t tstar = 0;
-            if (nspec > 0) {
-                // top = first-inserted genome among those with the max count
-                uint32_t best = 0;  // encodes (NONE - first window) to take a max
-                for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
-                    uint32_t g = ws.touched[t];
-                    if (ld_agent(&ws.g_spec[g]) == maxcnt) best = max(best, NONE - ld_agent(&ws.g_specmin[g]));
-                }
-                best = block_max(best, red);
-                uint32_t sec = 0, gs = 0;
-                for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
-                    uint32_t g = ws.touched[t];
-                    uint32_t c = ld_agent(&ws.g_spec[g]);
-                    if (c == maxcnt && NONE - ld_agent(&ws.g_specmin[g]) == best)
-                        gs = g + 1;
-                    else
-                        sec = max(sec, c);
-                }
-                gstar = block_max(gs, red) - 1;
-                sec = block_max(sec, red);
-                unique = nspec == 1 || (int64_t)maxcnt >= (int64_t)sec + a.prm.m;
-                if (unique && a.prm.p >= 0) {
-                    tstar = ld_agent(&ws.g_tot[gstar]);
-                    uint32_t mx = 0;
-                    for (uint32_t t = threadIdx.x; t < nt; t += kBlock)
-                        mx = max(mx, ld_agent(&ws.g_tot[ws.touched[t]]));
-                    mx = block_max(mx, red);
-                    demote = (int64_t)mx - (int64_t)tstar > a.prm.p;
-                }
-            }
-            // ---- emit genomes_mapped_to with list positions
-            if (unique && !demote) {
-                type = PA_UNIQUELY_MAPPED;
-                list_len = 1;
-                if (threadIdx.x == 0) {
-                    if (x.detail == 2) x.lists[x.list_off[r]] = gstar;
-                    if (!x.detail) {
-                        atomicAdd(&a.uniq[gstar], 1ull);
-                        atomicMin(&a.first[gstar], (unsigned long long)first_key(read_idx, 0));
-                    }
-                }
-            } else if (unique && demote) {
-                // the listed genomes' order keys (first window << 32 | genome)
-                // staged in LDS once, so that each one's rank is counted over
-                // LDS rather than over the scratch in global memory (2 nt loads
-                // per genome: ~1 ms for the reads of C5's families)
-                if (threadIdx.x == 0) n_rank = 0;
-                __syncthreads();
-                uint32_t nq = 0;
-                for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
-                    const uint32_t g = ws.touched[t];
-                    if (ld_agent(&ws.g_tot[g]) < tstar) continue;
-                    nq++;
-                    const uint32_t i = atomicAdd(&n_rank, 1u);
-                    if (i < kRankLds) rank_key[i] = ((uint64_t)ld_agent(&ws.g_totmin[g]) << 32) | g;
-                }
-                nq = block_sum(nq, red);  // (its barriers also publish rank_key)
-                list_len = 1 + nq;
-                for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
-                    const uint32_t g = ws.touched[t];
-                    const uint32_t tg = ld_agent(&ws.g_tot[g]);
-                    if (tg < tstar) continue;
-                    const uint64_t me = ((uint64_t)ld_agent(&ws.g_totmin[g]) << 32) | g;
-                    uint32_t rank = 1;
-                    if (nq <= kRankLds) {
-                        for (uint32_t u = 0; u < nq; u++) rank += rank_key[u] < me;
-                    } else {
-                        for (uint32_t u = 0; u < nt; u++) {
-                            const uint32_t h = ws.touched[u];
-                            if (ld_agent(&ws.g_tot[h]) >= tstar &&
-                                (((uint64_t)ld_agent(&ws.g_totmin[h]) << 32) | h) < me)
-                                rank++;
-                        }
-                    }
-                    if (x.detail == 2) x.lists[x.list_off[r] + rank] = g;
-                    if (!x.detail) {
-                        atomicAdd(&a.amb[g], g == gstar ? 2ull : 1ull);
-                        atomicMin(&a.first[g], (unsigned long long)first_key(read_idx, g == gstar ? 0 : rank));
-                    }
-                }
-                if (threadIdx.x == 0 && x.detail == 2) x.lists[x.list_off[r]] = gstar;
-            } else if (nspec > 0) {
-                list_len = nspec;
-                // (the genomes with specific k-mers: their first windows staged in LDS, as above)
-                if (threadIdx.x == 0) n_rank = 0;
-                __syncthreads();
-                for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
-                    const uint32_t g = ws.touched[t];
-                    if (ld_agent(&ws.g_spec[g]) == 0) continue;
-                    const uint32_t i = atomicAdd(&n_rank, 1u);
-                    if (i < kRankLds) rank_key[i] = ld_agent(&ws.g_specmin[g]);
-                }
-                __syncthreads();
-                for (uint32_t t = threadIdx.x; t < nt; t += kBlock) {
-                    const uint32_t g = ws.touched[t];
-                    if (ld_agent(&ws.g_spec[g]) == 0) continue;
-                    const uint32_t mw = ld_agent(&ws.g_specmin[g]);
-                    uint32_t rank = 0;
-                    if (nspec <= kRankLds) {
-                        for (uint32_t u = 0; u < nspec; u++) rank += rank_key[u] < mw;
-                    } else {
-                        for (uint32_t u = 0; u < nt; u++) {
-                            const uint32_t h = ws.touched[u];
-                            if (ld_agent(&ws.g_spec[h]) > 0 && ld_agent(&ws.g_specmin[h]) < mw) rank++;
-                        }
-                    }
-                    if (x.detail == 2) x.lists[x.list_off[r] + rank] = g;
-                    if (!x.detail) {
-                        atomicAdd(&a.amb[g], 1ull);
-                        atomicMin(&a.first[g], (unsigned long long)first_key(read_idx, rank));
-                    }
-                }
-            }
+            type = exact_decide(a, x, ws, r, read_idx, nt, red, n_rank, rank_key, list_len);
             __syncthreads();
             exact_restore(ws, nt, n_touched, n_cls);
         }
@@ -800,6 +820,69 @@ __global__ __launch_bounds__(kBlock) void k_align_exact(ExactArgs x) {
                 if (has_mkq && qf) atomicAdd(&a.stats[4], (unsigned long long)qf);
                 if (has_mg && hr) atomicAdd(&a.stats[5], (unsigned long long)hr);
             }
+        }
+        __syncthreads();
+    }
+}
+
+// The exact kernel over pairs (pa_pair.hip): one
+// workgroup per queued pair, the windows of mate 1 numbered 0 .. W1 - 1 and
+// those of mate 2 W1 .. W1 + W2 - 1 over one dedup hash, so that a k-mer both
+// mates hold counts once, at its first appearance, mate 1's windows first; no
+// window spans the mates.  Then k_align_exact's totals, decision and lists,
+// unchanged.  Detail modes only (1: lengths, 2: lists); a queued pair is never
+// dropped (k_pair_combine settles those from the mates' types).
+struct PairArgs {
+    ExactArgs x;  // x.a: mates 1, the queue of pair numbers; the per-pair outputs
+    const uint8_t *seq2, *qual2;
+    const uint64_t *off2;
+};
+
+template <int NW>
+__global__ __launch_bounds__(kBlock) void k_align_pair_exact(PairArgs y) {
+    const ExactArgs &x = y.x;
+    const AlignArgs &a = x.a;
+    __shared__ uint32_t red[kWaves];
+    __shared__ uint32_t n_touched, n_cls, n_rank;
+    __shared__ uint64_t rank_key[kRankLds];
+    const uint32_t G = a.G;
+    const int k = a.k;
+    const uint64_t mask0 = k > 0 ? mask0_of(k, NW) : 0;
+    const Slot<NW> *table = (const Slot<NW> *)a.table;
+    const bool has_mkq = a.prm.flags & F_MKQ, has_mg = a.prm.flags & F_MG;
+    ExactWs ws = exact_ws(x.ws + (uint64_t)blockIdx.x * x.ws_stride, x.wcap, x.dh, G);
+    for (uint32_t g = threadIdx.x; g < G; g += kBlock) {
+        st_agent(&ws.g_spec[g], 0u);
+        st_agent(&ws.g_specmin[g], NONE);
+        st_agent(&ws.g_tot[g], 0u);
+        st_agent(&ws.g_totmin[g], NONE);
+    }
+    if (threadIdx.x == 0) n_touched = n_cls = 0;
+    __syncthreads();
+    const uint64_t nq = *a.qcount;
+    for (uint64_t q = blockIdx.x; q < nq; q += gridDim.x) {
+        const uint64_t r = a.queue[q];
+        const uint64_t off1 = a.off[r], off2 = y.off2[r];
+        const uint32_t len1 = (uint32_t)(a.off[r + 1] - off1), len2 = (uint32_t)(y.off2[r + 1] - off2);
+        const uint32_t W1 = (k > 0 && len1 >= (uint32_t)k) ? len1 - k + 1 : 0;
+        const uint32_t W2 = (k > 0 && len2 >= (uint32_t)k) ? len2 - k + 1 : 0;
+        uint32_t qf, hr;
+        const uint32_t any = exact_windows<NW, true>(a, x, ws, table, G, k, mask0, has_mkq, has_mg, off1, W1 + W2, red,
+                                                     qf, hr, y.seq2, y.qual2, off2, W1);
+        uint8_t type = PA_UNMAPPED;
+        uint32_t list_len = 0;
+        if (any) {
+            exact_totals(a, x, ws, G, W1 + W2, n_touched, n_cls);
+            const uint32_t nt = n_touched;
+            type = exact_decide(a, x, ws, r, 0, nt, red, n_rank, rank_key, list_len);
+            __syncthreads();
+            exact_restore(ws, nt, n_touched, n_cls);
+        }
+        if (threadIdx.x == 0) {
+            x.type_out[r] = type;
+            x.qf_out[r] = qf;
+            x.hr_out[r] = hr;
+            x.len_out[r] = list_len;
         }
         __syncthreads();
     }
@@ -1152,8 +1235,8 @@ AlignArgs make_args(const pa_index *idx, const pa_reads *r, const pa::DevParams 
 struct DetailOut { uint8_t *type; uint32_t *qf, *hr, *len; const uint64_t *list_off; uint32_t *lists; };
 
 pa_status exact_args(pa_index *idx, const pa_reads *r, const AlignArgs &a, const DetailOut *out, ExactArgs &x,
-                     unsigned &grid) {
-    const uint32_t wcap = std::max<uint32_t>(1, r->max_len);
+                     unsigned &grid, uint32_t pair_len = 0) {  // pair_len: the longest mate 1 + mate 2 (pairs)
+    const uint32_t wcap = std::max<uint32_t>(1, pair_len ? pair_len : r->max_len);
     uint32_t dh = 64;
     while (dh < 2 * wcap) dh <<= 1;
     const uint64_t stride = exact_ws_stride(wcap, dh, idx->n_genomes);
@@ -1621,6 +1704,37 @@ pa_status candidates_pass(pa_index *idx, const pa_reads *r, const DevParams &p_i
     const unsigned grid = (unsigned)std::min<uint64_t>(egrid, n_queued);
     with_nw(idx->nw, [&](auto w) {
         hipLaunchKernelGGL(k_abund_cand<w()>, dim3(grid), dim3(kBlock), 0, st, x);
+    });
+    PA_HIP(hipGetLastError());
+    return PA_OK;
+}
+
+// The pair-exact kernel over a queue of batch-local pair numbers (n_queued of
+// them, also at *d_count): the pairs' types, filter counts and list lengths;
+// with d_off (n + 1 offsets) and d_lists their lists too.
+pa_status pair_exact_pass(pa_index *idx, const pa_reads *m1, const pa_reads *m2, const DevParams &p,
+                          const uint32_t *d_queue, const unsigned long long *d_count, uint64_t n_queued,
+                          uint8_t *d_type, uint32_t *d_qf, uint32_t *d_hr, uint32_t *d_len, const uint64_t *d_off,
+                          uint32_t *d_lists, hipStream_t st) {
+    if (n_queued == 0) return PA_OK;
+    const uint64_t pair_len = (uint64_t)m1->max_len + m2->max_len;
+    if (pair_len > 0x3FFFFFFFull) {
+        set_error("pa_align_pairs: the two mates of a pair hold at most 2^30 - 1 bases together");
+        return PA_EUNSUPPORTED;
+    }
+    // (the filters as given: a threshold no mate can fail only costs its test)
+    AlignArgs a = make_args(idx, m1, p, 0, Switches{});
+    a.queue = const_cast<uint32_t *>(d_queue);
+    a.qcount = const_cast<unsigned long long *>(d_count);
+    const DetailOut out{d_type, d_qf, d_hr, d_len, d_off, d_lists};
+    PairArgs y{};
+    unsigned egrid = 0;
+    PA_TRY(exact_args(idx, m1, a, &out, y.x, egrid, (uint32_t)std::max<uint64_t>(1, pair_len)));
+    y.x.use_queue = 1;
+    y.seq2 = m2->seq, y.qual2 = m2->qual, y.off2 = m2->off;
+    const unsigned grid = (unsigned)std::min<uint64_t>(egrid, n_queued);
+    with_nw(idx->nw, [&](auto w) {
+        hipLaunchKernelGGL(k_align_pair_exact<w()>, dim3(grid), dim3(kBlock), 0, st, y);
     });
     PA_HIP(hipGetLastError());
     return PA_OK;

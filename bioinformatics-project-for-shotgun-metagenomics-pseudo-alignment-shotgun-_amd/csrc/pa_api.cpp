@@ -682,6 +682,34 @@ pa_status pa_align_reads(const pa_index *idx, const pa_reads *reads, const pa_pa
                            list_off, lists, list_cap, list_total, as_stream(stream));
 }
 
+pa_status pa_align_pairs(const pa_index *idx, const pa_reads *mates1, const pa_reads *mates2,
+                         const pa_params *params, uint64_t pair_index_base, pa_result *acc, uint8_t *pair_type,
+                         uint32_t *filtered_kmers, uint32_t *redundant_kmers, uint64_t *list_off, uint32_t *lists,
+                         uint64_t list_cap, uint64_t *list_total, uint64_t *exact_pairs, void *stream) {
+    PA_CHECK(idx && mates1 && mates2, PA_EINVAL, "NULL argument");
+    PA_CHECK(!lists || (pair_type && list_off && list_total), PA_EINVAL,
+             "NULL argument (lists need pair_type, list_off and list_total)");
+    PA_TRY(check_batch(idx, mates1));
+    PA_TRY(check_batch(idx, mates2));
+    PA_CHECK(mates1->n == mates2->n, PA_EINVAL,
+             "pa_align_pairs: the two batches hold different numbers of reads (mate i of each is one pair)");
+    if (acc) PA_TRY(check_result(idx, acc));
+    PA_CHECK(mates1->n < 0xFFFFFFFFull, PA_EUNSUPPORTED,
+             "pa_align_pairs: a batch holds at most 2^32 - 2 pairs (split it; pair_index_base keeps the order)");
+    PA_CHECK(pair_index_base + mates1->n < (1ull << 44), PA_EUNSUPPORTED, "pair index beyond 2^44");
+    pa::DevParams dp;
+    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    if (list_off) list_off[0] = 0;
+    if (list_total) *list_total = 0;
+    if (exact_pairs) *exact_pairs = 0;
+    if (mates1->n == 0) return PA_OK;
+    PA_TRY(prepare_pass(idx, stream));
+    pa::ErrOp op("pa_align_pairs");
+    return pa::align_pairs(const_cast<pa_index *>(idx), mates1, mates2, dp, pair_index_base, acc, pair_type,
+                           filtered_kmers, redundant_kmers, list_off, lists, list_cap, list_total, exact_pairs,
+                           as_stream(stream));
+}
+
 pa_status pa_align_batch(const pa_index *idx, const uint8_t *seq, const uint8_t *qual, const uint64_t *read_off,
                          uint64_t n_reads, uint64_t read_index_base, const pa_params *params, pa_stats *stats,
                          uint64_t *unique_reads, uint64_t *ambiguous_reads, uint64_t *first_key, void *stream) {

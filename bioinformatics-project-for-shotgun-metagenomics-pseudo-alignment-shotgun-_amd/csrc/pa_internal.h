@@ -497,6 +497,14 @@ pa_status abundance_estimate(const pa_abundance *a, uint32_t max_iterations, dou
                              double *abundance, uint32_t *iterations_done, double *last_delta, hipStream_t st);
 pa_status align_candidates(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *type, uint64_t *set_off,
                            uint32_t *sets, uint64_t cap, uint64_t *total, hipStream_t st);
+// pairs (pa_pair.hip; the pair-exact kernel is k_align_exact's sibling in pa_align.hip)
+pa_status pair_exact_pass(pa_index *idx, const pa_reads *m1, const pa_reads *m2, const DevParams &p,
+                          const uint32_t *d_queue, const unsigned long long *d_count, uint64_t n_queued,
+                          uint8_t *d_type, uint32_t *d_qf, uint32_t *d_hr, uint32_t *d_len, const uint64_t *d_off,
+                          uint32_t *d_lists, hipStream_t st);
+pa_status align_pairs(pa_index *idx, const pa_reads *m1, const pa_reads *m2, const DevParams &p, uint64_t base,
+                      pa_result *acc, uint8_t *type, uint32_t *qf, uint32_t *hr, uint64_t *list_off, uint32_t *lists,
+                      uint64_t list_cap, uint64_t *list_total, uint64_t *exact_pairs, hipStream_t st);
 pa_status reads_measure(pa_reads *r, hipStream_t st);  // q_min / len_min of a batch (at its creation)
 // the filters an align of batch r applies: quality thresholds no read can fail dropped
 pa_status effective_params(const pa_reads *r, const DevParams &p, DevParams &out, hipStream_t st);

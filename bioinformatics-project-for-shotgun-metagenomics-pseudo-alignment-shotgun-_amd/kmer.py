@@ -571,6 +571,63 @@ class _Batch:
         return self._dropped
 
 
+    def results(self, index: N.Index):
+        """(types, list offsets, lists) per read of the batch, from the device."""
+        reads = N.Reads.upload(self.seq, self.qual, self.off, device=index.device)
+        try:
+            types, _, _, loff, lists = N.align_reads(index, reads, self.params)
+        finally:
+            reads.close()
+        return types, loff, lists
+
+
+class _PairBatch(_Batch):
+    """A batch of pairs (align_pairs_from_containers): the columns of both mates,
+    ``ids`` the pair identifiers; its per-pair results come from N.align_pairs."""
+
+    __slots__ = ("seq2", "qual2", "off2")
+
+    def __init__(self, base, ids, mate1, mate2, params, mrq, all_dropped=False):
+        super().__init__(base, ids, mate1[0], mate1[1], mate1[2], params, mrq, all_dropped)
+        self.seq2, self.qual2, self.off2 = mate2
+
+    def dropped(self) -> Optional[np.ndarray]:
+        """Pairs dropped by --min-read-quality: either mate fails it."""
+        if self.all_dropped:
+            return np.ones(len(self.ids), dtype=bool)
+        if self.mrq is None:
+            return None
+        if self._dropped is None:
+            self._dropped = _dropped_mask(self.qual, self.off, self.mrq) | _dropped_mask(self.qual2, self.off2,
+                                                                                         self.mrq)
+        return self._dropped
+
+    def results(self, index: N.Index):
+        m1 = N.Reads.upload(self.seq, self.qual, self.off, device=index.device)
+        m2 = N.Reads.upload(self.seq2, self.qual2, self.off2, device=index.device)
+        try:
+            types, _, _, loff, lists, _ = N.align_pairs(index, m1, m2, self.params)
+        finally:
+            m1.close()
+            m2.close()
+        return types, loff, lists
+
+
+def pair_identifier(id1: str, id2: str) -> str:
+    """The identifier of the pair whose mates' FASTQ ids are ``id1`` and ``id2``:
+    each id is cut at its first whitespace, a trailing ``/1`` is removed from
+    mate 1's and a trailing ``/2`` from mate 2's; the two must then be equal."""
+    a = id1.split(None, 1)[0] if id1.strip() else ""
+    b = id2.split(None, 1)[0] if id2.strip() else ""
+    if a.endswith("/1"):
+        a = a[:-2]
+    if b.endswith("/2"):
+        b = b[:-2]
+    if a != b:
+        raise ValueError(f"The identifiers of a pair's mates differ: {id1!r} and {id2!r}")
+    return a
+
+
 class _FileBatch(_Batch):
     """A FASTQ file aligned by pa_align_fastq_file: its columns (ids, bases,
     qualities) are parsed from the file only when per-read results or ids are
@@ -870,6 +927,72 @@ class PseudoAlignment:
             self._ids.update(ids if d is None else (i for i, x in zip(ids, d) if not x))
         self._next_index += n
 
+    def align_pairs_from_containers(self, reads1, reads2, m: int = 1, p: int = 1,
+                                    min_read_quality: Optional[int] = None, min_kmer_quality: Optional[int] = None,
+                                    max_genomes: Optional[int] = None) -> None:
+        """Paired-end reads: record i of ``reads1`` and record i of ``reads2`` are
+        the two ends of one fragment, classified as one by the k-mers of both
+        mates together.  ``reads``, the counters and
+        ``write_assignments`` hold one entry per pair, under pair_identifier of
+        the mates' ids.  The mates are taken as given: nothing is reverse-
+        complemented here, so paired data wants a both-strand reference."""
+        if self in _COVERAGE or self in _PILEUP or self in _ABUNDANCE:
+            raise ValueError("pairs are not supported with coverage, pileup or abundance: those accumulators take reads")
+        ids1, seq1, qual1, off1 = _columnar(reads1)
+        ids2, seq2, qual2, off2 = _columnar(reads2)
+        if len(ids1) != len(ids2):
+            raise ValueError(f"The two read files of a paired job hold different numbers of records: "
+                             f"{len(ids1)} and {len(ids2)}")
+        n = len(ids1)
+        if n == 0:
+            return
+        ids = [pair_identifier(a, b) for a, b in zip(ids1, ids2)]
+        mrq, mkq, mg = min_read_quality, min_kmer_quality, max_genomes
+        if mrq is not None:
+            self.filter_read_quality_flag = True
+        if mkq is not None:
+            self.filter_kmer_quality_flag = True
+        if mg is not None:
+            self.filter_max_genomes_flag = True
+        err = _check_align_args(self.kmer_reference, m, p, mrq, mkq, mg)
+        dropped = None
+        if mrq is not None and not isinstance(mrq, bool) and isinstance(mrq, (int, float)):
+            dropped = _dropped_mask(qual1, off1, mrq) | _dropped_mask(qual2, off2, mrq)
+        all_dropped = False
+        if err is not None:  # (as _align_columns: the arguments are checked only for what passes the read filter)
+            if dropped is None or not dropped.all():
+                raise err
+            all_dropped = True
+        self._add_ids(ids, dropped, False)  # (two mates' ids can collapse to one pair id: checked within the batch)
+        ref = self.kmer_reference
+        prm = None
+        if all_dropped:
+            self.filtered_quality_reads += n
+        else:
+            if self._result is None:
+                self._result = N.Result(ref.index)
+            prm = N.Params.make(m, p, mrq, mkq, mg)
+            ref.index.prepare(expected_reads=2 * n)
+            m1 = N.Reads.upload(seq1, qual1, off1, device=ref.index.device)
+            m2 = N.Reads.upload(seq2, qual2, off2, device=ref.index.device)
+            try:
+                N.align_pairs(ref.index, m1, m2, prm, self._next_index, self._result, lists=False)
+            finally:
+                m1.close()
+                m2.close()
+            stats, _, _, _ = self._result.fetch()
+            delta = stats - self._gpu_stats
+            self._gpu_stats = stats
+            self.filtered_quality_reads += int(delta[3])
+            self.filtered_quality_kmers += int(delta[4])
+            self.filtered_hr_kmers += int(delta[5])
+        b = _PairBatch(self._next_index, ids, (seq1, qual1, off1), (seq2, qual2, off2), prm, mrq, all_dropped)
+        b._dropped = dropped
+        self._batches.append(b)
+        if self._ids is not None:
+            self._ids.update(ids if dropped is None else (i for i, x in zip(ids, dropped) if not x))
+        self._next_index += n
+
     # -- results ----------------------------------------------------------------
 
     @property
@@ -883,9 +1006,7 @@ class PseudoAlignment:
                 continue
             if b.entries is None:
                 b.load()
-                reads = N.Reads.upload(b.seq, b.qual, b.off, device=ref.index.device)
-                types, _, _, loff, lists = N.align_reads(ref.index, reads, b.params)
-                reads.close()
+                types, loff, lists = b.results(ref.index)
                 names = [g.identifier for g in ref.genomes]
                 ent = []
                 for i, t in enumerate(types):
@@ -920,9 +1041,7 @@ class PseudoAlignment:
             if b.all_dropped:
                 fh.writelines(assignment_line(rid, _DROPPED, ()) for rid in b.ids)
                 continue
-            reads = N.Reads.upload(b.seq, b.qual, b.off, device=ref.index.device)
-            types, _, _, loff, lists = N.align_reads(ref.index, reads, b.params)
-            reads.close()
+            types, loff, lists = b.results(ref.index)
             loff = loff.astype(np.int64)
             fh.writelines(assignment_line(rid, int(types[i]), [names[int(g)] for g in lists[loff[i]:loff[i + 1]]])
                           for i, rid in enumerate(b.ids))

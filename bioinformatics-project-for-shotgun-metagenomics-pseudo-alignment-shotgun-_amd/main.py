@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Command-line interface, drop-in for the reference's src/main.py.
 
-    python3 main.py -t dumpalign -g GENOMES.fa -k 31 --reads READS.fq [-m M] [-p P]
+    python3 main.py -t dumpalign -g GENOMES.fa -k 31 --reads READS.fq [--reads2 MATES2.fq] [-m M] [-p P]
                     [--min-read-quality Q] [--min-kmer-quality QK] [--max-genomes MG]
                     [--filter-similar [--similarity-threshold T]]
                     [--coverage [--genomes a,b,c] [--min-coverage N] [--full-coverage]]
@@ -96,6 +96,11 @@ def _has_abundance_flag(argv: List[str]) -> bool:
     return False
 
 
+def _has_reads2_flag(argv: List[str]) -> bool:
+    """--reads2 on the command line (`--reads2 X`, `--reads2=X`)."""
+    return any(a.split("=", 1)[0] == "--reads2" for a in argv)
+
+
 def _early_reads_path(argv: List[str]) -> Optional[str]:
     """The --reads file of a `-t dumpalign` command line, read off argv before
     argparse and the heavy imports (every spelling argparse accepts: `-t X`,
@@ -130,6 +135,8 @@ def _early_reads_path(argv: List[str]) -> Optional[str]:
     if _has_variants_flag(argv):  # (and a pileup job: the base counts need the read columns)
         return None
     if _has_abundance_flag(argv):  # (and an abundance job: the candidate pass needs the read columns)
+        return None
+    if _has_reads2_flag(argv):  # (and a paired job: both files are parsed on the host)
         return None
     if os.environ.get("PA_GPUS", "1") not in ("", "0", "1"):  # (read-sharded over GPUs: no whole-file prefetch)
         return None
@@ -214,6 +221,9 @@ def parse_arguments(args: Optional[List[str]] = None) -> argparse.Namespace:
     parser.add_argument("-r", "--referencefile", help="KDB file (input/output)")
     parser.add_argument("-a", "--alignfile", help="aln file. Can be either input or name for output file")
     parser.add_argument("--reads", help="FASTQ reads file")
+    parser.add_argument("--reads2", default=None, metavar="FILE",
+                        help="FASTQ file of the second mates: record i of --reads and of --reads2 are one pair, "
+                             "classified as one fragment (paired data wants --both-strands)")
     parser.add_argument("-m", "--unique-threshold", help="unique k-mer threshold", type=int)
     parser.add_argument("-p", "--ambiguous-threhold", help="ambiguous k-mer threshold", type=int)
     parser.add_argument("--reverse-complement", action="store_true")  # parsed, unused (as in the reference)
@@ -351,6 +361,22 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
     return alignment
 
 
+def create_alignment_from_pairs(kmer_reference: KmerReference, reads_file: str, reads2_file: str, m: int, p: int,
+                                min_read_quality, min_kmer_quality, max_genomes) -> PseudoAlignment:
+    # a paired job: both files parsed on the host, one device, one entry per pair
+    FASTAQFile.check_extension(reads_file)
+    FASTAQFile.check_extension(reads2_file)
+    _stage("reference built")
+    alignment = PseudoAlignment(kmer_reference)
+    try:
+        alignment.align_pairs_from_containers(FASTAQFile(reads_file).container, FASTAQFile(reads2_file).container,
+                                              m, p, min_read_quality, min_kmer_quality, max_genomes)
+    except ValueError as err:  # (unequal record counts, a pair whose ids differ, the reference's argument errors)
+        sys.exit(f"Error: {err}")
+    _stage("pairs aligned")
+    return alignment
+
+
 def _print_json(obj) -> None:
     print(json.dumps(obj, indent=4))
 
@@ -371,6 +397,14 @@ def _check_task(args: argparse.Namespace) -> None:
     """Flag combinations (src/main.py:321-334), truthiness-based like the reference."""
     extra = (args.reads or args.alignfile or args.unique_threshold or args.ambiguous_threhold
              or args.min_read_quality or args.min_kmer_quality or args.max_genomes)
+    if args.reads2 is not None:
+        if not args.reads:
+            sys.exit("Error: --reads2 needs --reads (the first mates' file).")
+        if args.task not in ("align", "dumpalign"):
+            sys.exit("Error: --reads2 is only allowed for tasks 'align' and 'dumpalign'.")
+        if args.coverage or args.variants is not None or args.abundance is not None:
+            sys.exit("Error: --reads2 cannot be combined with --coverage, --variants or --abundance "
+                     "(those take single reads).")
     if not args.coverage and (args.genomes is not None or args.min_coverage is not None or args.full_coverage):
         sys.exit("Error: --genomes, --min-coverage and --full-coverage need --coverage.")
     if args.coverage:
@@ -513,10 +547,20 @@ def _run(args: argparse.Namespace) -> None:
             # (src/main.py:401), so the command ends with a traceback and exit
             # status 1 before any alignment is written -- reproduced, not fixed
             ref.save(args.referencefile)
+        if args.reads2 is not None:
+            validate_file_readable(args.reads2, "FASTQ second-mate reads")
+            create_alignment_from_pairs(ref, args.reads, args.reads2, *filt).save(args.alignfile)
+            return
         create_alignment_from_reference(ref, args.reads, *filt, per_read=True).save(args.alignfile)
     elif args.task == "dumpalign":
         if args.referencefile and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
+            if args.reads2 is not None:
+                validate_file_readable(args.reads2, "FASTQ second-mate reads")
+                ref = _load_reference(args.referencefile)
+                _check_strands(args, ref)
+                _print_alignment(create_alignment_from_pairs(ref, args.reads, args.reads2, *filt), args)
+                return
             host_parsed = (args.coverage or args.assignments is not None or args.variants is not None
                            or args.abundance is not None)
             pf = None if host_parsed else _prefetch_reads(args.reads)
@@ -531,6 +575,13 @@ def _run(args: argparse.Namespace) -> None:
         elif args.genomefile and args.kmer_size and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
             validate_file_readable(args.genomefile, "Genome FASTA")
+            if args.reads2 is not None:  # (a paired job runs on one device, both files parsed on the host)
+                validate_file_readable(args.reads2, "FASTQ second-mate reads")
+                ref = create_reference(args.genomefile, args.kmer_size, args.filter_similar,
+                                       args.similarity_threshold, reads_file=args.reads,
+                                       both_strands=args.both_strands)
+                _print_alignment(create_alignment_from_pairs(ref, args.reads, args.reads2, *filt), args)
+                return
             # (a coverage job runs on one device: the depth arrays of read shards are not reduced;
             # an assignments job too: its lines come from one host-parsed batch; a pileup job and an
             # abundance job, as coverage)

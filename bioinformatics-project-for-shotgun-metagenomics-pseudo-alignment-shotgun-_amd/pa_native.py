@@ -45,7 +45,7 @@ EXPORTS = (
     "pa_reads_download", "pa_reads_free",
     "pa_result_create", "pa_result_reset", "pa_result_fetch", "pa_result_device_view", "pa_result_copy_out",
     "pa_result_copy_in", "pa_result_load", "pa_result_free",
-    "pa_align", "pa_align_detail", "pa_align_reads", "pa_align_batch", "pa_align_fastq_file", "pa_align_fastq_range",
+    "pa_align", "pa_align_detail", "pa_align_reads", "pa_align_pairs", "pa_align_batch", "pa_align_fastq_file", "pa_align_fastq_range",
     "pa_idsets_disjoint", "pa_idset_free",
     "pa_fastq_prefetch_start", "pa_align_fastq_prefetched", "pa_fastq_prefetch_free",
     "pa_comm_unique_id", "pa_comm_init", "pa_comm_free", "pa_comm_count", "pa_counters_reduce",
@@ -189,6 +189,8 @@ def lib():
         "pa_coverage_create": (I32, [P, PP]),
         "pa_coverage_reset": (I32, [P, P]),
         "pa_align_reads": (I32, [P, P, ctypes.POINTER(Params), P, P, P, P, P, U64, ctypes.POINTER(U64), P]),
+        "pa_align_pairs": (I32, [P, P, P, ctypes.POINTER(Params), U64, P, P, P, P, P, P, U64, ctypes.POINTER(U64),
+                                 ctypes.POINTER(U64), P]),
         "pa_coverage_add": (I32, [P, P, ctypes.POINTER(Params), P, P]),
         "pa_coverage_summary": (I32, [P, U32, P, P, P, P, P]),
         "pa_coverage_depth": (I32, [P, U32, U64, U64, P, P, P]),
@@ -1005,6 +1007,46 @@ def align_reads(index: Index, reads: Reads, params: Params, stream=None):
     if lists is None:
         lists = np.zeros(0, dtype=np.uint32)
     return types, qf, hr, off, lists[:total]
+
+
+def align_pairs_call(index: Index, mates1: Reads, mates2: Reads, params: Params, list_cap: int, base: int = 0,
+                     result: Optional[Result] = None, lists: bool = True, stream=None):
+    """One pa_align_pairs call with room for `list_cap` list entries: (status,
+    types, qf, hr, list offsets, lists, list_total, exact_pairs).  With `lists`
+    and list_total > list_cap the status is PA_EINVAL, everything but the lists
+    is valid and `result` is untouched.  Without `lists` no list buffer is
+    passed (the counters of `result` need none)."""
+    n = mates1.n
+    types = np.zeros(max(n, 1), dtype=np.uint8)
+    qf = np.zeros(max(n, 1), dtype=np.uint32)
+    hr = np.zeros(max(n, 1), dtype=np.uint32)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    buf = np.zeros(max(int(list_cap), 1), dtype=np.uint32) if lists else None
+    total, exact = U64(0), U64(0)
+    st = lib().pa_align_pairs(index.handle, mates1.handle, mates2.handle, ctypes.byref(params), int(base),
+                              result.handle if result is not None else None, _ptr(types), _ptr(qf), _ptr(hr),
+                              _ptr(off), _ptr(buf), int(list_cap) if lists else 0, ctypes.byref(total),
+                              ctypes.byref(exact), _stream(stream))
+    return st, types[:n], qf[:n], hr[:n], off, buf, int(total.value), int(exact.value)
+
+
+def align_pairs(index: Index, mates1: Reads, mates2: Reads, params: Params, base: int = 0,
+                result: Optional[Result] = None, lists: bool = True, stream=None):
+    """pa_align_pairs: mate i of the two batches is one fragment, classified by
+    both mates' k-mers together.  Returns (types, qf, hr,
+    list offsets, lists, exact_pairs) per pair, as align_reads does per read;
+    `result` gets the pair counters at pair index `base` + i.  The first call
+    has room for one list entry per pair; a batch with longer lists is run once
+    more with the capacity the first call reported (`result` is only added to
+    by the call that succeeds)."""
+    st, types, qf, hr, off, buf, total, exact = align_pairs_call(index, mates1, mates2, params, mates1.n, base,
+                                                                 result, lists, stream)
+    if lists and st == PA_EINVAL and total > mates1.n:
+        st, types, qf, hr, off, buf, total, exact = align_pairs_call(index, mates1, mates2, params, total, base,
+                                                                     result, lists, stream)
+    _check(st)
+    out = buf[:total] if buf is not None else np.zeros(0, dtype=np.uint32)
+    return types, qf, hr, off, out, exact
 
 
 def align_placements(index: Index, reads: Reads, params: Params, stream=None):

@@ -30,6 +30,9 @@
  *                            write the reads they settle, the exact kernel the
  *                            rest (PseudoAlignment.reads, --assignments)    src/kmer.py:542, 551-561
  *   pa_result_fetch          PseudoAlignment.get_summary inputs             src/kmer.py:622-657
+ *   pa_align_pairs           paired-end reads: a pair classified as one fragment by the union of both
+ *                            mates' k-mers (--reads2); no reference counterpart: the definition is
+ *                            DESIGN.md section 15 (the decision is src/kmer.py:444-480 unchanged)
  *   pa_coverage_* /          the course project's EXTCOVERAGE extension (--coverage, --genomes,
  *   pa_align_placements      --min-coverage, --full-coverage), which the reference leaves out: it
  *                            has no coverage code, so the definition is DESIGN.md section 10; the
@@ -345,6 +348,28 @@ pa_status pa_align_reads(const pa_index *idx, const pa_reads *reads, const pa_pa
                          uint8_t *read_type, uint32_t *filtered_kmers /*nullable*/,
                          uint32_t *redundant_kmers /*nullable*/, uint64_t *list_off,
                          uint32_t *lists, uint64_t list_cap, uint64_t *list_total, void *stream);
+
+/* Pairs: mate i of mates1 and mate i of mates2 are one fragment:
+ * the pair is classified by the union of both mates' retained k-mers, mate 1's
+ * first; no window spans the mates; with min_read_quality a pair is dropped when
+ * either mate is.  Per-pair outputs as pa_align_reads gives them per read; acc
+ * (nullable) gets the pair counters (first_key = (pair_index_base + i) << 20 |
+ * list position), only when the call returns PA_OK.  Any of pair_type / counters
+ * may be NULL when only acc is wanted; list_off and lists may then be NULL too.
+ * If lists were asked for and list_cap is too small the call returns PA_EINVAL
+ * with *list_total, pair_type and list_off valid and acc untouched: the caller
+ * retries.  PA_EINVAL when the batches differ in read count or device;
+ * PA_EUNSUPPORTED above 2^32 - 2 pairs; PA_EINTERNAL when a pair was settled by
+ * no kernel.  *exact_pairs (nullable): pairs the pair-exact kernel classified;
+ * the others followed from their mates' results (an unmapped or dropped mate, two
+ * ambiguous mates without a specific k-mer).  PA_PAIR_COMBINE=0 in the
+ * environment sends every pair that is not dropped to the pair-exact kernel (A/B
+ * runs, a fallback); the results are the same. */
+pa_status pa_align_pairs(const pa_index *idx, const pa_reads *mates1, const pa_reads *mates2,
+                         const pa_params *params, uint64_t pair_index_base, pa_result *acc,
+                         uint8_t *pair_type, uint32_t *filtered_kmers, uint32_t *redundant_kmers,
+                         uint64_t *list_off, uint32_t *lists, uint64_t list_cap, uint64_t *list_total,
+                         uint64_t *exact_pairs, void *stream);
 /* ---- coverage: where on a genome its reads fall ----------
  *
  * Every read is classified as pa_align_detail classifies it with the same

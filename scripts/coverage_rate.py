@@ -44,6 +44,15 @@ interning.  It adds the align kernels' own times over one profiled add, the
 accumulator's info (reads by type, classes) and pa_abundance_estimate for 200
 iterations (tolerance 0) and with the default tolerance.
 
+--mode pairs times pa_align_pairs on a both-strand C2
+index: --reads pairs (default 1 000 000) made on the host -- fragments of 300 ..
+500 bases, mates of 150, mate 2 the reverse complement of the fragment's last
+150, --read-err substitutions -- and uploaded as two batches.  Next to it the
+same call under PA_PAIR_COMBINE=0 (every pair to the pair-exact kernel),
+pa_align_reads over mates 1 plus over mates 2 (the mates' pass the call rides
+on), pa_align_detail with its lists over the 2 N mates, and the call without a
+result (the difference is k_pair_count and the fetch-free counter pass).
+
 --read-err / --rc-rate / --foreign-rate give bench.py's c2mix reads (0.015, 0.2, 0.2).
 """
 
@@ -117,10 +126,85 @@ def time_assign(index, reads, prm, runs):
     return med, ts, int(total.value)
 
 
+def make_pairs(genomes, n, read_len, err, seed, chunk=250_000):
+    """Two uploaded batches of n mates: fragments of 300 .. 500 bases drawn uniformly
+    (genome, then start), mate 1 the first read_len bases, mate 2 the reverse
+    complement of the last read_len; `err` substitutions per base; an N of the
+    genome becomes a random base; qualities as synth.sample_reads draws them."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    lens = np.array([len(g) for g in genomes], dtype=np.int64)
+    parts = ([], [], [], [])
+    col = np.arange(read_len)[None, :]
+    for lo in range(0, n, chunk):
+        m = min(chunk, n - lo)
+        origin = rng.integers(0, len(genomes), size=m)
+        flen = rng.integers(300, 501, size=m)
+        starts = (rng.random(m) * (lens[origin] - flen + 1)).astype(np.int64)
+        s1 = np.empty((m, read_len), dtype=np.uint8)
+        s2 = np.empty((m, read_len), dtype=np.uint8)
+        for g in np.unique(origin):
+            rows = np.flatnonzero(origin == g)
+            s1[rows] = genomes[g][starts[rows, None] + col]
+            s2[rows] = genomes[g][(starts[rows] + flen[rows] - read_len)[:, None] + col]
+        s2 = synth.reverse_complement(s2)
+        for s in (s1, s2):
+            nmask = s == ord("N")
+            if nmask.any():
+                s[nmask] = synth.ACGT[rng.integers(0, 4, size=int(nmask.sum()))]
+            if err > 0:
+                emask = rng.random(s.shape) < err
+                ne = int(emask.sum())
+                if ne:
+                    s[emask] = synth.ACGT[(np.searchsorted(synth.ACGT, s[emask]) + rng.integers(1, 4, size=ne)) % 4]
+        for dst, s in ((0, s1), (2, s2)):
+            parts[dst].append(np.ascontiguousarray(s).reshape(-1))
+            q = np.clip(np.rint(rng.normal(60.0, 8.0, size=s.shape)), 35, 74).astype(np.uint8)
+            parts[dst + 1].append(q.reshape(-1))
+    off = np.arange(n + 1, dtype=np.uint64) * np.uint64(read_len)
+    return (N.Reads.upload(np.concatenate(parts[0]), np.concatenate(parts[1]), off),
+            N.Reads.upload(np.concatenate(parts[2]), np.concatenate(parts[3]), off))
+
+
+def run_pairs(args, genomes, out):
+    index = N.Index(genomes, 31, both_strands=True)
+    index.prepare()
+    m1, m2 = make_pairs(genomes, args.reads, 150, args.read_err, seed=2)
+    prm = N.Params.make()
+    n = args.reads
+    res = N.Result(index)
+    holder = {}
+
+    def pairs(result):
+        holder["r"] = N.align_pairs(index, m1, m2, prm, 0, result)
+    os.environ.pop("PA_PAIR_COMBINE", None)
+    med, ts = timed(lambda: pairs(res), args.runs)
+    exact = int(holder["r"][5])
+    types = holder["r"][0]
+    out.update(align_pairs_s=med, align_pairs_runs_s=ts, pairs_per_s=n / med, exact_pairs=exact,
+               exact_pairs_share=exact / n, list_entries=int(holder["r"][4].size),
+               pair_types={name: int((types == t).sum()) for t, name in
+                           ((2, "unique"), (3, "ambiguous"), (1, "unmapped"), (0, "dropped"))})
+    med, ts = timed(lambda: pairs(None), args.runs)
+    out.update(align_pairs_no_result_s=med, pair_count_s=out["align_pairs_s"] - med)
+    os.environ["PA_PAIR_COMBINE"] = "0"
+    med, ts = timed(lambda: pairs(res), args.runs)
+    out.update(align_pairs_exact_only_s=med, align_pairs_exact_only_runs_s=ts,
+               exact_pairs_exact_only=int(holder["r"][5]))
+    del os.environ["PA_PAIR_COMBINE"]
+    a1, _, e1 = time_assign(index, m1, prm, args.runs)
+    a2, _, e2 = time_assign(index, m2, prm, args.runs)
+    out.update(mates_assign_s=a1 + a2, mates_assign_each_s=[a1, a2], mates_list_entries=e1 + e2)
+    d1, _, _ = time_detail(index, m1, prm, args.runs)
+    d2, _, _ = time_detail(index, m2, prm, args.runs)
+    out.update(mates_detail_s=d1 + d2, ratio_pairs_over_mates_assign=out["align_pairs_s"] / (a1 + a2))
+    out["workload"] = (f"C2 both-strand index ({args.genomes} x {args.genome_len} bp, k=31), {n} pairs of 2 x 150 bp, "
+                       "fragments of 300..500 bp, mate 2 reverse-complemented")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("detail", "coverage", "assign", "pileup", "abundance"), required=True)
-    ap.add_argument("--reads", type=int, default=10_000_000)
+    ap.add_argument("--mode", choices=("detail", "coverage", "assign", "pileup", "abundance", "pairs"), required=True)
+    ap.add_argument("--reads", type=int, default=None, help="reads (default 10 000 000); pairs with --mode pairs (1 000 000)")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--genomes", type=int, default=50)
     ap.add_argument("--genome-len", type=int, default=2_000_000)
@@ -129,8 +213,16 @@ def main():
     ap.add_argument("--foreign-rate", type=float, default=0.0)
     ap.add_argument("--baseline-json", default=None, help="the line of a --mode detail run on the parent's library")
     args = ap.parse_args()
+    if args.reads is None:
+        args.reads = 1_000_000 if args.mode == "pairs" else 10_000_000
     genomes = synth.family_genomes(args.genomes, args.genome_len, seed=1, family_size=5, sub_rate=0.01,
                                    conserved_len=5000, n_rate=1e-4, n_run=10)
+    if args.mode == "pairs":
+        out = {"read_mix": {"err": args.read_err}, "mode": args.mode, "runs": args.runs,
+               "library": N.lib().pa_version().decode()}
+        run_pairs(args, genomes, out)
+        print(json.dumps(out), flush=True)
+        return
     index = N.Index(genomes, 31)
     index.prepare()
     reads = N.Reads.synthesize(index, args.reads, 150, first_read=0, seed=2, sub_rate=args.read_err,

@@ -1,0 +1,402 @@
+"""Paired-end reads on the host: the model the GPU tests
+compare the device with, checked against the unchanged CPU oracle; the pure
+pair_identifier; the NULL-index check of pa_align_pairs; the --reads2 flag
+checks (main.py in a child process, no device needed).
+
+The model is plain Python over the genome texts, written from rules 1-4 of
+section 15: a dict from k-mer to genome set (both strands: over g + "N" +
+rc(g)), the dropped test on either mate, the windows of mate 1 and then of mate
+2 into one dict keyed by the k-mer, and the reference's decision
+(src/kmer.py:444-480) on that dict.  Nothing from libpa feeds it.
+
+Its own check is the equivalent form of section 15: for a pair that is not
+dropped, type, list and redundant_kmers are the oracle's for the single read
+mate1 + "N" + mate2 without --min-read-quality (no window over the N is in the
+index), and filtered_kmers is the sum of the oracle's for the two mates aligned
+on their own (the joined read would count windows across the join).
+"""
+
+import functools
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import pa_oracle as O
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "bioinformatics-project-for-shotgun-metagenomics-pseudo-alignment-shotgun-_amd")
+MAIN = os.path.join(PKG, "main.py")
+GOLD = os.path.join(REPO, "tests", "golden")
+FA, FQ = os.path.join(GOLD, "config1.fa"), os.path.join(GOLD, "config1.fq")
+
+DROPPED, UNMAPPED, UNIQUE, AMBIGUOUS = 0, 1, 2, 3
+NO_KEY = 2 ** 64 - 1
+_COMP = str.maketrans("ACGTN", "TGCAN")
+
+
+# ---- the model --------------------------------------------------------------------------------
+
+def reverse_complement(s):
+    return s.translate(_COMP)[::-1]
+
+
+def regions_of(genomes, both):
+    return [g + "N" + reverse_complement(g) if both and g else g for g in genomes]
+
+
+def kmer_sets(genomes, both, k):
+    """{k-mer: ascending tuple of the genomes holding it}; windows with an N are not indexed."""
+    d = {}
+    for g, t in enumerate(regions_of(genomes, both)):
+        for j in range(len(t) - k + 1):
+            w = t[j:j + k]
+            if "N" not in w:
+                d.setdefault(w, set()).add(g)
+    return {w: tuple(sorted(s)) for w, s in d.items()}
+
+
+def _mean_below(q, lo, hi, threshold):
+    return sum(q[lo:hi]) < threshold * (hi - lo)  # the integer form of mean < threshold
+
+
+def pair_model(kmer_dict, k, mate1, q1, mate2, q2, m=1, p=1, mrq=None, mkq=None, mg=None):
+    """(type, genomes_mapped_to, filtered_kmers, redundant_kmers, p-demoted) of one pair."""
+    mates = [(mate1, [ord(c) for c in q1]), (mate2, [ord(c) for c in q2])]
+    # rule 1: dropped when either mate's mean quality is below the threshold
+    if mrq is not None and any(_mean_below(q, 0, len(q), mrq) for _, q in mates):
+        return DROPPED, [], 0, 0, False
+    # rule 2: the windows of mate 1, then of mate 2, into one dict keyed by the k-mer
+    kmers, qf, hr = {}, 0, 0
+    for seq, q in mates:
+        for j in range(len(seq) - k + 1):
+            if mkq is not None and _mean_below(q, j, j + k, mkq):
+                qf += 1
+                continue
+            s = kmer_dict.get(seq[j:j + k])
+            if s:
+                if mg is not None and len(s) > mg:
+                    hr += 1
+                    continue
+                kmers.setdefault(seq[j:j + k], s)
+    if not kmers:
+        return UNMAPPED, [], qf, hr, False
+    # rule 3: try_to_align_specific(m), validate_unique_mappings(p)
+    spec, tot = {}, {}
+    for s in kmers.values():
+        if len(s) == 1:
+            spec[s[0]] = spec.get(s[0], 0) + 1
+        for g in s:
+            tot[g] = tot.get(g, 0) + 1
+    top = None
+    if len(spec) == 1:
+        top = next(iter(spec))
+    elif len(spec) > 1:
+        order = sorted(spec, key=spec.get, reverse=True)  # (stable: the first inserted of equal counts)
+        if spec[order[0]] >= spec[order[1]] + m:
+            top = order[0]
+    if top is None:
+        return AMBIGUOUS, list(spec), qf, hr, False
+    if p >= 0 and max(tot.values()) - tot[top] > p:
+        return AMBIGUOUS, [top] + [g for g, c in tot.items() if c >= tot[top]], qf, hr, True
+    return UNIQUE, [top], qf, hr, False
+
+
+def model_all(kmer_dict, k, pairs, **ps):
+    """pairs: [(mate1, q1, mate2, q2)]."""
+    return [pair_model(kmer_dict, k, *pr, **ps) for pr in pairs]
+
+
+def accumulate(results, G, base=0):
+    """(stats [6], unique [G], ambiguous [G], first_key [G]) of a batch of pairs at pair index base + i."""
+    stats, uq, am, fk = [0] * 6, [0] * G, [0] * G, [NO_KEY] * G
+    for i, (t, lst, qf, hr, _) in enumerate(results):
+        if t == DROPPED:
+            stats[3] += 1
+            continue
+        stats[{UNIQUE: 0, AMBIGUOUS: 1, UNMAPPED: 2}[t]] += 1
+        stats[4] += qf
+        stats[5] += hr
+        for pos, g in enumerate(lst):
+            (uq if t == UNIQUE else am)[g] += 1
+            fk[g] = min(fk[g], ((base + i) << 20) | pos)
+    return stats, uq, am, fk
+
+
+def summary_of(results, names, mrq=None, mkq=None, mg=None, **_):
+    """get_summary of a paired job, by walking the pairs in order (as pa_oracle.summary_by_walk walks reads)."""
+    stats, _, _, _ = accumulate(results, len(names))
+    st = {"unique_mapped_reads": stats[0], "ambiguous_mapped_reads": stats[1], "unmapped_reads": stats[2]}
+    if mrq is not None:
+        st["filtered_quality_reads"] = stats[3]
+    if mkq is not None:
+        st["filtered_quality_kmers"] = stats[4]
+    if mg is not None:
+        st["filtered_hr_kmers"] = stats[5]
+    genomes = {}
+    for t, lst, _, _, _ in results:
+        if t in (UNIQUE, AMBIGUOUS):
+            for g in lst:
+                genomes.setdefault(names[g], {"unique_reads": 0, "ambiguous_reads": 0})[
+                    "unique_reads" if t == UNIQUE else "ambiguous_reads"] += 1
+    return {"Statistics": st, "Summary": genomes}
+
+
+# ---- the model's own check: the oracle in the equivalent form ---------------------------------
+
+def oracle_check(genomes, both, k, pairs, results, ps):
+    """Every pair of `results` (the model's) against the unchanged CPU oracle."""
+    idx = O.OracleIndex(regions_of(genomes, both), k)
+    no_mrq = {n: v for n, v in ps.items() if n != "mrq"}
+
+    def run(seqs, quals, **kw):
+        seq, off = O.concat(seqs)
+        qual, _ = O.concat(quals)
+        return idx.align(seq, qual, off, **kw)
+    joined = run([a + "N" + b for a, _, b, _ in pairs], [qa + "I" + qb for _, qa, _, qb in pairs], **no_mrq)
+    m1 = run([pr[0] for pr in pairs], [pr[1] for pr in pairs], **ps)
+    m2 = run([pr[2] for pr in pairs], [pr[3] for pr in pairs], **ps)
+    for i, (t, lst, qf, hr, _) in enumerate(results):
+        if m1.types[i] == DROPPED or m2.types[i] == DROPPED:
+            assert (t, lst, qf, hr) == (DROPPED, [], 0, 0), i
+            continue
+        assert t == joined.types[i], i
+        assert lst == joined.genomes_of(i), i
+        assert hr == joined.hr[i], i
+        assert qf == int(m1.qf[i]) + int(m2.qf[i]), i
+    return m1, m2
+
+
+# ---- the hand-built pairs ---------------------------------------------------------------------
+
+def rand_dna(rng, n):
+    return "".join("ACGT"[i] for i in rng.integers(0, 4, n))
+
+
+def mutate(rng, seq, rate):
+    s = list(seq)
+    for i in np.flatnonzero(rng.random(len(s)) < rate):
+        s[i] = "ACGT"[("ACGT".index(s[i]) + int(rng.integers(1, 4))) % 4]
+    return "".join(s)
+
+
+HAND_PS = dict(m=1, p=1, mrq=50)
+HAND_KS = [31, 63, 97]  # one key word (lane path), two words, four words (no lane path: the mates' pass is all exact)
+
+
+@functools.lru_cache(maxsize=None)
+def hand_case(k):
+    """Three genomes g, h, j: S3 in all three, S12 in h and j only; the rest private.
+    Returns (genomes, names, [(pair name, mate1, q1, mate2, q2)])."""
+    rng = np.random.default_rng(700 + k)
+    S3, S12 = rand_dna(rng, 2 * k + 60), rand_dna(rng, 2 * k + 40)
+    pg, ph, pj = rand_dna(rng, 900), rand_dna(rng, 900), rand_dna(rng, 600)
+    g = pg[:450] + S3 + pg[450:]
+    h = ph[:450] + S3 + ph[450:] + S12
+    j = pj[:300] + S3 + pj[300:] + S12 + rand_dna(rng, 60)
+
+    def other(*used):  # a base that extends neither neighbour's match
+        return next(b for b in "ACGT" if b not in used)
+    a, b, c = 100, 60, 300  # Gs = pg[a : a + k + 1] (two k-mers of g), H1 = ph[b : b + k], H2 = ph[c : c + k]
+    Gs, H1, H2 = pg[a:a + k + 1], ph[b:b + k], ph[c:c + k]
+    mate1 = H1 + other(ph[b + k], pg[a - 1]) + Gs
+    mate2 = Gs + other(pg[a + k + 1], ph[c - 1]) + H2
+    foreign1, foreign2 = rand_dna(rng, k + 40), rand_dna(rng, k + 25)
+    in_g = pg[500:500 + k + 30]
+    pairs = [
+        ("shared_kmers", mate1, mate2),           # each mate UNIQUE [g]; the pair AMBIGUOUS [h, g]
+        ("swapped", mate2, mate1),                # AMBIGUOUS [g, h]
+        ("mate2_foreign", mate1, foreign1),       # mate 1's result
+        ("mate1_foreign", foreign1, in_g),        # mate 2's result
+        ("both_foreign", foreign1, foreign2),     # unmapped
+        ("both_shared", S3[0:k + 30], S3[20:k + 55]),  # ambiguous, empty list
+        ("mate2_short", in_g, pg[600:600 + k - 1]),
+        ("mate2_exactly_k", in_g, ph[700:700 + k]),
+        ("lengths_differ", pg[200:200 + k + 5], pg[460:460 + 2 * k + 40]),
+        ("with_n", in_g[:k + 3] + "N" + in_g[k + 4:], pg[250:250 + k + 10]),
+        ("dropped_by_mate2", in_g, pg[620:620 + k + 20]),
+        # mate 1: 3 k-mers specific to g; mate 2: 11 k-mers of {h, j}
+        ("p_demoted", pg[10:10 + k + 2], S12[0:k + 10]),
+        ("both_unique_same", pg[700:700 + k + 20], pg[760:760 + k + 20]),
+        ("unique_and_shared", in_g, S3[5:k + 25]),
+    ]
+    out = [(n, s1, "I" * len(s1), s2, ("#" if n == "dropped_by_mate2" else "I") * len(s2)) for n, s1, s2 in pairs]
+    return [g, h, j], ["g", "h", "j"], out
+
+
+@pytest.mark.parametrize("both", [False, True], ids=["forward", "both_strands"])
+@pytest.mark.parametrize("k", HAND_KS)
+def test_hand_built_model(k, both):
+    genomes, _, named = hand_case(k)
+    pairs = [pr[1:] for pr in named]
+    res = model_all(kmer_sets(genomes, both, k), k, pairs, **HAND_PS)
+    m1, m2 = oracle_check(genomes, both, k, pairs, res, HAND_PS)
+    got = {pr[0]: (r[0], r[1]) for pr, r in zip(named, res)}
+    i = {pr[0]: n for n, pr in enumerate(named)}
+    G, H, J = 0, 1, 2
+    # the shared k-mers count once, first appearance is ordered mate 1 first, no "both unique" shortcut
+    for n in ("shared_kmers", "swapped"):
+        assert (m1.types[i[n]], m1.genomes_of(i[n])) == (UNIQUE, [G])
+        assert (m2.types[i[n]], m2.genomes_of(i[n])) == (UNIQUE, [G])
+    assert got["shared_kmers"] == (AMBIGUOUS, [H, G])
+    assert got["swapped"] == (AMBIGUOUS, [G, H])
+    assert got["mate2_foreign"] == (UNIQUE, [G]) and m2.types[i["mate2_foreign"]] == UNMAPPED
+    assert got["mate1_foreign"] == (UNIQUE, [G]) and m1.types[i["mate1_foreign"]] == UNMAPPED
+    assert got["both_foreign"] == (UNMAPPED, [])
+    assert got["both_shared"] == (AMBIGUOUS, [])
+    assert got["mate2_short"] == (UNIQUE, [G])
+    assert got["mate2_exactly_k"] == (UNIQUE, [G]) and m2.types[i["mate2_exactly_k"]] == UNIQUE
+    assert got["lengths_differ"] == (UNIQUE, [G])
+    assert got["with_n"] == (UNIQUE, [G])
+    assert got["dropped_by_mate2"] == (DROPPED, [])
+    assert m1.types[i["dropped_by_mate2"]] == UNIQUE and m2.types[i["dropped_by_mate2"]] == DROPPED
+    assert got["p_demoted"] == (AMBIGUOUS, [G, G, H, J]) and res[i["p_demoted"]][4]
+    assert sum(r[4] for r in res) == 1
+    assert got["both_unique_same"] == (UNIQUE, [G])
+    assert got["unique_and_shared"] == (UNIQUE, [G])
+
+
+# ---- the random pairs -------------------------------------------------------------------------
+
+RAND_SEED = 7
+RAND_N = 2000
+RAND_SHAPES = {31: 100, 63: 150}  # k: mate length
+RAND_PS = [dict(m=1, p=1), dict(m=2, p=0), dict(m=1, p=1, mg=2), dict(m=1, p=1, mkq=52),
+           dict(m=3, p=2, mrq=52, mkq=50, mg=3)]
+
+
+@functools.lru_cache(maxsize=None)
+def rand_genomes():
+    """Four genomes: 400 private bases, a 3 % substituted copy of one 3000-base text, 400 private bases."""
+    rng = np.random.default_rng(RAND_SEED)
+    text = rand_dna(rng, 3000)
+    return [rand_dna(rng, 400) + mutate(rng, text, 0.03) + rand_dna(rng, 400) for _ in range(4)]
+
+
+@functools.lru_cache(maxsize=None)
+def rand_pairs(k):
+    """RAND_N pairs [(mate1, q1, mate2, q2)]: the two ends (both forward) of a fragment of L + 20 ..
+    3 L + 99 bases, 1 % substitutions, qualities uniform in 33..73; 10 % with mate 2 from another
+    random place of any genome, 10 % with a foreign mate 2, 5 % both foreign, 3 % with mate 2 cut to k - 1."""
+    L = RAND_SHAPES[k]
+    rng = np.random.default_rng(RAND_SEED + k)
+    genomes = rand_genomes()
+    out = []
+    for _ in range(RAND_N):
+        g = genomes[int(rng.integers(0, 4))]
+        flen = int(rng.integers(L + 20, 3 * L + 100))
+        a = int(rng.integers(0, len(g) - flen + 1))
+        s1, s2 = g[a:a + L], g[a + flen - L:a + flen]
+        u = rng.random()
+        if u < 0.10:
+            h = genomes[int(rng.integers(0, 4))]
+            b = int(rng.integers(0, len(h) - L + 1))
+            s2 = h[b:b + L]
+        elif u < 0.20:
+            s2 = rand_dna(rng, L)
+        elif u < 0.25:
+            s1, s2 = rand_dna(rng, L), rand_dna(rng, L)
+        s1, s2 = mutate(rng, s1, 0.01), mutate(rng, s2, 0.01)
+        if 0.25 <= u < 0.28:
+            s2 = s2[:k - 1]
+        q1 = bytes(rng.integers(33, 74, len(s1), dtype=np.uint8)).decode()
+        q2 = bytes(rng.integers(33, 74, len(s2), dtype=np.uint8)).decode()
+        out.append((s1, q1, s2, q2))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def rand_kd(k, both):
+    return kmer_sets(rand_genomes(), both, k)
+
+
+@functools.lru_cache(maxsize=None)
+def rand_model(k, both, i):
+    """The model's results of the random set under RAND_PS[i], oracle-checked; with the mates' own oracle results."""
+    pairs = rand_pairs(k)
+    res = model_all(rand_kd(k, both), k, pairs, **RAND_PS[i])
+    m1, m2 = oracle_check(rand_genomes(), both, k, pairs, res, RAND_PS[i])
+    return res, m1, m2
+
+
+def rand_conditions(k, both):
+    """What keeps the random test from being vacuous.  The first three are asked of k = 31, (m=1, p=1): at
+    k = 63 a window of four 3 % divergent copies is almost never shared (0.97^126 = 2 % for two of them),
+    so nearly every k-mer is specific and a p-demotion, which needs shared k-mers, is rare by construction;
+    the figures are printed for both."""
+    res, m1, _ = rand_model(k, both, 0)
+    differs = sum((r[0], r[1]) != (int(m1.types[i]), m1.genomes_of(i)) for i, r in enumerate(res))
+    long_amb = sum(r[0] == AMBIGUOUS and len(r[1]) >= 2 for r in res)
+    demoted = sum(r[4] for r in res)
+    last, _, _ = rand_model(k, both, len(RAND_PS) - 1)
+    dropped = sum(r[0] == DROPPED for r in last)
+    print(f"k={k} both={both}: differs from mate 1 {differs}, ambiguous with >= 2 entries {long_amb}, "
+          f"p-demoted {demoted}, dropped / kept under the last set {dropped} / {len(last) - dropped}")
+    if k == 31:
+        assert differs >= 60
+        assert long_amb >= 10
+        assert demoted >= 10
+    assert dropped >= 100 and len(last) - dropped >= 100
+
+
+@pytest.mark.parametrize("both", [False, True], ids=["forward", "both_strands"])
+@pytest.mark.parametrize("k", sorted(RAND_SHAPES))
+def test_random_model_vs_oracle(k, both):
+    for i in range(len(RAND_PS)):
+        rand_model(k, both, i)
+    rand_conditions(k, both)
+
+
+# ---- pair_identifier --------------------------------------------------------------------------
+
+@pytest.mark.parametrize("ids, want", [(("r1/1", "r1/2"), "r1"), (("r1 1:N:0", "r1 2:N:0"), "r1"),
+                                       (("r1", "r1"), "r1")])
+def test_pair_identifier(ids, want):
+    from kmer import pair_identifier
+    assert pair_identifier(*ids) == want
+
+
+@pytest.mark.parametrize("ids", [("a/1", "b/2"), ("r/2", "r/1")])  # (only the mate's own suffix is removed)
+def test_pair_identifier_mismatch(ids):
+    from kmer import pair_identifier
+    with pytest.raises(ValueError) as e:
+        pair_identifier(*ids)
+    assert ids[0] in str(e.value) and ids[1] in str(e.value)
+
+
+# ---- the C entry point's handle check (before any HIP call) -----------------------------------
+
+def test_align_pairs_null_index_is_einval():
+    import ctypes
+
+    import pa_native as N
+    L = N.lib()
+    dummy = ctypes.create_string_buffer(64)  # (mates not NULL, and never read: the index is looked at first)
+    st = L.pa_align_pairs(None, ctypes.addressof(dummy), ctypes.addressof(dummy), ctypes.byref(N.Params.make()), 0,
+                          None, None, None, None, None, None, 0, ctypes.byref(N.U64()), None, None)
+    assert st == N.PA_EINVAL
+    assert L.pa_last_error() == b"NULL argument"
+
+
+# ---- the --reads2 flag checks that need no device ---------------------------------------------
+
+def run_main(argv):
+    return subprocess.run([sys.executable, MAIN] + argv, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                          timeout=300)
+
+
+@pytest.mark.parametrize("argv, message", [
+    (["-t", "dumpalign", "-g", FA, "-k", "21", "--reads2", FQ], "Error: --reads2 needs --reads"),
+    (["-t", "dumpref", "-g", FA, "-k", "21", "--reads", FQ, "--reads2", FQ],
+     "Error: --reads2 is only allowed for tasks 'align' and 'dumpalign'."),
+    (["-t", "reference", "-g", FA, "-k", "21", "-r", "x.kdb", "--reads", FQ, "--reads2", FQ],
+     "Error: --reads2 is only allowed for tasks 'align' and 'dumpalign'."),
+    (["-t", "dumpalign", "-g", FA, "-k", "21", "--reads", FQ, "--reads2", FQ, "--coverage"],
+     "Error: --reads2 cannot be combined with --coverage, --variants or --abundance"),
+], ids=["without_reads", "dumpref", "reference", "coverage"])
+def test_cli_reads2_misuse(argv, message):
+    r = run_main(argv)
+    assert r.returncode != 0 and r.stdout == ""
+    assert message in r.stderr
