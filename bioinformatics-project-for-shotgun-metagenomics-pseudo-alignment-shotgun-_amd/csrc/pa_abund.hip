@@ -17,10 +17,15 @@
 //              class transpose (classes ascending), a one-block max reduction
 //              for the delta: double precision, no floating-point atomics,
 //              every sum in a fixed order.
+//   bootstrap   B resamples of the reads over their
+//              classes, draw by draw in integers (k_boot_draw, a grid strip per
+//              replicate), then the same EM on every resample, a workgroup per
+//              replicate and the whole loop in one launch (k_boot_em).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <new>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -244,6 +249,127 @@ __global__ __launch_bounds__(kBlock) void k_em_delta(const double *__restrict__ 
     if (threadIdx.x == 0) *out = red[0];
 }
 
+// ---- the bootstrap --------------------------------------
+
+constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
+// cum and the block's histogram are kept in LDS up to this many classes:
+// (4096 + 1) * 8 + 4096 * 4 bytes = 48 KB + 8, dynamic, sized by the classes held.
+constexpr uint32_t kBootLdsClasses = 4096;
+constexpr uint64_t kBootBlockDraws = 1ull << 31;  // a block's draws at most: its uint32 histogram cannot wrap
+
+inline size_t boot_lds_bytes(uint32_t nc) { return ((size_t)nc + 1) * 8 + (size_t)nc * 4; }
+
+// Replicate blockIdx.y, draws blockIdx.x * kBlock + threadIdx.x, + gridDim.x * kBlock, ...:
+// draw i is r = floor(fmix64(key_b + golden * i) * N / 2^64), counted in the
+// class c with cum[c] <= r < cum[c + 1] (cum: nc + 1 entries, strictly
+// ascending, cum[nc] = N > r).  Integers only.  LDS: cum and a uint32 histogram
+// in (dynamic) LDS, flushed with one 64-bit atomic per class the block touched;
+// otherwise cum from global memory and a 64-bit atomic per draw.
+template <bool LDS>
+__global__ __launch_bounds__(kBlock) void k_boot_draw(const uint64_t *__restrict__ cum, uint32_t nc, uint64_t N,
+                                                      uint64_t seed, unsigned long long *__restrict__ counts) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char boot_lds[];
+    uint64_t *s_cum = (uint64_t *)boot_lds;
+    uint32_t *s_hist = (uint32_t *)(boot_lds + ((size_t)nc + 1) * 8);
+    const uint32_t b = blockIdx.y;
+    unsigned long long *mine = counts + (uint64_t)b * nc;
+    if (LDS) {
+        for (uint32_t c = threadIdx.x; c <= nc; c += kBlock) s_cum[c] = cum[c];
+        for (uint32_t c = threadIdx.x; c < nc; c += kBlock) s_hist[c] = 0;
+        __syncthreads();
+    }
+    const uint64_t *cm = LDS ? s_cum : cum;
+    const uint64_t key = pad::fmix64(seed + kGolden * ((uint64_t)b + 1));
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += (uint64_t)gridDim.x * kBlock) {
+        const uint64_t r = __umul64hi(pad::fmix64(key + kGolden * i), N);
+        uint32_t lo = 0, hi = nc;  // cm[lo] <= r < cm[hi]
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (cm[mid] <= r)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        if (LDS)
+            atomicAdd(&s_hist[lo], 1u);
+        else
+            atomicAdd(&mine[lo], 1ull);
+    }
+    if (LDS) {
+        __syncthreads();
+        for (uint32_t c = threadIdx.x; c < nc; c += kBlock)
+            if (s_hist[c]) atomicAdd(&mine[c], (unsigned long long)s_hist[c]);
+    }
+}
+
+// The EM of replicate blockIdx.x, the whole loop in one launch: k_em_e's and
+// k_em_m's sums term for term with the replicate's counts for n_C, the classes
+// and then the genomes strided over the workgroup's threads.  d and the two
+// thetas are the replicate's rows of global scratch: what one phase writes the
+// next reads from other threads of the workgroup, through agent-scope accesses
+// with a barrier between the phases; LDS holds the max reduction only.
+__global__ __launch_bounds__(kBlock) void k_boot_em(const uint64_t *__restrict__ c_off, const uint32_t *__restrict__ c_g,
+                                                    const uint64_t *__restrict__ t_off, const uint32_t *__restrict__ t_c,
+                                                    uint32_t nc, uint32_t G, const double *__restrict__ len,
+                                                    const unsigned long long *__restrict__ counts, double n_total,
+                                                    uint32_t max_iterations, double tolerance, double *d_all,
+                                                    double *theta_all, double *__restrict__ theta_out,
+                                                    uint32_t *__restrict__ iterations, double *__restrict__ delta_out) {
+    __shared__ double red[kBlock];
+    const uint32_t b = blockIdx.x;
+    const unsigned long long *n_c = counts + (uint64_t)b * nc;
+    double *d = d_all + (uint64_t)b * nc;
+    double *theta = theta_all + (uint64_t)b * 2 * G, *theta_new = theta + G;
+    for (uint32_t g = threadIdx.x; g < G; g += kBlock) pad::st_agent(&theta[g], 1.0 / (double)G);
+    __syncthreads();
+    uint32_t it = 0;
+    double delta = 0;
+    while (it < max_iterations) {
+        for (uint32_t c = threadIdx.x; c < nc; c += kBlock) {
+            double s = 0;
+            for (uint64_t i = c_off[c]; i < c_off[c + 1]; i++) {
+                const uint32_t g = c_g[i];
+                s += rho_of(pad::ld_agent(&theta[g]), len[g]);
+            }
+            pad::st_agent(&d[c], s);
+        }
+        __syncthreads();
+        double m = 0;
+        for (uint32_t g = threadIdx.x; g < G; g += kBlock) {
+            const double th = pad::ld_agent(&theta[g]);
+            const double rho = rho_of(th, len[g]);
+            double s = 0;
+            for (uint64_t i = t_off[g]; i < t_off[g + 1]; i++) {
+                const uint32_t c = t_c[i];
+                const double dc = pad::ld_agent(&d[c]);
+                const double n = (double)n_c[c];
+                if (dc != 0) s += n * rho / dc;
+            }
+            const double t = s / n_total;
+            pad::st_agent(&theta_new[g], t);
+            m = fmax(m, fabs(t - th));
+        }
+        red[threadIdx.x] = m;
+        __syncthreads();
+        for (int s = kBlock / 2; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
+            __syncthreads();
+        }
+        delta = red[0];
+        __syncthreads();  // (red is written again in the next iteration)
+        double *sw = theta;
+        theta = theta_new;
+        theta_new = sw;
+        it++;
+        if (tolerance > 0 && delta < tolerance) break;  // (uniform: every thread read the same red[0])
+    }
+    for (uint32_t g = threadIdx.x; g < G; g += kBlock) theta_out[(uint64_t)b * G + g] = pad::ld_agent(&theta[g]);
+    if (threadIdx.x == 0) {
+        iterations[b] = it;
+        delta_out[b] = delta;
+    }
+}
+
 using pa::Bufs;
 
 // The candidate pass left on the device.
@@ -399,6 +525,35 @@ pa_status collect(const pa_abundance *a, hipStream_t st, std::map<std::vector<ui
     return PA_OK;
 }
 
+// The classes in reported order as a CSR (class -> genomes), its transpose
+// (genome -> classes, ascending) and their counts: what the EM kernels read.
+struct ClassTables {
+    uint32_t nc = 0;
+    std::vector<uint64_t> c_off, t_off, n;
+    std::vector<uint32_t> c_g, t_c;
+    void build(const std::map<std::vector<uint32_t>, uint64_t> &m, uint32_t G) {
+        uint64_t E = 0;
+        for (const auto &kv : m) E += kv.first.size();
+        nc = (uint32_t)m.size();
+        c_off.assign((size_t)nc + 1, 0);
+        t_off.assign((size_t)G + 1, 0);
+        n.resize(nc);
+        c_g.resize(E);
+        t_c.resize(E);
+        uint32_t c = 0;
+        uint64_t o = 0;
+        for (const auto &kv : m) {
+            n[c] = kv.second;
+            for (uint32_t g : kv.first) c_g[o++] = g, t_off[g + 1]++;
+            c_off[++c] = o;
+        }
+        for (uint32_t g = 0; g < G; g++) t_off[g + 1] += t_off[g];
+        std::vector<uint64_t> at(t_off.begin(), t_off.end() - 1);
+        for (c = 0; c < nc; c++)
+            for (uint64_t i = c_off[c]; i < c_off[c + 1]; i++) t_c[at[c_g[i]]++] = c;
+    }
+};
+
 }  // namespace
 
 namespace pa {
@@ -514,24 +669,13 @@ pa_status abundance_estimate(const pa_abundance *a, uint32_t max_iterations, dou
     uint64_t N = 0, E = 0;
     for (const auto &kv : m) N += kv.second, E += kv.first.size();
     if (N == 0 || G == 0) return PA_OK;
-    // the classes (CSR) and their transpose, genome -> classes ascending: per-class host work, once per estimate
-    const uint32_t nc = (uint32_t)m.size();
-    std::vector<uint64_t> c_off((size_t)nc + 1, 0), t_off((size_t)G + 1, 0);
-    std::vector<uint32_t> c_g(E), t_c(E);
-    std::vector<double> n_c(nc), theta0(G, 1.0 / (double)G);
-    {
-        uint32_t c = 0;
-        uint64_t o = 0;
-        for (const auto &kv : m) {
-            n_c[c] = (double)kv.second;
-            for (uint32_t g : kv.first) c_g[o++] = g, t_off[g + 1]++;
-            c_off[++c] = o;
-        }
-        for (uint32_t g = 0; g < G; g++) t_off[g + 1] += t_off[g];
-        std::vector<uint64_t> at(t_off.begin(), t_off.end() - 1);
-        for (c = 0; c < nc; c++)
-            for (uint64_t i = c_off[c]; i < c_off[c + 1]; i++) t_c[at[c_g[i]]++] = c;
-    }
+    // the classes (CSR) and their transpose: per-class host work, once per estimate
+    ClassTables t;
+    t.build(m, G);
+    const uint32_t nc = t.nc;
+    const std::vector<uint64_t> &c_off = t.c_off, &t_off = t.t_off;
+    const std::vector<uint32_t> &c_g = t.c_g, &t_c = t.t_c;
+    std::vector<double> n_c(t.n.begin(), t.n.end()), theta0(G, 1.0 / (double)G);
     Bufs b(st);
     uint64_t *d_c_off = nullptr, *d_t_off = nullptr;
     uint32_t *d_c_g = nullptr, *d_t_c = nullptr;
@@ -586,6 +730,86 @@ pa_status abundance_estimate(const pa_abundance *a, uint32_t max_iterations, dou
     }
     if (iterations_done) *iterations_done = it;
     if (last_delta) *last_delta = delta;
+    return PA_OK;
+}
+
+pa_status abundance_bootstrap(const pa_abundance *a, uint32_t replicates, uint64_t seed, uint32_t max_iterations,
+                              double tolerance, uint64_t *counts, double *read_fraction, double *abundance,
+                              uint32_t *iterations, double *last_delta, hipStream_t st) {
+    const uint32_t G = a->n_genomes, B = replicates;
+    std::map<std::vector<uint32_t>, uint64_t> m;
+    PA_TRY(collect(a, st, m, nullptr));
+    const uint64_t n_classes = m.size();
+    if (counts) std::fill(counts, counts + (uint64_t)B * n_classes, (uint64_t)0);
+    if (read_fraction) std::fill(read_fraction, read_fraction + (uint64_t)B * G, 0.0);
+    if (abundance) std::fill(abundance, abundance + (uint64_t)B * G, 0.0);
+    if (iterations) std::fill(iterations, iterations + B, 0u);
+    if (last_delta) std::fill(last_delta, last_delta + B, 0.0);
+    uint64_t N = 0;
+    for (const auto &kv : m) N += kv.second;
+    if (N == 0 || G == 0) return PA_OK;
+    ClassTables t;
+    t.build(m, G);
+    const uint32_t nc = t.nc;
+    const uint64_t E = t.c_g.size();
+    std::vector<uint64_t> cum((size_t)nc + 1, 0);
+    for (uint32_t c = 0; c < nc; c++) cum[c + 1] = cum[c] + t.n[c];
+    Bufs b(st);
+    uint64_t *d_c_off = nullptr, *d_t_off = nullptr, *d_cum = nullptr;
+    uint32_t *d_c_g = nullptr, *d_t_c = nullptr, *d_it = nullptr;
+    unsigned long long *d_cnt = nullptr;
+    double *d_len = nullptr, *d_theta = nullptr, *d_d = nullptr, *d_out = nullptr, *d_delta = nullptr;
+    PA_HIP(b.get(&d_c_off, t.c_off.size() * 8));
+    PA_HIP(b.get(&d_t_off, t.t_off.size() * 8));
+    PA_HIP(b.get(&d_c_g, E * 4));
+    PA_HIP(b.get(&d_t_c, E * 4));
+    PA_HIP(b.get(&d_cum, cum.size() * 8));
+    PA_HIP(b.get(&d_len, (uint64_t)G * 8));
+    PA_HIP(b.get(&d_cnt, (uint64_t)B * nc * 8));
+    PA_HIP(b.get(&d_d, (uint64_t)B * nc * 8));
+    PA_HIP(b.get(&d_theta, (uint64_t)B * 2 * G * 8));
+    PA_HIP(b.get(&d_out, (uint64_t)B * G * 8));
+    PA_HIP(b.get(&d_it, (uint64_t)B * 4));
+    PA_HIP(b.get(&d_delta, (uint64_t)B * 8));
+    PA_HIP(hipMemcpyAsync(d_c_off, t.c_off.data(), t.c_off.size() * 8, hipMemcpyHostToDevice, st));
+    PA_HIP(hipMemcpyAsync(d_t_off, t.t_off.data(), t.t_off.size() * 8, hipMemcpyHostToDevice, st));
+    PA_HIP(hipMemcpyAsync(d_c_g, t.c_g.data(), E * 4, hipMemcpyHostToDevice, st));
+    PA_HIP(hipMemcpyAsync(d_t_c, t.t_c.data(), E * 4, hipMemcpyHostToDevice, st));
+    PA_HIP(hipMemcpyAsync(d_cum, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, st));
+    PA_HIP(hipMemcpyAsync(d_len, a->h_len.data(), (uint64_t)G * 8, hipMemcpyHostToDevice, st));
+    PA_HIP(hipMemsetAsync(d_cnt, 0, (uint64_t)B * nc * 8, st));
+    PA_HIP(hipStreamSynchronize(st));  // (the host vectors above are pageable)
+    // the draws: a thread takes 64 of them or more, 256 blocks a replicate at most -- and as many as keep a
+    // block's draws under 2^31
+    const char *e = std::getenv("PA_BOOT_LDS");
+    const bool lds = nc <= kBootLdsClasses && !(e && e[0] == '0');
+    const uint64_t per_block = (uint64_t)kBlock * 64;
+    const unsigned gx = (unsigned)std::max<uint64_t>(std::min<uint64_t>((N + per_block - 1) / per_block, 256),
+                                                     (N + kBootBlockDraws - 1) / kBootBlockDraws);
+    if (lds)
+        hipLaunchKernelGGL(k_boot_draw<true>, dim3(gx, B), dim3(kBlock), boot_lds_bytes(nc), st, d_cum, nc, N, seed,
+                           d_cnt);
+    else
+        hipLaunchKernelGGL(k_boot_draw<false>, dim3(gx, B), dim3(kBlock), 0, st, d_cum, nc, N, seed, d_cnt);
+    PA_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_boot_em, dim3(B), dim3(kBlock), 0, st, d_c_off, d_c_g, d_t_off, d_t_c, nc, G, d_len, d_cnt,
+                       (double)N, max_iterations, tolerance, d_d, d_theta, d_out, d_it, d_delta);
+    PA_HIP(hipGetLastError());
+    std::vector<double> theta((size_t)B * G);
+    if (counts) PA_HIP(hipMemcpyAsync(counts, d_cnt, (uint64_t)B * nc * 8, hipMemcpyDeviceToHost, st));
+    if (iterations) PA_HIP(hipMemcpyAsync(iterations, d_it, (uint64_t)B * 4, hipMemcpyDeviceToHost, st));
+    if (last_delta) PA_HIP(hipMemcpyAsync(last_delta, d_delta, (uint64_t)B * 8, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipMemcpyAsync(theta.data(), d_out, theta.size() * 8, hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
+    if (read_fraction) std::copy(theta.begin(), theta.end(), read_fraction);
+    if (abundance)
+        for (uint32_t r = 0; r < B; r++) {
+            const double *th = theta.data() + (size_t)r * G;
+            double *out = abundance + (size_t)r * G;
+            double sum = 0;
+            for (uint32_t g = 0; g < G; g++) sum += rho_of(th[g], a->h_len[g]);
+            for (uint32_t g = 0; g < G; g++) out[g] = sum != 0 ? rho_of(th[g], a->h_len[g]) / sum : 0.0;
+        }
     return PA_OK;
 }
 

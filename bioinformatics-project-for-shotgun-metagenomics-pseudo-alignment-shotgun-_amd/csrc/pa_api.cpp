@@ -943,6 +943,18 @@ pa_status pa_abundance_estimate(const pa_abundance *a, uint32_t max_iterations, 
                                   as_stream(stream));
 }
 
+pa_status pa_abundance_bootstrap(const pa_abundance *a, uint32_t replicates, uint64_t seed, uint32_t max_iterations,
+                                 double tolerance, uint64_t *counts, double *read_fraction, double *abundance,
+                                 uint32_t *iterations, double *last_delta, void *stream) {
+    PA_CHECK(a != nullptr, PA_EINVAL, "NULL argument");
+    PA_CHECK(replicates >= 1 && replicates <= 10000, PA_EINVAL, "replicates must be 1 to 10000");
+    PA_CHECK(max_iterations >= 1 && max_iterations <= 10000, PA_EINVAL, "max_iterations must be 1 to 10000");
+    PA_CHECK(tolerance >= 0, PA_EINVAL, "tolerance must be a number that is not negative");  // (false for NaN too)
+    PA_HIP(hipSetDevice(a->device));
+    return pa::abundance_bootstrap(a, replicates, seed, max_iterations, tolerance, counts, read_fraction, abundance,
+                                   iterations, last_delta, as_stream(stream));
+}
+
 void pa_abundance_free(pa_abundance *a) {
     if (!a) return;
     hipSetDevice(a->device);

@@ -495,6 +495,9 @@ pa_status abundance_classes(const pa_abundance *a, uint64_t *class_off, uint32_t
                             hipStream_t st);
 pa_status abundance_estimate(const pa_abundance *a, uint32_t max_iterations, double tolerance, double *read_fraction,
                              double *abundance, uint32_t *iterations_done, double *last_delta, hipStream_t st);
+pa_status abundance_bootstrap(const pa_abundance *a, uint32_t replicates, uint64_t seed, uint32_t max_iterations,
+                              double tolerance, uint64_t *counts, double *read_fraction, double *abundance,
+                              uint32_t *iterations, double *last_delta, hipStream_t st);
 pa_status align_candidates(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *type, uint64_t *set_off,
                            uint32_t *sets, uint64_t cap, uint64_t *total, hipStream_t st);
 // pairs (pa_pair.hip; the pair-exact kernel is k_align_exact's sibling in pa_align.hip)

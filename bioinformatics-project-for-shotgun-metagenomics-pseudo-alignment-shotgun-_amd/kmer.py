@@ -33,6 +33,7 @@ from __future__ import annotations
 
 import gzip
 import json
+import math
 import os
 import pickle
 import weakref
@@ -692,19 +693,73 @@ _ABUNDANCE: "weakref.WeakKeyDictionary[PseudoAlignment, Optional[N.Abundance]]" 
 ABUNDANCE_HEADER = "#genome\tlength\tunique_reads\tcompatible_reads\testimated_reads\tread_fraction\tabundance\n"
 
 
+ABUNDANCE_BOOTSTRAP_COLUMNS = ("abundance_mean", "abundance_sd", "abundance_lo", "abundance_hi")
+
+
+def confidence_permille(confidence) -> int:
+    """The per-mille integer of a confidence level, round(1000 * confidence),
+    converted once as variant_permille converts its fraction, so the quantile
+    index below is integer arithmetic.  ValueError outside 1 .. 999."""
+    if isinstance(confidence, bool) or not isinstance(confidence, (int, float)) or confidence != confidence:
+        raise ValueError("confidence must be a number with round(1000 * confidence) in 1 .. 999")
+    c = int(round(1000 * confidence))
+    if not 1 <= c <= 999:
+        raise ValueError("confidence must be a number with round(1000 * confidence) in 1 .. 999")
+    return c
+
+
+def bootstrap_summary(matrix, confidence):
+    """Per genome (column) of a replicates x genomes matrix: (mean, sd, lo, hi).
+    mean: the sum over the replicates in replicate order, divided by B; sd: the
+    sample standard deviation (ddof = 1; 0 for B = 1); lo and hi: the percentile
+    interval, sorted[j] and sorted[B - 1 - j] with j = ((1000 - c) * B) // 2000
+    and c = confidence_permille(confidence)."""
+    c = confidence_permille(confidence)
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.ndim != 2 or m.shape[0] < 1:
+        raise ValueError("matrix must be replicates x genomes with at least one replicate")
+    B = m.shape[0]
+    j = ((1000 - c) * B) // 2000
+    out = []
+    for g in range(m.shape[1]):
+        col = [float(x) for x in m[:, g]]
+        total = 0.0
+        for x in col:
+            total += x
+        mean = total / B
+        ss = 0.0
+        for x in col:
+            ss += (x - mean) * (x - mean)
+        sd = math.sqrt(ss / (B - 1)) if B > 1 else 0.0
+        s = sorted(col)
+        out.append((mean, sd, s[j], s[B - 1 - j]))
+    return out
+
+
 def abundance_text(names, lengths, unique_reads, compatible_reads, read_fraction, abundance, n_reads, iterations,
-                   last_delta, n_classes) -> str:
+                   last_delta, n_classes, bootstrap=None) -> str:
     """The --abundance file: ABUNDANCE_HEADER, one tab-separated line per genome
     (estimated_reads = read_fraction * n_reads; floats as format(x, ".9g")) and a
-    last comment line with the EM's iterations, its last delta and the classes."""
+    last comment line with the EM's iterations, its last delta and the classes.
+    With ``bootstrap`` = (per-genome (mean, sd, lo, hi), bootstraps, seed,
+    confidence) the header and the lines gain ABUNDANCE_BOOTSTRAP_COLUMNS and the
+    last line the three settings."""
     def f(x) -> str:
         return format(float(x), ".9g")
-    lines = [ABUNDANCE_HEADER]
+    header, last = ABUNDANCE_HEADER, ""
+    if bootstrap is not None:
+        summary, bootstraps, seed, confidence = bootstrap
+        header = ABUNDANCE_HEADER[:-1] + "".join("\t" + c for c in ABUNDANCE_BOOTSTRAP_COLUMNS) + "\n"
+        last = f"\tbootstraps\t{int(bootstraps)}\tseed\t{int(seed)}\tconfidence\t{f(confidence)}"
+    lines = [header]
     for g, name in enumerate(names):
-        lines.append("\t".join((str(name), str(int(lengths[g])), str(int(unique_reads[g])),
-                                str(int(compatible_reads[g])), f(float(read_fraction[g]) * n_reads),
-                                f(read_fraction[g]), f(abundance[g]))) + "\n")
-    lines.append(f"#iterations\t{int(iterations)}\tlast_delta\t{f(last_delta)}\tclasses\t{int(n_classes)}\n")
+        cols = (str(name), str(int(lengths[g])), str(int(unique_reads[g])),
+                str(int(compatible_reads[g])), f(float(read_fraction[g]) * n_reads),
+                f(read_fraction[g]), f(abundance[g]))
+        if bootstrap is not None:
+            cols += tuple(f(x) for x in summary[g])
+        lines.append("\t".join(cols) + "\n")
+    lines.append(f"#iterations\t{int(iterations)}\tlast_delta\t{f(last_delta)}\tclasses\t{int(n_classes)}{last}\n")
     return "".join(lines)
 
 
@@ -1177,21 +1232,34 @@ class PseudoAlignment:
             ab = _ABUNDANCE[self] = N.Abundance(self.kmer_reference.index)
         return ab
 
-    def get_abundance(self, iterations: int = 200, tolerance: float = 1e-9) -> Dict[str, Any]:
+    def get_abundance(self, iterations: int = 200, tolerance: float = 1e-9, bootstraps: int = 0, seed: int = 1,
+                      confidence: float = 0.95) -> Dict[str, Any]:
         """The EM estimate over the reads' compatibility classes (DESIGN.md section
         14): ``{"genomes": [{"genome", "length", "unique_reads", "compatible_reads",
         "estimated_reads", "read_fraction", "abundance"}, ...], "reads", "iterations",
         "last_delta", "classes"}``, one entry per genome of the index in FASTA
         order.  compatible_reads counts the reads whose class holds the genome,
-        estimated_reads = read_fraction * reads.  ValueError for an alignment made
-        without ``abundance=True`` (or loaded from a file), iterations outside
-        1 .. 10000 and a negative tolerance."""
+        estimated_reads = read_fraction * reads.  With ``bootstraps`` > 0 (at most
+        10000) that many bootstrap replicates of the estimate are run under
+        ``seed``: every genome gains "abundance_mean",
+        "abundance_sd", "abundance_lo" and "abundance_hi" (bootstrap_summary of the
+        replicates' abundances at ``confidence``) and the dict "bootstraps", "seed"
+        and "confidence".  ValueError for an alignment made without
+        ``abundance=True`` (or loaded from a file), iterations outside 1 .. 10000,
+        a negative tolerance, bootstraps outside 0 .. 10000, a seed outside
+        0 .. 2^64 - 1 and a confidence bootstrap_summary refuses."""
         if self not in _ABUNDANCE:
             raise ValueError("this alignment was made without abundance=True")
         if isinstance(iterations, bool) or not isinstance(iterations, int) or not 1 <= iterations <= 10000:
             raise ValueError("iterations must be an integer in 1 .. 10000")
         if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float)) or not tolerance >= 0:
             raise ValueError("tolerance must be a number that is not negative")
+        if isinstance(bootstraps, bool) or not isinstance(bootstraps, int) or not 0 <= bootstraps <= 10000:
+            raise ValueError("bootstraps must be an integer in 0 .. 10000")
+        if bootstraps:
+            if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed <= 2 ** 64 - 1:
+                raise ValueError("seed must be an integer in 0 .. 2^64 - 1")
+            confidence_permille(confidence)
         ab = self._abundance()
         names = [g.identifier for g in self.kmer_reference.genomes]
         G = len(names)
@@ -1201,19 +1269,30 @@ class PseudoAlignment:
         unique = self._result.fetch()[1] if self._result is not None else np.zeros(G, dtype=np.uint64)
         theta, share, done, delta = ab.estimate(iterations, float(tolerance))
         n_reads = int(cnt.sum())
-        return {"genomes": [{"genome": names[g], "length": ab.lengths[g], "unique_reads": int(unique[g]),
-                             "compatible_reads": int(compatible[g]), "estimated_reads": float(theta[g]) * n_reads,
-                             "read_fraction": float(theta[g]), "abundance": float(share[g])} for g in range(G)],
-                "reads": n_reads, "iterations": done, "last_delta": delta, "classes": int(cnt.size)}
+        out = {"genomes": [{"genome": names[g], "length": ab.lengths[g], "unique_reads": int(unique[g]),
+                            "compatible_reads": int(compatible[g]), "estimated_reads": float(theta[g]) * n_reads,
+                            "read_fraction": float(theta[g]), "abundance": float(share[g])} for g in range(G)],
+               "reads": n_reads, "iterations": done, "last_delta": delta, "classes": int(cnt.size)}
+        if bootstraps:
+            shares = ab.bootstrap(bootstraps, seed, iterations, float(tolerance))[1]
+            for row, stats in zip(out["genomes"], bootstrap_summary(shares, confidence)):
+                row.update(zip(ABUNDANCE_BOOTSTRAP_COLUMNS, stats))
+            out.update(bootstraps=bootstraps, seed=seed, confidence=float(confidence))
+        return out
 
-    def write_abundance(self, fh, iterations: int = 200, tolerance: float = 1e-9) -> None:
+    def write_abundance(self, fh, iterations: int = 200, tolerance: float = 1e-9, bootstraps: int = 0, seed: int = 1,
+                        confidence: float = 0.95) -> None:
         """get_abundance as text (abundance_text)."""
-        a = self.get_abundance(iterations, tolerance)
+        a = self.get_abundance(iterations, tolerance, bootstraps, seed, confidence)
         rows = a["genomes"]
+        boot = None
+        if bootstraps:
+            boot = ([tuple(r[c] for c in ABUNDANCE_BOOTSTRAP_COLUMNS) for r in rows], a["bootstraps"], a["seed"],
+                    a["confidence"])
         fh.write(abundance_text([r["genome"] for r in rows], [r["length"] for r in rows],
                                 [r["unique_reads"] for r in rows], [r["compatible_reads"] for r in rows],
                                 [r["read_fraction"] for r in rows], [r["abundance"] for r in rows], a["reads"],
-                                a["iterations"], a["last_delta"], a["classes"]))
+                                a["iterations"], a["last_delta"], a["classes"], boot))
 
     def get_reads_by_mapping_type(self, mapping_type: ReadMappingType) -> List[str]:
         return [rid for rid, d in self.reads.items() if d["mapping_type"] == mapping_type]

@@ -8,7 +8,8 @@
                     [--assignments FILE]
                     [--variants FILE [--variant-min-depth N] [--variant-min-count N]
                      [--variant-min-fraction F] [--variant-min-base-quality Q]]
-                    [--abundance FILE [--abundance-iterations N] [--abundance-tolerance X]]
+                    [--abundance FILE [--abundance-iterations N] [--abundance-tolerance X]
+                     [--abundance-bootstraps B [--abundance-seed S] [--abundance-confidence X]]]
 
 Same tasks (reference | dumpref | align | dumpalign), flags, flag-combination
 checks, default coercions and error exits as src/main.py:61-402:
@@ -83,7 +84,8 @@ def _has_variants_flag(argv: List[str]) -> bool:
     return False
 
 
-_ABUNDANCE_FLAGS = ("--abundance", "--abundance-iterations", "--abundance-tolerance")
+_ABUNDANCE_FLAGS = ("--abundance", "--abundance-iterations", "--abundance-tolerance", "--abundance-bootstraps",
+                    "--abundance-seed", "--abundance-confidence")
 
 
 def _has_abundance_flag(argv: List[str]) -> bool:
@@ -259,6 +261,12 @@ def parse_arguments(args: Optional[List[str]] = None) -> argparse.Namespace:
     parser.add_argument("--abundance-iterations", type=int, default=None, help="EM iterations at most (default: 200)")
     parser.add_argument("--abundance-tolerance", type=float, default=None,
                         help="stop once no read fraction moves by this much (default: 1e-9; 0: never)")
+    parser.add_argument("--abundance-bootstraps", type=int, default=None, metavar="B",
+                        help="add mean, sd and a confidence interval of the abundance over B bootstrap replicates")
+    parser.add_argument("--abundance-seed", type=int, default=None, metavar="S",
+                        help="seed of the bootstrap's resampling, 0 .. 2^64 - 1 (default: 1)")
+    parser.add_argument("--abundance-confidence", type=float, default=None, metavar="X",
+                        help="confidence level of the bootstrap interval (default: 0.95)")
     return parser.parse_args(args)
 
 
@@ -435,6 +443,9 @@ def _check_task(args: argparse.Namespace) -> None:
         validate_file_writable(args.variants, "Variants output")
     if args.abundance is None and (args.abundance_iterations is not None or args.abundance_tolerance is not None):
         sys.exit("Error: --abundance-iterations and --abundance-tolerance need --abundance.")
+    if args.abundance is None and (args.abundance_bootstraps is not None or args.abundance_seed is not None
+                                   or args.abundance_confidence is not None):
+        sys.exit("Error: --abundance-bootstraps, --abundance-seed and --abundance-confidence need --abundance.")
     if args.abundance is not None:
         if args.task != "dumpalign" or not args.reads:
             sys.exit("Error: --abundance is only allowed for task 'dumpalign' with --reads.")
@@ -442,6 +453,16 @@ def _check_task(args: argparse.Namespace) -> None:
             sys.exit("Error: --abundance-iterations must be in 1 .. 10000.")
         if args.abundance_tolerance is not None and not args.abundance_tolerance >= 0:
             sys.exit("Error: --abundance-tolerance must be at least 0.")
+        if args.abundance_bootstraps is None and (args.abundance_seed is not None
+                                                  or args.abundance_confidence is not None):
+            sys.exit("Error: --abundance-seed and --abundance-confidence need --abundance-bootstraps.")
+        if args.abundance_bootstraps is not None and not 1 <= args.abundance_bootstraps <= 10000:
+            sys.exit("Error: --abundance-bootstraps must be in 1 .. 10000.")
+        if args.abundance_seed is not None and not 0 <= args.abundance_seed <= 2 ** 64 - 1:
+            sys.exit("Error: --abundance-seed must be in 0 .. 2^64 - 1.")
+        if args.abundance_confidence is not None and not (  # (false for NaN too)
+                0 < args.abundance_confidence < 1 and 1 <= int(round(1000 * args.abundance_confidence)) <= 999):
+            sys.exit("Error: --abundance-confidence must be in 0.001 .. 0.999.")
         validate_file_writable(args.abundance, "Abundance output")
     if args.task == "reference":
         if extra:
@@ -512,7 +533,10 @@ def _print_alignment(alignment: PseudoAlignment, args: argparse.Namespace) -> No
     if args.abundance is not None:
         with open(args.abundance, "w") as fh:
             alignment.write_abundance(fh, 200 if args.abundance_iterations is None else args.abundance_iterations,
-                                      1e-9 if args.abundance_tolerance is None else args.abundance_tolerance)
+                                      1e-9 if args.abundance_tolerance is None else args.abundance_tolerance,
+                                      args.abundance_bootstraps or 0,
+                                      1 if args.abundance_seed is None else args.abundance_seed,
+                                      0.95 if args.abundance_confidence is None else args.abundance_confidence)
 
 
 def _run(args: argparse.Namespace) -> None:

@@ -54,7 +54,7 @@ EXPORTS = (
     "pa_pileup_create", "pa_pileup_reset", "pa_pileup_add", "pa_pileup_stats_get", "pa_pileup_counts",
     "pa_pileup_variants", "pa_pileup_free",
     "pa_abundance_create", "pa_abundance_reset", "pa_abundance_add", "pa_abundance_info_get", "pa_abundance_classes",
-    "pa_abundance_estimate", "pa_abundance_free", "pa_align_candidates",
+    "pa_abundance_estimate", "pa_abundance_bootstrap", "pa_abundance_free", "pa_align_candidates",
     "pa_profile_enable", "pa_profile_read", "pa_profile_read_kernels", "pa_mem_trim",
     "pa_parse_text", "pa_parse_file", "pa_seqset_sizes", "pa_seqset_export", "pa_seqset_free", "pa_gz_inflate_file",
 )
@@ -210,6 +210,7 @@ def lib():
         "pa_abundance_classes": (I32, [P, P, P, P, U64, U64, ctypes.POINTER(U64), ctypes.POINTER(U64), P]),
         "pa_abundance_estimate": (I32, [P, U32, ctypes.c_double, P, P, ctypes.POINTER(U32),
                                         ctypes.POINTER(ctypes.c_double), P]),
+        "pa_abundance_bootstrap": (I32, [P, U32, U64, U32, ctypes.c_double, P, P, P, P, P, P]),
         "pa_abundance_free": (None, [P]),
         "pa_align_candidates": (I32, [P, P, ctypes.POINTER(Params), P, P, P, U64, ctypes.POINTER(U64), P]),
         "pa_profile_enable": (I32, [P, I32]),
@@ -1303,6 +1304,29 @@ class Abundance:
         _check(lib().pa_abundance_estimate(self._h, int(iterations), float(tolerance), _ptr(theta), _ptr(ab),
                                            ctypes.byref(it), ctypes.byref(delta), _stream(stream)))
         return theta[:G], ab[:G], int(it.value), float(delta.value)
+
+    def bootstrap(self, replicates: int, seed: int = 1, iterations: int = 200, tolerance: float = 1e-9,
+                  counts: bool = False, stream=None):
+        """(read_fraction [B, G], abundance [B, G], iterations [B], last delta [B])
+        of B = ``replicates`` bootstrap replicates of the estimate (DESIGN.md
+        section 16), and with ``counts`` the resampled class counts [B, classes]
+        (uint64, ``classes``' order) as a fifth array."""
+        for name, v, lo, hi in (("replicates", replicates, 1, 10000), ("seed", seed, 0, 2 ** 64 - 1),
+                                ("iterations", iterations, 1, 10000)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} must be an integer in {lo} .. {hi}")
+        B, G = int(replicates), self.n_genomes
+        theta = np.zeros((B, max(G, 1)), dtype=np.float64)
+        ab = np.zeros((B, max(G, 1)), dtype=np.float64)
+        its = np.zeros(B, dtype=np.uint32)
+        delta = np.zeros(B, dtype=np.float64)
+        nc = self.info(stream)["n_classes"] if counts else 0
+        cnt = np.zeros((B, max(nc, 1)), dtype=np.uint64)
+        _check(lib().pa_abundance_bootstrap(self._h, B, int(seed), int(iterations), float(tolerance),
+                                            _ptr(cnt) if counts else None, _ptr(theta), _ptr(ab), _ptr(its),
+                                            _ptr(delta), _stream(stream)))
+        out = (theta[:, :G], ab[:, :G], its, delta)
+        return out + (cnt[:, :nc],) if counts else out
 
     def close(self):
         if getattr(self, "_h", None):

@@ -541,6 +541,34 @@ pa_status pa_abundance_classes(const pa_abundance *a, uint64_t *class_off, uint3
 pa_status pa_abundance_estimate(const pa_abundance *a, uint32_t max_iterations, double tolerance,
                                 double *read_fraction, double *abundance, uint32_t *iterations_done,
                                 double *last_delta, void *stream);
+/* Bootstrap replicates of the estimate.  The classes in
+ * reported order are C_0 .. C_{nc-1} with counts n_c, N = sum of n_c, cum_c the
+ * exclusive prefix sum of n.  Replicate b (0 <= b < replicates) has key_b =
+ * fmix64(seed + 0x9E3779B97F4A7C15 (b + 1)) (mod 2^64; fmix64: MurmurHash3's
+ * 64-bit finalizer).  Its draw i (0 <= i < N) is u = fmix64(key_b +
+ * 0x9E3779B97F4A7C15 i), r = floor(u N / 2^64), and falls in the class c with
+ * cum_c <= r < cum_{c+1}; counts[b][c] is the number of its draws in c, so every
+ * row sums to N (integers only: the counts depend on nothing but the classes,
+ * the seed and b).  Replicate b's EM is pa_abundance_estimate's, term for term
+ * and in its summation order, with counts[b][.] for n_C and the same N, started
+ * at 1/G; it stops after its own first iteration with delta < tolerance
+ * (iterations[b], last_delta[b]).  read_fraction[b][g] = theta_g of replicate
+ * b, abundance[b][g] from it as pa_abundance_estimate computes it.  N == 0
+ * gives zeros and 0 iterations.
+ *
+ * counts: replicates x n_classes (pa_abundance_info_get), read_fraction and
+ * abundance: replicates x n_genomes, iterations and last_delta: replicates;
+ * row-major; any output may be NULL.  replicates 1 .. 10000, max_iterations and
+ * tolerance as pa_abundance_estimate, else PA_EINVAL; PA_ENOMEM when the
+ * replicates' device scratch does not fit.  The accumulator is not modified;
+ * the call returns when done.  The draws run one workgroup strip per replicate
+ * (PA_BOOT_LDS=0 in the environment, read per call, counts through global
+ * atomics instead of a histogram in LDS: the same counts), the EMs one
+ * workgroup per replicate, every replicate's whole loop in one launch. */
+pa_status pa_abundance_bootstrap(const pa_abundance *a, uint32_t replicates, uint64_t seed,
+                                 uint32_t max_iterations, double tolerance, uint64_t *counts,
+                                 double *read_fraction, double *abundance, uint32_t *iterations,
+                                 double *last_delta, void *stream);
 void pa_abundance_free(pa_abundance *a);
 /* Per read C(r): read_type[n], set_off[n + 1], sets (ascending genomes).  If
  * cap < *total the call returns PA_EINVAL with *total, read_type and set_off

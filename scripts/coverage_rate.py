@@ -5,6 +5,7 @@ genomes, k = 31, synthesized 150-bp reads, 0.5 % substitutions).
     python scripts/coverage_rate.py --mode detail   [--reads N] [--runs R] > parent.json
     python scripts/coverage_rate.py --mode coverage [--reads N] [--runs R] [--baseline-json parent.json]
     python scripts/coverage_rate.py --mode assign   [--reads N] [--runs R] [--read-err E --rc-rate X --foreign-rate Y]
+    python scripts/coverage_rate.py --mode bootstrap [--reads N] [--runs R] [--replicates B]
 
 --mode detail times one pa_align_detail call with its lists (the pass a
 coverage add rides on); run it with PA_LIBRARY=<the parent commit's libpa.so>
@@ -43,6 +44,14 @@ from above and abundance_add_s - align_reads_s the candidate kernel plus the
 interning.  It adds the align kernels' own times over one profiled add, the
 accumulator's info (reads by type, classes) and pa_abundance_estimate for 200
 iterations (tolerance 0) and with the default tolerance.
+
+--mode bootstrap adds the reads once and times pa_abundance_bootstrap (DESIGN.md
+section 16) at --replicates B (default 100), seed 1: 200 iterations with
+tolerance 0 and with the default tolerance, each also under PA_BOOT_LDS=0, and
+next to each one pa_abundance_estimate with the same settings.  The yardstick
+is B x that estimate -- what a loop over pa_abundance_estimate would cost, with
+no resampling at all -- so ratio_*_over_B_estimates is the call's time over it.
+The draw / EM split comes from a kernel trace of this mode.
 
 --mode pairs times pa_align_pairs on a both-strand C2
 index: --reads pairs (default 1 000 000) made on the host -- fragments of 300 ..
@@ -203,7 +212,9 @@ def run_pairs(args, genomes, out):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("detail", "coverage", "assign", "pileup", "abundance", "pairs"), required=True)
+    ap.add_argument("--mode", choices=("detail", "coverage", "assign", "pileup", "abundance", "bootstrap", "pairs"),
+                    required=True)
+    ap.add_argument("--replicates", type=int, default=100, help="bootstrap replicates of --mode bootstrap")
     ap.add_argument("--reads", type=int, default=None, help="reads (default 10 000 000); pairs with --mode pairs (1 000 000)")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--genomes", type=int, default=50)
@@ -318,6 +329,30 @@ def main():
         dmed, dts, dentries = time_detail(index, reads, prm, args.runs)
         out.update(align_detail_s=dmed, align_detail_runs_s=dts,
                    ratio_abundance_add_over_align_detail=out["abundance_add_s"] / dmed)
+    elif args.mode == "bootstrap":
+        ab = N.Abundance(index)
+        ab.add(reads, prm)
+        out["info"] = ab.info()
+        B = args.replicates
+        out["replicates"] = B
+        holder = {}
+        os.environ.pop("PA_BOOT_LDS", None)
+        for tag, tol in (("200", 0.0), ("default", 1e-9)):
+            med, ts = timed(lambda: holder.update(e=ab.estimate(200, tol)), args.runs)
+            out.update({f"estimate_{tag}_s": med, f"estimate_{tag}_runs_s": ts,
+                        f"estimate_{tag}_iterations": holder["e"][2]})
+            for env, name in ((None, f"bootstrap_{tag}"), ("0", f"bootstrap_{tag}_global")):
+                if env is not None:
+                    os.environ["PA_BOOT_LDS"] = env
+                med_b, ts = timed(lambda: holder.update(b=ab.bootstrap(B, 1, 200, tol)), args.runs)
+                os.environ.pop("PA_BOOT_LDS", None)
+                its = holder["b"][2]
+                out.update({f"{name}_s": med_b, f"{name}_runs_s": ts,
+                            f"{name}_iterations_min_max": [int(its.min()), int(its.max())],
+                            f"ratio_{name}_over_B_estimates": med_b / (B * med)})
+        share = holder["b"][1]
+        out["abundance_sd_max"] = float(share.std(axis=0, ddof=1).max()) if B > 1 else 0.0
+        ab.close()
     else:
         med, ts, entries = time_detail(index, reads, prm, args.runs)
         out.update(align_detail_branch_s=med, align_detail_branch_runs_s=ts, list_entries=entries)
