@@ -1541,6 +1541,7 @@ static pa_status print_stats(pa_index *idx, const pa_reads *r, hipStream_t st) {
     fprintf(stderr, "[pa_stats] lane: cooperative probes %llu re-anchors %llu neighbour words %llu | pending: invalid %llu "
             "2+ mismatches %llu neighbour present %llu\n", d[18], d[19], d[20], d[21], d[22], d[23]);
     fprintf(stderr, "[pa_stats] lane: single-probe re-anchors %llu second walks given up unprobed %llu\n", d[32], d[33]);
+    fprintf(stderr, "[pa_stats] lane: neighbour words skipped (read settled by the bound without them) %llu\n", d[34]);
     fprintf(stderr, "[pa_stats] lane found: shared-neighbour+specific %llu second-walk specific %llu probed-shared+specific %llu"
             " | unique by bound %llu, by off-walk counts %llu | probes past the Bloom filter %llu\n", d[24], d[25], d[26], d[27], d[28],
             d[29]);

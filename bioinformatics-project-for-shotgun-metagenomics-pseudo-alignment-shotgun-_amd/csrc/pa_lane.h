@@ -144,6 +144,19 @@ constexpr uint32_t kLaneSure = 1u << 31;
 constexpr bool lane_sure(bool win_q, bool mg, int nm, int nw) {
     return PA_LANE_SURE && nw == 1 && (nm == 2 || !mg);
 }
+//   PA_LANE_NBSKIP: lane_walk_150 loads no neighbour word for a read that the
+//     bound of step 6 settles whatever the words hold: with Xall = the
+//     unindexed live windows + the walked-stretch windows with a mismatch and
+//     ns = the walked specific k-mers, ns >= Xall + max(m, 1) (DESIGN.md
+//     section 4, step 6a: the bits can only take windows out of X); =0: every
+//     mismatch's word is loaded first (A/B).
+#ifndef PA_LANE_NBSKIP
+#define PA_LANE_NBSKIP 1
+#endif
+// The instantiations with that skip: the 150-bp shape with single-word keys,
+// not --max-genomes (there the words also give the highly redundant count of
+// the windows off the walk).
+constexpr bool lane_nbskip(bool mg, int nm, int nw) { return PA_LANE_NBSKIP && !mg && nm == 2 && nw == 1; }
 // s_waitcnt immediate, gfx9 encoding: vmcnt [3:0] and [15:14] = 0, expcnt [6:4]
 // = 7 and lgkmcnt [11:8] = 15 (not waited for)
 constexpr int kLaneWaitVm0 = 0x0F70;
@@ -1044,7 +1057,8 @@ __device__ __forceinline__ void shifted_planes(const uint64_t (&p)[NM + 1], uint
 // SURE (PA_LANE_SURE; single-word keys with both halves of the neighbour
 // words): 1: the read that is walked again whatever its probes return keeps
 // one window to probe (the last step); 2: only reported, for lane_walk_halves.
-template <bool WIN_Q, bool MG, int NW = 1, int SURE = lane_sure(WIN_Q, MG, 2, NW)>
+// SKIP (PA_LANE_NBSKIP): no neighbour word for a read the bound settles anyway.
+template <bool WIN_Q, bool MG, int NW = 1, int SURE = lane_sure(WIN_Q, MG, 2, NW), bool SKIP = false>
 __device__ __forceinline__ void lane_walk_150(const AlignArgs &a, const uint64_t *row, LaneRead<2> &S) {
     const int k = a.k;
     uint32_t W = S.W, len = S.len;
@@ -1191,6 +1205,29 @@ __device__ __forceinline__ void lane_walk_150(const AlignArgs &a, const uint64_t
         }
     }
 #endif
+    // The words can only take windows out of the bound's X (k_align_lane): a
+    // window with a mismatch counts in X unless its bit says absent, an
+    // unindexed one always.  With every such window counted, Xall, and ns the
+    // walked specific k-mers (no --max-genomes: all included), ns >= Xall +
+    // max(m, 1) settles the read UNIQUE g whatever the words hold (X <= Xall
+    // and X - ns < 0 <= p), with the same counts: its words are not loaded and
+    // it leaves with nothing to probe (the local-repeat test below still runs).
+    bool nbskip = false;
+    if constexpr (SKIP) {
+        const uint64_t i0 = W >= 64 ? ~0ull : ((1ull << W) - 1);
+        const uint64_t i1 = W <= 64 ? 0ull : (W >= 128 ? ~0ull : ((1ull << (W - 64)) - 1));
+        const uint64_t l0 = WIN_Q ? i0 & ~S.F[0] : i0, l1 = WIN_Q ? i1 & ~S.F[1] : i1;
+        const uint64_t v0 = IX0 & l0, v1 = IX1 & l1;
+        const uint32_t xall = (uint32_t)(__popcll((l0 & ~v0) | (v0 & U0)) + __popcll((l1 & ~v1) | (v1 & U1)));
+        const uint32_t ns = (uint32_t)(__popcll(v0 & ~U0 & PA0 & PB0) + __popcll(v1 & ~U1 & PA1 & PB1));
+        if (nnb && ns >= xall + (uint32_t)(a.prm.m > 0 ? a.prm.m : 1)) {
+#ifdef PA_STATS
+            atomicAdd(&a.dbg[30], (unsigned long long)nnb);
+#endif
+            nbskip = true;
+            nnb = 0;
+        }
+    }
     // the neighbour words, four loads in flight at a time (one round trip for
     // up to four mismatches, not one per mismatch)
 #pragma unroll 1
@@ -1362,6 +1399,12 @@ __device__ __forceinline__ void lane_walk_150(const AlignArgs &a, const uint64_t
     S.hr = hr + hr_off;  // windows, repeats included (quirk 4)
     S.P[0] = P0;
     S.P[1] = P1;
+    if constexpr (SKIP) {
+        if (nbskip) {  // settled by the bound with X = 0 (S.uoff is 0: no word was loaded); never over the pending cap
+            S.P[0] = S.P[1] = 0;
+            return;
+        }
+    }
     // With cs > 0 such windows the probes find nsoff >= cs specific k-mers off
     // the walk, and both ways to settle the read need nspec >= nsoff + max(m, 1)
     // (k_align_lane: the bound's X >= cs, the two-genome decision's c = nsoff):
@@ -2050,7 +2093,7 @@ void k_align_lane(AlignArgs a) {
         for (int attempt = again_batch ? 1 : 0; attempt < 2; attempt++) {
             if (S.kind == LANE_WALK) {
                 if constexpr (NM == 2)
-                    lane_walk_150<WIN_Q, MG, NW>(a, my_row(), S);
+                    lane_walk_150<WIN_Q, MG, NW, lane_sure(WIN_Q, MG, 2, NW), lane_nbskip(MG, NM, NW)>(a, my_row(), S);
                 else
                     if constexpr (NM == 4 && !WIN_Q && NW == 1 && PA_LANE_HALVES)
                         lane_walk_halves<MG>(a, my_row(), S);

@@ -19,6 +19,11 @@
 //                    nontemporal) + one of a 64 MB region: does the region stay
 //                    in the Infinity Cache behind the big random reads?
 //   stream16         coalesced 16 B per lane, sequential (the guide's 1/2 case)
+// --ntmix (profiles/nt_policy/calib.json; DESIGN.md section 6, "Cache policy"):
+//   pair32           two 16-B loads per lane of one aligned 32-B group of a
+//                    random line (the step of lane_probe<NP, 2>), plain / nontemporal
+//   lanemix          per lane ten 16-B loads of its 150 B of a dense stream (plain)
+//                    + eight isolated random lines, plain / nontemporal, 64 and 100 GB
 // Run under `rocprofv3 --kernel-trace --pmc FETCH_SIZE -- ./fetch_calib` and
 // divide: bytes touched / FETCH_SIZE bytes = the correction of that shape;
 // lines / time = the random-line rate (profiles/fetch_calib.json).
@@ -128,6 +133,61 @@ __global__ __launch_bounds__(256) void k_stream16(const uint4 *__restrict__ buf,
     if (acc == 0x12345679u) out[0] = acc;
 }
 
+// ---- --ntmix: the library's read-once loads in the lane kernel's own mix ----
+// (profiles/nt_policy/calib.json).  The library's form of a nontemporal load:
+// ONE global_load_dwordx4 nt, where ld16<true> above is four dword loads.
+typedef uint32_t u32x4_g __attribute__((ext_vector_type(4), aligned(8)));
+template <bool NT>
+__device__ __forceinline__ uint4 ld16v(const uint4 *p) {
+    if (NT) {
+        const auto v = __builtin_nontemporal_load((const __attribute__((address_space(1))) u32x4_g *)(uintptr_t)p);
+        return make_uint4(v.x, v.y, v.z, v.w);
+    }
+    return *p;
+}
+
+// Shape (a), the probe step of lane_probe<NP, 2>: per lane R random 128-B
+// lines, of each the two 16-B slots of one aligned 32-B group -- two loads
+// that the L1 coalesces when they are plain.
+template <bool NT, int R>
+__global__ __launch_bounds__(256) void k_pair32(const uint4 *__restrict__ buf, uint64_t n_groups, uint64_t seed,
+                                                uint32_t *out) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < R; i++) {
+        const uint64_t g = __umul64hi(mix(seed ^ (t * 0x9E3779B97F4A7C15ull + (uint64_t)i)), n_groups);
+        const uint4 v0 = ld16v<NT>(buf + 2 * g), v1 = ld16v<NT>(buf + 2 * g + 1);
+        acc ^= v0.x ^ v0.w ^ v1.y ^ v1.z;
+    }
+    if (acc == 0x12345679u) out[t & 0xFFFFF] = acc;
+}
+
+// Shape (b), a lane of k_align_lane in outline: ten 16-B loads of the lane's
+// own 150 B of a dense stream (plain, through L1: neighbouring lanes share
+// its lines) and R isolated random 16-B loads of a big region, plain or
+// nontemporal, all in flight together.
+template <bool NT, int R>
+__global__ __launch_bounds__(256) void k_lanemix(const uint4 *__restrict__ big, uint64_t big_lines,
+                                                 const uint4 *__restrict__ stream, uint64_t seed, uint32_t *out) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint4 *sp = stream + ((150 * t) >> 4);  // (the buffer holds 16 B past the last lane's 160)
+    uint32_t acc = 0;
+    uint4 s[10], r[R];
+#pragma unroll
+    for (int i = 0; i < 10; i++) s[i] = sp[i];
+#pragma unroll
+    for (int i = 0; i < R; i++) {
+        const uint64_t h = mix(seed ^ (t * 0x9E3779B97F4A7C15ull + (uint64_t)i));
+        r[i] = ld16v<NT>(big + __umul64hi(h, big_lines) * 4 + (h & 3));
+    }
+#pragma unroll
+    for (int i = 0; i < 10; i++) acc ^= s[i].x ^ s[i].w;
+#pragma unroll
+    for (int i = 0; i < R; i++) acc ^= r[i].y ^ r[i].z;
+    if (acc == 0x12345679u) out[t & 0xFFFFF] = acc;
+}
+
 static hipEvent_t e0, e1;
 static bool first_row = true;
 
@@ -184,8 +244,52 @@ static int footprint_sweep() {
     return 0;
 }
 
+// --ntmix: shapes (a) and (b) above over regions of 64 and 100 GB (C4's table;
+// its whole index), plain and nontemporal alternating, three times each.
+static int nt_mix() {
+    const uint64_t GB = 1000ull * 1000 * 1000;
+    const uint64_t bytes = (100 * GB) & ~((1ull << 20) - 1);
+    const unsigned blocks = 16384;
+    const uint64_t lanes = (uint64_t)blocks * 256;
+    constexpr int R = 8;
+    const uint64_t L = lanes * R;
+    uint4 *buf = nullptr, *stream = nullptr;
+    uint32_t *out = nullptr;
+    CK(hipMalloc(&buf, bytes));
+    CK(hipMalloc(&stream, 150 * lanes + 4096));
+    CK(hipMalloc(&out, 4u << 20));
+    CK(hipMemset(buf, 0x5A, bytes));
+    CK(hipMemset(stream, 0x3C, 150 * lanes + 4096));
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    CK(hipDeviceSynchronize());
+    std::printf("{\"buffer_bytes\": %llu, \"random_accesses_per_lane\": %d, \"lanes\": %llu, \"nt_mix\": [\n",
+                (unsigned long long)bytes, R, (unsigned long long)lanes);
+    char name[64];
+    for (uint64_t gb : {64ull, 100ull}) {
+        const uint64_t nb = std::min<uint64_t>(gb * GB, bytes);
+        for (int rep = 0; rep < 3; rep++) {
+            const uint64_t seed = 100 * gb + 10 * rep;
+            std::snprintf(name, sizeof name, "k_pair32<plain>@%lluGB", (unsigned long long)gb);
+            timed(name, L, L * 64, [&] { hipLaunchKernelGGL((k_pair32<false, R>), dim3(blocks), dim3(256), 0, 0, buf, nb / 32, seed + 1, out); });
+            std::snprintf(name, sizeof name, "k_pair32<nt>@%lluGB", (unsigned long long)gb);
+            timed(name, L, L * 64, [&] { hipLaunchKernelGGL((k_pair32<true, R>), dim3(blocks), dim3(256), 0, 0, buf, nb / 32, seed + 2, out); });
+            std::snprintf(name, sizeof name, "k_lanemix<plain>@%lluGB", (unsigned long long)gb);
+            timed(name, L, L * 64, [&] { hipLaunchKernelGGL((k_lanemix<false, R>), dim3(blocks), dim3(256), 0, 0, buf, nb / 64, stream, seed + 3, out); });
+            std::snprintf(name, sizeof name, "k_lanemix<nt>@%lluGB", (unsigned long long)gb);
+            timed(name, L, L * 64, [&] { hipLaunchKernelGGL((k_lanemix<true, R>), dim3(blocks), dim3(256), 0, 0, buf, nb / 64, stream, seed + 4, out); });
+        }
+    }
+    std::printf("]}\n");
+    CK(hipFree(buf));
+    CK(hipFree(stream));
+    CK(hipFree(out));
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc > 1 && std::string(argv[1]) == "--footprint") return footprint_sweep();
+    if (argc > 1 && std::string(argv[1]) == "--ntmix") return nt_mix();
     const uint64_t bytes = 16ull << 30, n_lines = bytes / 64;
     uint4 *buf = nullptr;
     uint32_t *out = nullptr;
