@@ -371,21 +371,13 @@ __global__ __launch_bounds__(kBlock) void k_boot_em(const uint64_t *__restrict__
 }
 
 using pa::Bufs;
+using pa::CandDev;
 
-// The candidate pass left on the device.
-struct CandDev {
-    pa::AssignDev as;
-    uint32_t *queue = nullptr;   // [n] the ambiguous reads, nq of them
-    uint64_t nq = 0;
-    uint32_t *len = nullptr;     // [n + 1] set sizes
-    uint64_t *off = nullptr;     // [n + 1]
-    uint32_t *sets = nullptr;    // [total] (null when total > cap or 0)
-    uint64_t total = 0;
-};
+}  // namespace
 
-// counts: the accumulator's [4 + G], or null (a scratch array is used).
-pa_status candidates_device(pa_index *idx, const pa_reads *r, const pa::DevParams &p, uint64_t cap,
-                            unsigned long long *counts, CandDev &out, Bufs &b, hipStream_t st) {
+// The candidate pass left on the device (declared in pa_internal.h: pa_lineage.hip starts from it too).
+pa_status pa::candidates_device(pa_index *idx, const pa_reads *r, const pa::DevParams &p, uint64_t cap,
+                                unsigned long long *counts, CandDev &out, Bufs &b, hipStream_t st) {
     const uint64_t n = r->n;
     const uint32_t G = idx->n_genomes;
     PA_TRY(pa::assign_pass_device(idx, r, p, ~0ull, out.as, b, st));
@@ -426,6 +418,8 @@ pa_status candidates_device(pa_index *idx, const pa_reads *r, const pa::DevParam
     }
     return pa::candidates_pass(idx, r, p, out.queue, d_qcount, nq, out.len, out.off, out.sets, st);
 }
+
+namespace {
 
 // One batch's ambiguous reads reduced to classes and merged into acc->classes.
 pa_status intern_batch(const CandDev &c, pa_abundance *acc, Bufs &b, hipStream_t st) {

@@ -970,6 +970,69 @@ pa_status pa_align_candidates(const pa_index *idx, const pa_reads *reads, const 
                                 as_stream(stream));
 }
 
+// ---- lineages (csrc/pa_lineage.hip) -------------------------------------------------------
+
+pa_status pa_lineage_create(const pa_index *idx, const uint32_t *parent, uint32_t n_nodes,
+                            const uint32_t *genome_node, pa_lineage **out) {
+    PA_CHECK(out != nullptr, PA_EINVAL, "NULL argument");
+    *out = nullptr;
+    PA_TRY(check_index(idx));
+    PA_CHECK(parent != nullptr && (genome_node != nullptr || idx->n_genomes == 0), PA_EINVAL, "NULL argument");
+    PA_CHECK(n_nodes != PA_NO_NODE, PA_EUNSUPPORTED, "a tree holds at most 2^32 - 2 nodes");
+    PA_HIP(hipSetDevice(idx->device));
+    return pa::lineage_create(idx, parent, n_nodes, genome_node, out);
+}
+
+pa_status pa_lineage_reset(pa_lineage *l, void *stream) {
+    PA_CHECK(l != nullptr, PA_EINVAL, "NULL argument");
+    PA_HIP(hipSetDevice(l->device));
+    pa::ErrOp op("pa_lineage_reset");
+    return pa::lineage_reset(l, as_stream(stream));
+}
+
+pa_status pa_lineage_add(const pa_index *idx, const pa_reads *reads, const pa_params *params, pa_lineage *acc,
+                         uint32_t *read_node, void *stream) {
+    PA_CHECK(acc != nullptr, PA_EINVAL, "NULL argument");
+    PA_TRY(check_batch(idx, reads));
+    PA_TRY(check_acc(acc, idx, "pa_lineage"));
+    pa::DevParams dp;
+    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    PA_CHECK(reads->n <= 0xFFFFFFFEull, PA_EUNSUPPORTED, "a batch of a pa_lineage holds at most 2^32 - 2 reads");
+    PA_TRY(prepare_pass(idx, stream));
+    pa::ErrOp op("pa_lineage_add");
+    return pa::lineage_add(const_cast<pa_index *>(idx), reads, dp, acc, read_node, as_stream(stream));
+}
+
+pa_status pa_lineage_counts(const pa_lineage *l, uint64_t *direct, uint64_t *clade, pa_lineage_info *info,
+                            void *stream) {
+    PA_CHECK(l != nullptr, PA_EINVAL, "NULL argument");
+    PA_HIP(hipSetDevice(l->device));
+    pa::ErrOp op("pa_lineage_counts");
+    return pa::lineage_counts(l, direct, clade, info, as_stream(stream));
+}
+
+pa_status pa_lineage_lca(const pa_lineage *l, const uint64_t *set_off, const uint32_t *sets, uint64_t n_sets,
+                         uint32_t *node_out, void *stream) {
+    PA_CHECK(l != nullptr, PA_EINVAL, "NULL argument");
+    PA_CHECK(n_sets == 0 || (set_off && node_out), PA_EINVAL, "NULL argument");
+    PA_CHECK(n_sets <= 0xFFFFFFFEull, PA_EUNSUPPORTED, "pa_lineage_lca takes at most 2^32 - 2 sets a call");
+    if (n_sets) {
+        PA_CHECK(set_off[0] == 0, PA_EINVAL, "set_off must start at 0");
+        for (uint64_t i = 0; i < n_sets; i++)
+            PA_CHECK(set_off[i] <= set_off[i + 1], PA_EINVAL, "set_off must not descend");
+        PA_CHECK(sets != nullptr || set_off[n_sets] == 0, PA_EINVAL, "NULL argument");
+    }
+    PA_HIP(hipSetDevice(l->device));
+    pa::ErrOp op("pa_lineage_lca");
+    return pa::lineage_lca(l, set_off, sets, n_sets, node_out, as_stream(stream));
+}
+
+void pa_lineage_free(pa_lineage *l) {
+    if (!l) return;
+    hipSetDevice(l->device);
+    pa::lineage_free(l);
+}
+
 pa_status pa_profile_enable(pa_index *idx, int32_t enable) {
     PA_CHECK(idx != nullptr, PA_EINVAL, "NULL argument");
     idx->profile = enable != 0;

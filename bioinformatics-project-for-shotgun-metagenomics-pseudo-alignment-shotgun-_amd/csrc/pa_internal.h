@@ -360,6 +360,22 @@ struct pa_abundance : pa::AccBase {
     std::map<std::vector<uint32_t>, uint64_t> classes;  // C -> n_C of the ambiguous reads
 };
 
+// Lineage accumulator of one index (pa_lineage.hip): the caller's tree
+// renumbered in depth-first preorder (pa_tree.h) and the reads counted per
+// node.  The device tables are indexed by preorder number; the counts and
+// everything reported are in the caller's node numbers.
+struct pa_lineage : pa::AccBase {
+    uint32_t n_nodes = 0;
+    std::vector<uint32_t> h_parent;    // [n_nodes] the caller's parent array (the clade sums climb it)
+    std::vector<uint32_t> h_gpre;      // [G] preorder number of genome g's node (the host copy of gpre)
+    uint32_t *parent = nullptr;        // device [n_nodes] preorder number of the parent
+    uint32_t *last = nullptr;          // device [n_nodes] the largest preorder number of the subtree
+    uint32_t *node_of = nullptr;       // device [n_nodes] preorder number -> the caller's node
+    uint32_t *gpre = nullptr;          // device [G]
+    unsigned long long *direct = nullptr;  // device [n_nodes] reads with node(r) == v, the caller's v
+    unsigned long long *counts = nullptr;  // device [4 + G] as pa_abundance's (candidates_device fills it)
+};
+
 struct pa_result {
     int device = 0;
     uint32_t n_genomes = 0;
@@ -500,6 +516,32 @@ pa_status abundance_bootstrap(const pa_abundance *a, uint32_t replicates, uint64
                               uint32_t *iterations, double *last_delta, hipStream_t st);
 pa_status align_candidates(pa_index *idx, const pa_reads *r, const DevParams &p, uint8_t *type, uint64_t *set_off,
                            uint32_t *sets, uint64_t cap, uint64_t *total, hipStream_t st);
+// The candidate pass left on the device (pa_abund.hip; the abundance and the
+// lineage accumulators both start from it).  Held by the caller's Bufs b.
+struct CandDev {
+    AssignDev as;
+    uint32_t *queue = nullptr;   // [n] the ambiguous reads, nq of them
+    uint64_t nq = 0;
+    uint32_t *len = nullptr;     // [n + 1] set sizes
+    uint64_t *off = nullptr;     // [n + 1]
+    uint32_t *sets = nullptr;    // [total] (null when total > cap or 0)
+    uint64_t total = 0;
+};
+// counts: an accumulator's [4 + G] (reads unique, ambiguous, unmapped, dropped; unique reads of g),
+// or null (a scratch array is used).
+pa_status candidates_device(pa_index *idx, const pa_reads *r, const DevParams &p, uint64_t cap,
+                            unsigned long long *counts, CandDev &out, Bufs &b, hipStream_t st);
+// lineage (pa_lineage.hip)
+pa_status lineage_create(const pa_index *idx, const uint32_t *parent, uint32_t n_nodes, const uint32_t *genome_node,
+                         pa_lineage **out);
+pa_status lineage_reset(pa_lineage *l, hipStream_t st);
+void lineage_free(pa_lineage *l);
+pa_status lineage_add(pa_index *idx, const pa_reads *r, const DevParams &p, pa_lineage *acc, uint32_t *read_node,
+                      hipStream_t st);
+pa_status lineage_counts(const pa_lineage *l, uint64_t *direct, uint64_t *clade, pa_lineage_info *info,
+                         hipStream_t st);
+pa_status lineage_lca(const pa_lineage *l, const uint64_t *set_off, const uint32_t *sets, uint64_t n_sets,
+                      uint32_t *node_out, hipStream_t st);
 // pairs (pa_pair.hip; the pair-exact kernel is k_align_exact's sibling in pa_align.hip)
 pa_status pair_exact_pass(pa_index *idx, const pa_reads *m1, const pa_reads *m2, const DevParams &p,
                           const uint32_t *d_queue, const unsigned long long *d_count, uint64_t n_queued,

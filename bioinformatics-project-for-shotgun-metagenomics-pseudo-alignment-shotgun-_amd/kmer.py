@@ -46,6 +46,7 @@ import numpy as np
 
 import constants
 import pa_native as N
+from lineage import ASSIGNMENTS_TAXON_HEADER, Lineages, LineageTree, lineage_report_rows, lineage_report_text
 from records import FASTAQRecordContainer, FASTARecordContainer, Record
 
 IGNORE_AMBIGUOUS_THRESHOLD = 0
@@ -551,11 +552,13 @@ class _Batch:
     ``all_dropped``: every read failed --min-read-quality on the host (no GPU
     pass was needed, see _align_columns)."""
 
-    __slots__ = ("base", "ids", "seq", "qual", "off", "params", "mrq", "entries", "all_dropped", "_dropped")
+    __slots__ = ("base", "ids", "seq", "qual", "off", "params", "mrq", "entries", "all_dropped", "_dropped",
+                 "read_node")
 
     def __init__(self, base, ids, seq, qual, off, params, mrq, all_dropped=False):
         self.base, self.ids, self.seq, self.qual, self.off, self.params = base, ids, seq, qual, off, params
         self.mrq, self.all_dropped, self.entries, self._dropped = mrq, all_dropped, None, None
+        self.read_node = None  # (lineages: every read's node, uint32, N.NO_NODE for none; 4 B per read)
 
     def load(self) -> None:
         pass
@@ -690,6 +693,12 @@ _PILEUP: "weakref.WeakKeyDictionary[PseudoAlignment, list]" = weakref.WeakKeyDic
 # _COVERAGE and for the same reason.
 _ABUNDANCE: "weakref.WeakKeyDictionary[PseudoAlignment, Optional[N.Abundance]]" = weakref.WeakKeyDictionary()
 
+# Lineage state of the alignments made with lineages=..., kept like _COVERAGE and
+# for the same reason: [Lineages, tree or None, accumulator or None, reads of
+# batches dropped whole on the host].  The tree and the accumulator are made
+# with the first batch (or the first report), from the index's genomes.
+_LINEAGE: "weakref.WeakKeyDictionary[PseudoAlignment, list]" = weakref.WeakKeyDictionary()
+
 ABUNDANCE_HEADER = "#genome\tlength\tunique_reads\tcompatible_reads\testimated_reads\tread_fraction\tabundance\n"
 
 
@@ -793,10 +802,21 @@ class PseudoAlignment:
     ``abundance=True`` (not in the reference either): every read of those batches
     is counted in its compatibility class, and ``get_abundance`` /
     ``write_abundance`` report an EM estimate of the genomes' shares of the
-    sample."""
+    sample.
+
+    ``lineages=Lineages(...)`` (not in the reference either): every read of those
+    batches gets a node of the genomes' taxonomy tree -- its genome's node, or
+    the lowest common ancestor of its compatibility set -- and
+    ``get_lineage_report`` / ``write_lineage_report`` report the reads per node
+    and clade; ``write_assignments`` gains a ``taxon`` column."""
 
     def __init__(self, kmer_reference: KmerReference, coverage: bool = False, pileup: bool = False,
-                 min_base_quality: Optional[int] = None, abundance: bool = False) -> None:
+                 min_base_quality: Optional[int] = None, abundance: bool = False,
+                 lineages: Optional[Lineages] = None) -> None:
+        if lineages is not None:
+            if not isinstance(lineages, Lineages):
+                raise ValueError("lineages must be a Lineages")
+            _LINEAGE[self] = [lineages, None, None, 0]
         if abundance:
             _ABUNDANCE[self] = None  # (the accumulator is made with the first batch)
         if coverage:
@@ -888,7 +908,7 @@ class PseudoAlignment:
         from data_file import FASTAQFile
         # (a coverage job takes the host-parsed path: the placements need the read columns)
         fresh = (not self._batches and not self._host and self._result is None and self not in _COVERAGE
-                 and self not in _PILEUP and self not in _ABUNDANCE)
+                 and self not in _PILEUP and self not in _ABUNDANCE and self not in _LINEAGE)
         err = _check_align_args(self.kmer_reference, m, p, min_read_quality, min_kmer_quality, max_genomes)
         n = None
         if fresh and err is None and os.environ.get("PA_STREAM", "1") != "0":
@@ -950,8 +970,12 @@ class PseudoAlignment:
         self._add_ids(ids, np.ones(n, dtype=bool) if all_dropped else dropped, unique_batch)
         ref = self.kmer_reference
         prm = None
+        read_node = None
         if all_dropped:
             self.filtered_quality_reads += n
+            if self in _LINEAGE:
+                _LINEAGE[self][3] += n
+                read_node = np.full(n, N.NO_NODE, dtype=np.uint32)
         else:
             if self._result is None:
                 self._result = N.Result(ref.index)
@@ -968,6 +992,8 @@ class PseudoAlignment:
                 self._pileup().add(reads, prm, _PILEUP[self][1])
             if self in _ABUNDANCE:
                 self._abundance().add(reads, prm)
+            if self in _LINEAGE:
+                read_node = self._lineage().add(reads, prm)
             reads.close()
             delta = stats - self._gpu_stats
             self._gpu_stats = stats
@@ -976,6 +1002,7 @@ class PseudoAlignment:
             self.filtered_hr_kmers += int(delta[5])
         b = _Batch(self._next_index, ids, seq, qual, off, prm, mrq, all_dropped)
         b._dropped = dropped
+        b.read_node = read_node
         self._batches.append(b)
         if self._ids is not None:
             d = b.dropped()
@@ -993,6 +1020,8 @@ class PseudoAlignment:
         complemented here, so paired data wants a both-strand reference."""
         if self in _COVERAGE or self in _PILEUP or self in _ABUNDANCE:
             raise ValueError("pairs are not supported with coverage, pileup or abundance: those accumulators take reads")
+        if self in _LINEAGE:
+            raise ValueError("pairs are not supported with lineages: that accumulator takes reads")
         ids1, seq1, qual1, off1 = _columnar(reads1)
         ids2, seq2, qual2, off2 = _columnar(reads2)
         if len(ids1) != len(ids2):
@@ -1080,25 +1109,39 @@ class PseudoAlignment:
         line per read in the order the reads were added (assignment_line).
         Reads dropped by --min-read-quality are written as ``filtered``, so a
         FASTQ file gives as many lines as it has records.  Written batch by
-        batch from the device's per-read arrays; the ``reads`` dict is not built."""
+        batch from the device's per-read arrays; the ``reads`` dict is not built.
+        An alignment made with ``lineages`` writes a fourth column ``taxon``
+        (ASSIGNMENTS_TAXON_HEADER): the path of the read's node, empty for a read
+        without one."""
         ref = self.kmer_reference
         names = [g.identifier for g in ref.genomes]
-        fh.write(ASSIGNMENTS_HEADER)
+        # lineages: a fourth column, the path of the read's node (empty: none, or a read of add_read())
+        paths = self._lineage_tree().paths if self in _LINEAGE else None
+
+        def line(rid, mapping_type, genomes, node=N.NO_NODE) -> str:
+            text = assignment_line(rid, mapping_type, genomes)
+            if paths is None:
+                return text
+            return text[:-1] + "\t" + (paths[int(node)] if int(node) != N.NO_NODE else "") + "\n"
+
+        def node_of(b, i):
+            return N.NO_NODE if b.read_node is None else b.read_node[i]
+        fh.write(ASSIGNMENTS_HEADER if paths is None else ASSIGNMENTS_TAXON_HEADER)
         parts: List[Tuple[int, Any]] = [(b.base, b) for b in self._batches] + [(i, (rid, e)) for i, rid, e in self._host]
         parts.sort(key=lambda x: x[0])
         for _, part in parts:
             if isinstance(part, tuple):  # a read of add_read()
                 rid, e = part
-                fh.write(assignment_line(rid, int(e["mapping_type"].value), e["genomes_mapped_to"]))
+                fh.write(line(rid, int(e["mapping_type"].value), e["genomes_mapped_to"]))
                 continue
             b = part
             b.load()
             if b.all_dropped:
-                fh.writelines(assignment_line(rid, _DROPPED, ()) for rid in b.ids)
+                fh.writelines(line(rid, _DROPPED, ()) for rid in b.ids)
                 continue
             types, loff, lists = b.results(ref.index)
             loff = loff.astype(np.int64)
-            fh.writelines(assignment_line(rid, int(types[i]), [names[int(g)] for g in lists[loff[i]:loff[i + 1]]])
+            fh.writelines(line(rid, int(types[i]), [names[int(g)] for g in lists[loff[i]:loff[i + 1]]], node_of(b, i))
                           for i, rid in enumerate(b.ids))
 
     def get_summary(self) -> Dict[str, Dict[str, Union[int, Dict[str, int]]]]:
@@ -1248,6 +1291,10 @@ class PseudoAlignment:
         ``abundance=True`` (or loaded from a file), iterations outside 1 .. 10000,
         a negative tolerance, bootstraps outside 0 .. 10000, a seed outside
         0 .. 2^64 - 1 and a confidence bootstrap_summary refuses."""
+        return self._abundance_estimates(iterations, tolerance, bootstraps, seed, confidence)[0]
+
+    def _abundance_estimates(self, iterations, tolerance, bootstraps, seed, confidence):
+        """(get_abundance's dict, the replicates x genomes abundance matrix or None)."""
         if self not in _ABUNDANCE:
             raise ValueError("this alignment was made without abundance=True")
         if isinstance(iterations, bool) or not isinstance(iterations, int) or not 1 <= iterations <= 10000:
@@ -1273,12 +1320,13 @@ class PseudoAlignment:
                             "compatible_reads": int(compatible[g]), "estimated_reads": float(theta[g]) * n_reads,
                             "read_fraction": float(theta[g]), "abundance": float(share[g])} for g in range(G)],
                "reads": n_reads, "iterations": done, "last_delta": delta, "classes": int(cnt.size)}
+        shares = None
         if bootstraps:
             shares = ab.bootstrap(bootstraps, seed, iterations, float(tolerance))[1]
             for row, stats in zip(out["genomes"], bootstrap_summary(shares, confidence)):
                 row.update(zip(ABUNDANCE_BOOTSTRAP_COLUMNS, stats))
             out.update(bootstraps=bootstraps, seed=seed, confidence=float(confidence))
-        return out
+        return out, shares
 
     def write_abundance(self, fh, iterations: int = 200, tolerance: float = 1e-9, bootstraps: int = 0, seed: int = 1,
                         confidence: float = 0.95) -> None:
@@ -1293,6 +1341,66 @@ class PseudoAlignment:
                                 [r["unique_reads"] for r in rows], [r["compatible_reads"] for r in rows],
                                 [r["read_fraction"] for r in rows], [r["abundance"] for r in rows], a["reads"],
                                 a["iterations"], a["last_delta"], a["classes"], boot))
+
+    def _lineage_tree(self) -> LineageTree:
+        slot = _LINEAGE[self]
+        if slot[1] is None:
+            slot[1] = slot[0].tree([g.identifier for g in self.kmer_reference.genomes])
+        return slot[1]
+
+    def _lineage(self) -> "N.Lineage":
+        slot = _LINEAGE[self]
+        if slot[2] is None:
+            tree = self._lineage_tree()
+            slot[2] = N.Lineage(self.kmer_reference.index, tree.parent, tree.genome_node)
+        return slot[2]
+
+    def get_lineage_report(self, iterations: int = 200, tolerance: float = 1e-9, bootstraps: int = 0, seed: int = 1,
+                           confidence: float = 0.95) -> Dict[str, Any]:
+        """The reads rolled up the lineage tree: ``{"rows":
+        [{"node", "taxon", "depth", "genomes", "reads_clade", "reads_direct",
+        "clade_share"}, ...], "reads", "classified", "unmapped", "dropped",
+        "nodes"}``, one row per node in preorder (children in node order).  An
+        alignment that also has ``abundance=True`` gains per row "read_fraction"
+        and "abundance" -- the genomes' estimates summed over the subtree in
+        ascending genome index -- and "iterations", "last_delta" and "classes";
+        with ``bootstraps`` the four ABUNDANCE_BOOTSTRAP_COLUMNS per row, from
+        bootstrap_summary of the replicates x nodes matrix rolled up the same way.
+        The arguments are get_abundance's and are read only with abundance.
+        ValueError for an alignment made without ``lineages``."""
+        if self not in _LINEAGE:
+            raise ValueError("this alignment was made without lineages")
+        tree = self._lineage_tree()
+        direct, clade, info = self._lineage().counts()
+        rows = lineage_report_rows(tree, direct, clade)
+        dropped = info["reads_dropped"] + _LINEAGE[self][3]
+        out: Dict[str, Any] = {"rows": rows, "classified": int(clade[0]), "unmapped": info["reads_unmapped"],
+                               "dropped": dropped, "nodes": tree.n_nodes}
+        out["reads"] = out["classified"] + out["unmapped"] + dropped
+        if self in _ABUNDANCE:
+            a, shares = self._abundance_estimates(iterations, tolerance, bootstraps, seed, confidence)
+            theta = tree.roll_up([g["read_fraction"] for g in a["genomes"]])
+            share = tree.roll_up([g["abundance"] for g in a["genomes"]])
+            for r in rows:
+                r["read_fraction"], r["abundance"] = theta[r["node"]], share[r["node"]]
+            out.update(iterations=a["iterations"], last_delta=a["last_delta"], classes=a["classes"])
+            if shares is not None:
+                rolled = np.array([tree.roll_up(rep) for rep in shares], dtype=np.float64).reshape(len(shares), -1)
+                summary = bootstrap_summary(rolled, confidence)
+                for r in rows:
+                    r.update(zip(ABUNDANCE_BOOTSTRAP_COLUMNS, summary[r["node"]]))
+                out.update(bootstraps=a["bootstraps"], seed=a["seed"], confidence=a["confidence"])
+        return out
+
+    def write_lineage_report(self, fh, iterations: int = 200, tolerance: float = 1e-9, bootstraps: int = 0,
+                             seed: int = 1, confidence: float = 0.95) -> None:
+        """get_lineage_report as text (lineage.lineage_report_text)."""
+        rep = self.get_lineage_report(iterations, tolerance, bootstraps, seed, confidence)
+        ab = None
+        if "iterations" in rep:
+            boot = (rep["bootstraps"], rep["seed"], rep["confidence"]) if "bootstraps" in rep else None
+            ab = (rep["iterations"], rep["last_delta"], rep["classes"], boot)
+        fh.write(lineage_report_text(rep["rows"], rep["reads"], rep["unmapped"], rep["dropped"], ab))
 
     def get_reads_by_mapping_type(self, mapping_type: ReadMappingType) -> List[str]:
         return [rid for rid, d in self.reads.items() if d["mapping_type"] == mapping_type]

@@ -10,6 +10,7 @@
                      [--variant-min-fraction F] [--variant-min-base-quality Q]]
                     [--abundance FILE [--abundance-iterations N] [--abundance-tolerance X]
                      [--abundance-bootstraps B [--abundance-seed S] [--abundance-confidence X]]]
+                    [--lineages FILE [--lineage-report FILE]]
 
 Same tasks (reference | dumpref | align | dumpalign), flags, flag-combination
 checks, default coercions and error exits as src/main.py:61-402:
@@ -98,6 +99,19 @@ def _has_abundance_flag(argv: List[str]) -> bool:
     return False
 
 
+_LINEAGE_FLAGS = ("--lineages", "--lineage-report")
+
+
+def _has_lineage_flag(argv: List[str]) -> bool:
+    """--lineages / --lineage-report on the command line, in any spelling argparse
+    accepts (as _has_coverage_flag)."""
+    for a in argv:
+        name = a.split("=", 1)[0]
+        if len(name) > 2 and name.startswith("--") and any(f.startswith(name) for f in _LINEAGE_FLAGS):
+            return True
+    return False
+
+
 def _has_reads2_flag(argv: List[str]) -> bool:
     """--reads2 on the command line (`--reads2 X`, `--reads2=X`)."""
     return any(a.split("=", 1)[0] == "--reads2" for a in argv)
@@ -137,6 +151,8 @@ def _early_reads_path(argv: List[str]) -> Optional[str]:
     if _has_variants_flag(argv):  # (and a pileup job: the base counts need the read columns)
         return None
     if _has_abundance_flag(argv):  # (and an abundance job: the candidate pass needs the read columns)
+        return None
+    if _has_lineage_flag(argv):  # (and a lineage job, as an abundance job)
         return None
     if _has_reads2_flag(argv):  # (and a paired job: both files are parsed on the host)
         return None
@@ -267,6 +283,11 @@ def parse_arguments(args: Optional[List[str]] = None) -> argparse.Namespace:
                         help="seed of the bootstrap's resampling, 0 .. 2^64 - 1 (default: 1)")
     parser.add_argument("--abundance-confidence", type=float, default=None, metavar="X",
                         help="confidence level of the bootstrap interval (default: 0.95)")
+    # not in the reference: reads and abundances rolled up a taxonomy tree, dumpalign with --reads
+    parser.add_argument("--lineages", default=None, metavar="FILE",
+                        help="the genomes' lineages, one line per genome: identifier<TAB>name;name;... (root first)")
+    parser.add_argument("--lineage-report", default=None, metavar="FILE",
+                        help="write one line per node of the lineage tree (reads in the clade, on the node) to FILE")
     return parser.parse_args(args)
 
 
@@ -343,7 +364,7 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
                                     prefetch=None, per_read: bool = False,
                                     coverage: bool = False, assignments: bool = False,
                                     pileup: bool = False, min_base_quality=None,
-                                    abundance: bool = False) -> PseudoAlignment:
+                                    abundance: bool = False, lineages=None) -> PseudoAlignment:
     # the FASTQ file goes straight to the device (parsed there, aligned in
     # windows); a file outside that subset of the grammar is parsed the exact
     # way (FASTAQFile), which also raises the reference's errors.  per_read
@@ -355,9 +376,16 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
     # coverage: the reads are parsed on the host and aligned on one device (align_reads_from_file
     # then takes its exact path: the placements need the read columns)
     # pileup: likewise (the base counts need the read columns); abundance: likewise (the candidate pass does)
+    # lineages: likewise (its pass is the candidate pass); the tree is made over the index's genomes, now,
+    # so that a genome without a lineage ends the job before a read is aligned
     alignment = (PseudoAlignment(kmer_reference, coverage=coverage, pileup=pileup, min_base_quality=min_base_quality,
-                                 abundance=abundance)
-                 if coverage or pileup or abundance else PseudoAlignment(kmer_reference))
+                                 abundance=abundance, lineages=lineages)
+                 if coverage or pileup or abundance or lineages is not None else PseudoAlignment(kmer_reference))
+    if lineages is not None:
+        try:
+            alignment._lineage_tree()
+        except ValueError as err:
+            sys.exit(f"Error: {err} in lineage file.")
     # assignments: the host parse too -- every read's line needs its id and the read columns
     if per_read or assignments:
         alignment.align_reads_from_container(FASTAQFile(reads_file).container, m, p, min_read_quality,
@@ -383,6 +411,19 @@ def create_alignment_from_pairs(kmer_reference: KmerReference, reads_file: str, 
         sys.exit(f"Error: {err}")
     _stage("pairs aligned")
     return alignment
+
+
+def _load_lineages(args: argparse.Namespace):
+    """The --lineages file, parsed once (main() reads it before any device work); None without the flag."""
+    if args.lineages is None:
+        return None
+    if getattr(args, "_lineages", None) is None:
+        from lineage import Lineages
+        try:
+            args._lineages = Lineages.from_file(args.lineages)
+        except ValueError as err:
+            sys.exit(f"Error: {err}")
+    return args._lineages
 
 
 def _print_json(obj) -> None:
@@ -464,6 +505,18 @@ def _check_task(args: argparse.Namespace) -> None:
                 0 < args.abundance_confidence < 1 and 1 <= int(round(1000 * args.abundance_confidence)) <= 999):
             sys.exit("Error: --abundance-confidence must be in 0.001 .. 0.999.")
         validate_file_writable(args.abundance, "Abundance output")
+    if args.lineage_report is not None and args.lineages is None:
+        sys.exit("Error: --lineage-report needs --lineages.")
+    if args.lineages is not None:
+        if args.lineage_report is None and args.assignments is None:
+            sys.exit("Error: --lineages needs --lineage-report (or --assignments, whose lines then gain the taxon).")
+        if args.task != "dumpalign" or not args.reads:
+            sys.exit("Error: --lineages is only allowed for task 'dumpalign' with --reads.")
+        if args.reads2 is not None:
+            sys.exit("Error: --reads2 cannot be combined with --lineages (the lineage pass takes single reads).")
+        validate_file_readable(args.lineages, "Lineages")
+        if args.lineage_report is not None:
+            validate_file_writable(args.lineage_report, "Lineage report output")
     if args.task == "reference":
         if extra:
             sys.exit("Error: For task 'reference', only -g, -k, -r, --filter-similar, and --similarity-threshold "
@@ -530,13 +583,17 @@ def _print_alignment(alignment: PseudoAlignment, args: argparse.Namespace) -> No
             alignment.write_variants(fh, 4 if args.variant_min_depth is None else args.variant_min_depth,
                                      2 if args.variant_min_count is None else args.variant_min_count,
                                      0.2 if args.variant_min_fraction is None else args.variant_min_fraction)
+    em = (200 if args.abundance_iterations is None else args.abundance_iterations,
+          1e-9 if args.abundance_tolerance is None else args.abundance_tolerance,
+          args.abundance_bootstraps or 0,
+          1 if args.abundance_seed is None else args.abundance_seed,
+          0.95 if args.abundance_confidence is None else args.abundance_confidence)
     if args.abundance is not None:
         with open(args.abundance, "w") as fh:
-            alignment.write_abundance(fh, 200 if args.abundance_iterations is None else args.abundance_iterations,
-                                      1e-9 if args.abundance_tolerance is None else args.abundance_tolerance,
-                                      args.abundance_bootstraps or 0,
-                                      1 if args.abundance_seed is None else args.abundance_seed,
-                                      0.95 if args.abundance_confidence is None else args.abundance_confidence)
+            alignment.write_abundance(fh, *em)
+    if args.lineage_report is not None:  # (with --abundance: its estimates rolled up the tree, under the same settings)
+        with open(args.lineage_report, "w") as fh:
+            alignment.write_lineage_report(fh, *em)
 
 
 def _run(args: argparse.Namespace) -> None:
@@ -586,7 +643,7 @@ def _run(args: argparse.Namespace) -> None:
                 _print_alignment(create_alignment_from_pairs(ref, args.reads, args.reads2, *filt), args)
                 return
             host_parsed = (args.coverage or args.assignments is not None or args.variants is not None
-                           or args.abundance is not None)
+                           or args.abundance is not None or args.lineages is not None)
             pf = None if host_parsed else _prefetch_reads(args.reads)
             ref = _load_reference(args.referencefile)
             _check_strands(args, ref)
@@ -595,7 +652,8 @@ def _run(args: argparse.Namespace) -> None:
                                                              assignments=args.assignments is not None,
                                                              pileup=args.variants is not None,
                                                              min_base_quality=args.variant_min_base_quality,
-                                                             abundance=args.abundance is not None), args)
+                                                             abundance=args.abundance is not None,
+                                                             lineages=_load_lineages(args)), args)
         elif args.genomefile and args.kmer_size and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
             validate_file_readable(args.genomefile, "Genome FASTA")
@@ -610,7 +668,7 @@ def _run(args: argparse.Namespace) -> None:
             # an assignments job too: its lines come from one host-parsed batch; a pileup job and an
             # abundance job, as coverage)
             host_parsed = (args.coverage or args.assignments is not None or args.variants is not None
-                           or args.abundance is not None)
+                           or args.abundance is not None or args.lineages is not None)
             sharded = None if host_parsed else _dumpalign_sharded(args, filt)
             if sharded is not None:
                 _print_json(sharded.get_summary())
@@ -623,7 +681,8 @@ def _run(args: argparse.Namespace) -> None:
                                                              assignments=args.assignments is not None,
                                                              pileup=args.variants is not None,
                                                              min_base_quality=args.variant_min_base_quality,
-                                                             abundance=args.abundance is not None), args)
+                                                             abundance=args.abundance is not None,
+                                                             lineages=_load_lineages(args)), args)
         elif args.alignfile:
             validate_file_readable(args.alignfile, "Alignment output")
             try:
@@ -641,6 +700,7 @@ def main(argv: Optional[List[str]] = None) -> None:
     _stage("imports done")
     args = parse_arguments(argv)
     _check_task(args)
+    _load_lineages(args)  # (a file the parser refuses ends the job here)
     # falsy -> default, as src/main.py:337-342 (so -m 0 and -p 0 become 1)
     if not args.unique_threshold:
         args.unique_threshold = DEFAULT_UNIQUE_THRESHOLD

@@ -34,6 +34,8 @@ PA_POS_REVERSE, PA_POS_RC_BIT = 1, 0x80000000
 PA_READS_UNKNOWN = 2 ** 64 - 1
 PA_NB_READS_PER_KBASE = 2500  # (include/pa.h: the neighbour bits' break-even, reads per 1000 genome bases)
 PA_NB_READS_PER_KBASE_2W, PA_NB_READS_PER_KBASE_3W = 10000, 18000  # (two- / three-word keys)
+NO_NODE = 0xFFFFFFFF  # PA_NO_NODE: a read no node of the lineage tree holds
+LINEAGE_LDS_NODES = 4096  # PA_LINEAGE_LDS_NODES (include/pa.h: the largest tree counted through the LDS histogram)
 
 # every symbol declared in include/pa.h
 EXPORTS = (
@@ -55,6 +57,7 @@ EXPORTS = (
     "pa_pileup_variants", "pa_pileup_free",
     "pa_abundance_create", "pa_abundance_reset", "pa_abundance_add", "pa_abundance_info_get", "pa_abundance_classes",
     "pa_abundance_estimate", "pa_abundance_bootstrap", "pa_abundance_free", "pa_align_candidates",
+    "pa_lineage_create", "pa_lineage_reset", "pa_lineage_add", "pa_lineage_counts", "pa_lineage_lca", "pa_lineage_free",
     "pa_profile_enable", "pa_profile_read", "pa_profile_read_kernels", "pa_mem_trim",
     "pa_parse_text", "pa_parse_file", "pa_seqset_sizes", "pa_seqset_export", "pa_seqset_free", "pa_gz_inflate_file",
 )
@@ -101,6 +104,11 @@ class PileupStats(ctypes.Structure):
 class AbundanceInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("reads_unique", "reads_ambiguous", "reads_unmapped", "reads_dropped",
                                                "n_classes", "class_entries")]
+
+
+class LineageInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("reads_unique", "reads_ambiguous", "reads_unmapped", "reads_dropped")] \
+        + [("n_nodes", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 # pa_variant, one record of Pileup.variants (40 bytes, no implicit padding)
@@ -213,6 +221,12 @@ def lib():
         "pa_abundance_bootstrap": (I32, [P, U32, U64, U32, ctypes.c_double, P, P, P, P, P, P]),
         "pa_abundance_free": (None, [P]),
         "pa_align_candidates": (I32, [P, P, ctypes.POINTER(Params), P, P, P, U64, ctypes.POINTER(U64), P]),
+        "pa_lineage_create": (I32, [P, P, U32, P, PP]),
+        "pa_lineage_reset": (I32, [P, P]),
+        "pa_lineage_add": (I32, [P, P, ctypes.POINTER(Params), P, P, P]),
+        "pa_lineage_counts": (I32, [P, P, P, ctypes.POINTER(LineageInfo), P]),
+        "pa_lineage_lca": (I32, [P, P, P, U64, P, P]),
+        "pa_lineage_free": (None, [P]),
         "pa_profile_enable": (I32, [P, I32]),
         "pa_profile_read": (I32, [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.POINTER(U64)]),
         "pa_profile_read_kernels": (I32, [P, P, P]),
@@ -1331,6 +1345,72 @@ class Abundance:
     def close(self):
         if getattr(self, "_h", None):
             lib().pa_abundance_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class Lineage:
+    """Every read's node in a taxonomy tree and the reads counted per node
+    (pa_lineage).  ``parent``: parent[0] == 0 and
+    parent[i] < i; ``genome_node``: a node for every genome of the index.
+    ``add`` classifies a batch as align_detail does and returns every read's
+    node (NO_NODE: none), ``counts`` reads the direct and clade counts,
+    ``lca`` runs the reduction alone on the caller's genome sets."""
+
+    def __init__(self, index: Index, parent, genome_node):
+        par = np.ascontiguousarray(parent, dtype=np.uint32)
+        gn = np.ascontiguousarray(genome_node, dtype=np.uint32)
+        if par.ndim != 1 or gn.ndim != 1 or gn.size != index.n_genomes:
+            raise ValueError("parent must be one-dimensional and genome_node hold one node per genome of the index")
+        h = P()
+        _check(lib().pa_lineage_create(index.handle, _ptr(par), int(par.size), _ptr(gn) if gn.size else None,
+                                       ctypes.byref(h)))
+        self._h = h
+        self._index = index  # (kept alive: the accumulator is checked against it)
+        self.n_genomes = index.n_genomes
+        self.n_nodes = int(par.size)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def add(self, reads: Reads, params: Params, nodes: bool = True, stream=None) -> Optional[np.ndarray]:
+        """Count a batch; with ``nodes`` its per-read node array (uint32) is returned."""
+        out = np.zeros(max(reads.n, 1), dtype=np.uint32) if nodes else None
+        _check(lib().pa_lineage_add(self._index.handle, reads.handle, ctypes.byref(params), self._h, _ptr(out),
+                                    _stream(stream)))
+        return out[:reads.n] if nodes else None
+
+    def reset(self, stream=None) -> None:
+        _check(lib().pa_lineage_reset(self._h, _stream(stream)))
+
+    def counts(self, stream=None):
+        """(direct [n_nodes], clade [n_nodes], info) since the last reset: uint64
+        arrays in the caller's node numbers and {"reads_unique", "reads_ambiguous",
+        "reads_unmapped", "reads_dropped", "n_nodes"}."""
+        direct = np.zeros(self.n_nodes, dtype=np.uint64)
+        clade = np.zeros(self.n_nodes, dtype=np.uint64)
+        s = LineageInfo()
+        _check(lib().pa_lineage_counts(self._h, _ptr(direct), _ptr(clade), ctypes.byref(s), _stream(stream)))
+        return direct, clade, {n: int(getattr(s, n)) for n, _ in LineageInfo._fields_ if n != "reserved"}
+
+    def lca(self, set_off, sets, stream=None) -> np.ndarray:
+        """node[i] = the lowest common ancestor of the genomes' nodes over set i of
+        the CSR (set_off [n + 1], sets); NO_NODE for an empty set."""
+        off = np.ascontiguousarray(set_off, dtype=np.uint64)
+        flat = np.ascontiguousarray(sets, dtype=np.uint32)
+        if off.ndim != 1 or off.size < 1 or flat.ndim != 1 or int(off[-1]) != flat.size:
+            raise ValueError("set_off must hold n + 1 offsets ending at len(sets)")
+        n = off.size - 1
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        _check(lib().pa_lineage_lca(self._h, _ptr(off), _ptr(flat) if flat.size else None, n, _ptr(out),
+                                    _stream(stream)))
+        return out[:n]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().pa_lineage_free(self._h)
             self._h = None
 
     __del__ = close

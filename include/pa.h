@@ -43,6 +43,9 @@
  *   pa_align_candidates      compatibility classes and an EM over them; no reference counterpart: the
  *                            definition is DESIGN.md section 14 (T_r(g) is generate_genome_counts(
  *                            map_count=False), src/kmer.py:431-442)
+ *   pa_lineage_*             every read's node in a taxonomy tree (the lowest common ancestor of its
+ *                            compatibility set) and the reads per node and clade (--lineages); no
+ *                            reference counterpart: the definition is DESIGN.md section 17
  *   pa_align_batch           one-shot host-buffer form of pa_align
  *   pa_align_fastq_file      FASTAQFile + align_reads_from_container as one
  *                            device-parsed stream                          src/data_file.py:134-158,
@@ -576,6 +579,65 @@ void pa_abundance_free(pa_abundance *a);
 pa_status pa_align_candidates(const pa_index *idx, const pa_reads *reads, const pa_params *params,
                               uint8_t *read_type, uint64_t *set_off, uint32_t *sets, uint64_t cap,
                               uint64_t *total, void *stream);
+
+/* ---- lineages: reads and counts rolled up a taxonomy tree ----
+ *
+ * The tree: nodes 0 .. n_nodes - 1, node 0 the root, parent[0] == 0 and
+ * parent[i] < i for i >= 1; genome_node[g], for every genome of the index, is
+ * any node (not necessarily a leaf; several genomes may share one).
+ *
+ * Every read is classified as pa_align_detail classifies it with the same
+ * params.  node(r): PA_NO_NODE for a dropped, unmapped or shorter-than-k read;
+ * genome_node[g] for a PA_UNIQUELY_MAPPED read with list [g]; for a
+ * PA_AMBIGUOUSLY_MAPPED read (a p-demoted one included) the lowest common
+ * ancestor of genome_node[g] over g in C(r), the compatibility set
+ * pa_align_candidates returns (never empty; not genomes_mapped_to).
+ *
+ * direct[v] = the reads with node(r) == v; clade[v] = the sum of direct over
+ * v's subtree, so clade[0] = the classified reads = unique + ambiguous.  64-bit
+ * integers summed with integer atomics only: the same reads give the same
+ * counts in whatever batches they come.
+ *
+ * The library renumbers the nodes in depth-first preorder at creation; the
+ * lowest common ancestor of a set is then that of its smallest and its largest
+ * preorder number, one climb (a read costs one min/max scan of its set and one
+ * climb).  Everything reported is in the caller's node numbers.  direct goes
+ * through a histogram in LDS, flushed per workgroup, for trees of up to
+ * PA_LINEAGE_LDS_NODES nodes (16 KiB of uint32 counters: eight workgroups of
+ * 256 threads per CU, every wave slot, within the 160 KiB of LDS), through
+ * 64-bit global atomics above (PA_LINEAGE_LDS=0 in the environment, read per
+ * call: global atomics for every tree; the same counts).
+ *
+ * PA_EINVAL: n_nodes == 0, parent[0] != 0, parent[i] >= i, genome_node[g] >=
+ * n_nodes; an accumulator used with another index, or with its own after a
+ * pa_index_reduce.  PA_EUNSUPPORTED: more than 2^32 - 2 nodes, reads in a batch
+ * or sets in a call.  PA_ENOMEM leaves the index usable.  The accumulator's
+ * bytes are not part of pa_index_info; a lineage job runs on one device. */
+#define PA_NO_NODE 0xFFFFFFFFu
+#define PA_LINEAGE_LDS_NODES 4096
+typedef struct pa_lineage pa_lineage;
+typedef struct {
+    uint64_t reads_unique, reads_ambiguous, reads_unmapped, reads_dropped;
+    uint32_t n_nodes, reserved;
+} pa_lineage_info;
+pa_status pa_lineage_create(const pa_index *idx, const uint32_t *parent, uint32_t n_nodes,
+                            const uint32_t *genome_node, pa_lineage **out);
+pa_status pa_lineage_reset(pa_lineage *l, void *stream);
+/* read_node: host [reads], nullable.  Returns when done; after an error `acc`
+ * may hold a part of the batch: reset it. */
+pa_status pa_lineage_add(const pa_index *idx, const pa_reads *reads, const pa_params *params, pa_lineage *acc,
+                         uint32_t *read_node, void *stream);
+/* direct / clade: n_nodes entries each; any output may be NULL. */
+pa_status pa_lineage_counts(const pa_lineage *l, uint64_t *direct, uint64_t *clade, pa_lineage_info *info,
+                            void *stream);
+/* The reduction alone, on the caller's genome sets (a host CSR: set i is
+ * sets[set_off[i] .. set_off[i + 1]), set_off ascending from 0): node_out[i] =
+ * the lowest common ancestor of genome_node over set i, PA_NO_NODE for an empty
+ * set; a genome >= n_genomes or a descending offset is PA_EINVAL.  The
+ * accumulator's counts are not touched. */
+pa_status pa_lineage_lca(const pa_lineage *l, const uint64_t *set_off, const uint32_t *sets, uint64_t n_sets,
+                         uint32_t *node_out, void *stream);
+void pa_lineage_free(pa_lineage *l);
 
 /* upload + pa_align + fetch for host buffers (stats and per-genome arrays accumulate: +=, min) */
 pa_status pa_align_batch(const pa_index *idx, const uint8_t *seq, const uint8_t *qual, const uint64_t *read_off,

@@ -6,6 +6,7 @@ genomes, k = 31, synthesized 150-bp reads, 0.5 % substitutions).
     python scripts/coverage_rate.py --mode coverage [--reads N] [--runs R] [--baseline-json parent.json]
     python scripts/coverage_rate.py --mode assign   [--reads N] [--runs R] [--read-err E --rc-rate X --foreign-rate Y]
     python scripts/coverage_rate.py --mode bootstrap [--reads N] [--runs R] [--replicates B]
+    python scripts/coverage_rate.py --mode lineage  [--reads N] [--runs R]
 
 --mode detail times one pa_align_detail call with its lists (the pass a
 coverage add rides on); run it with PA_LIBRARY=<the parent commit's libpa.so>
@@ -52,6 +53,13 @@ next to each one pa_abundance_estimate with the same settings.  The yardstick
 is B x that estimate -- what a loop over pa_abundance_estimate would cost, with
 no resampling at all -- so ratio_*_over_B_estimates is the call's time over it.
 The draw / EM split comes from a kernel trace of this mode.
+
+--mode lineage times pa_lineage_add next to pa_align_reads
+and pa_abundance_add on the same batch, under a tree whose species are the
+genome families, with and without the node array and under PA_LINEAGE_LDS=0
+(global atomics instead of the LDS histogram).  With PA_LIBRARY naming the
+parent's library (and PA_LIBRARY_PARTIAL=1), which has no pa_lineage_*, the
+line holds the two yardsticks only.
 
 --mode pairs times pa_align_pairs on a both-strand C2
 index: --reads pairs (default 1 000 000) made on the host -- fragments of 300 ..
@@ -212,7 +220,8 @@ def run_pairs(args, genomes, out):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("detail", "coverage", "assign", "pileup", "abundance", "bootstrap", "pairs"),
+    ap.add_argument("--mode", choices=("detail", "coverage", "assign", "pileup", "abundance", "bootstrap", "pairs",
+                                       "lineage"),
                     required=True)
     ap.add_argument("--replicates", type=int, default=100, help="bootstrap replicates of --mode bootstrap")
     ap.add_argument("--reads", type=int, default=None, help="reads (default 10 000 000); pairs with --mode pairs (1 000 000)")
@@ -353,6 +362,39 @@ def main():
         share = holder["b"][1]
         out["abundance_sd_max"] = float(share.std(axis=0, ddof=1).max()) if B > 1 else 0.0
         ab.close()
+    elif args.mode == "lineage":
+        # families of five strains are species, the species hang off the root: an ambiguous read of a
+        # family lands on its species node, so most of them share ten counters
+        species = (args.genomes + 4) // 5
+        parent = [0] + [0] * species + [1 + g // 5 for g in range(args.genomes)]
+        genome_node = [1 + species + g for g in range(args.genomes)]
+        med, ts, entries = time_assign(index, reads, prm, args.runs)
+        out.update(align_reads_s=med, align_reads_runs_s=ts, list_entries=entries)
+        ab = N.Abundance(index)
+        med, ts = timed(lambda: ab.add(reads, prm), args.runs)
+        out.update(abundance_add_s=med, abundance_add_runs_s=ts)
+        ab.close()
+        if not hasattr(N.lib(), "pa_lineage_create"):  # (the parent's library: the two yardsticks only)
+            print(json.dumps(out), flush=True)
+            return
+        lin = N.Lineage(index, parent, genome_node)
+        os.environ.pop("PA_LINEAGE_LDS", None)
+        med, ts = timed(lambda: lin.add(reads, prm, nodes=False), args.runs)
+        out.update(lineage_add_s=med, lineage_add_runs_s=ts, lineage_reads_per_s=args.reads / med,
+                   ratio_lineage_add_over_abundance_add=med / out["abundance_add_s"])
+        med, ts = timed(lambda: lin.add(reads, prm), args.runs)
+        out.update(lineage_add_with_nodes_s=med)
+        os.environ["PA_LINEAGE_LDS"] = "0"
+        med, ts = timed(lambda: lin.add(reads, prm, nodes=False), args.runs)
+        out.update(lineage_add_global_atomics_s=med, lineage_add_global_atomics_runs_s=ts)
+        del os.environ["PA_LINEAGE_LDS"]
+        lin.reset()
+        nodes = lin.add(reads, prm)
+        direct, clade, info = lin.counts()
+        out.update(info=info, nodes=len(parent), reads_on_species_nodes=int(direct[1:1 + species].sum()),
+                   reads_on_root=int(direct[0]), classified=int(clade[0]),
+                   no_node=int((nodes == N.NO_NODE).sum()))
+        lin.close()
     else:
         med, ts, entries = time_detail(index, reads, prm, args.runs)
         out.update(align_detail_branch_s=med, align_detail_branch_runs_s=ts, list_entries=entries)
