@@ -33,7 +33,7 @@ GOLD = os.path.join(REPO, "tests", "golden")
 FA, FQ = os.path.join(GOLD, "config1.fa"), os.path.join(GOLD, "config1.fq")
 
 DROPPED, UNMAPPED, UNIQUE, AMBIGUOUS = 0, 1, 2, 3
-NO_KEY = 2 ** 64 - 1
+NO_KEY = 2 ** 63 - 1  # include/pa.h PA_NO_FIRST_KEY: the first_key of a genome no pair was counted for
 _COMP = str.maketrans("ACGTN", "TGCAN")
 
 
@@ -347,6 +347,53 @@ def test_random_model_vs_oracle(k, both):
     for i in range(len(RAND_PS)):
         rand_model(k, both, i)
     rand_conditions(k, both)
+
+
+# ---- pairs over many genomes: past the membership masks (G > 64), past the LDS counters (G > 2048) ----
+
+LARGE_SHAPES = [(70, 500, 200, 31, 90), (300, 500, 200, 31, 90), (2100, 70, 40, 21, 60)]  # test_gpu_abundance.large_case
+LARGE_PS = [dict(m=1, p=1), dict(m=1, p=1, mg=2), dict(m=0, p=3)]
+
+
+@functools.lru_cache(maxsize=None)
+def large_pairs(shape):
+    """(genomes, pairs) of one large_case shape: its reads (one in three inside the stretch every genome
+    holds, the others anywhere on one genome) paired as neighbours, (2i, 2i + 1), and three apart, (i, i + 3)."""
+    from test_gpu_abundance import large_case
+    genomes, seqs, quals = large_case(*shape)
+    n = len(seqs)
+    ij = [(2 * i, 2 * i + 1) for i in range(n // 2)] + [(i, (i + 3) % n) for i in range(n)]
+    return genomes, [(seqs[a], quals[a], seqs[b], quals[b]) for a, b in ij]
+
+
+@functools.lru_cache(maxsize=None)
+def large_kd(shape, both):
+    return kmer_sets(large_pairs(shape)[0], both, shape[3])
+
+
+@functools.lru_cache(maxsize=None)
+def large_model(shape, both, i):
+    """The model's results of large_pairs(shape) under LARGE_PS[i], oracle-checked."""
+    genomes, pairs = large_pairs(shape)
+    res = model_all(large_kd(shape, both), shape[3], pairs, **LARGE_PS[i])
+    oracle_check(genomes, both, shape[3], pairs, res, LARGE_PS[i])
+    return res
+
+
+@pytest.mark.parametrize("both", [False, True], ids=["forward", "both_strands"])
+@pytest.mark.parametrize("shape", LARGE_SHAPES, ids=[f"{s[0]}_genomes" for s in LARGE_SHAPES])
+def test_large_pairs_model_conditions(shape, both):
+    """What the pairs over 70, 300 and 2100 genomes must hold before a device result is compared with them:
+    pairs the exact kernel has to count over many genomes (UNIQUE against the whole stretch's set, AMBIGUOUS)
+    and, under --max-genomes 2, pairs that lose every k-mer.  The forward model gives UNIQUE / AMBIGUOUS
+    96 / 39, 94 / 41, 54 / 36 and 39, 39, 27 UNMAPPED; the figures of both kinds of index are printed."""
+    res, res_mg = large_model(shape, both, 0), large_model(shape, both, 1)
+    large_model(shape, both, 2)
+    unique, ambiguous = (sum(r[0] == t for r in res) for t in (UNIQUE, AMBIGUOUS))
+    unmapped = sum(r[0] == UNMAPPED for r in res_mg)
+    print(f"G={shape[0]} both={both}: m=1, p=1 UNIQUE / AMBIGUOUS {unique} / {ambiguous}, mg=2 UNMAPPED {unmapped}")
+    assert ambiguous >= 30 and unique >= 50
+    assert unmapped >= 25
 
 
 # ---- pair_identifier --------------------------------------------------------------------------
