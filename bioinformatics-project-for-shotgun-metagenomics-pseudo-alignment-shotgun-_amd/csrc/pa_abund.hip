@@ -775,8 +775,7 @@ pa_status abundance_bootstrap(const pa_abundance *a, uint32_t replicates, uint64
     PA_HIP(hipStreamSynchronize(st));  // (the host vectors above are pageable)
     // the draws: a thread takes 64 of them or more, 256 blocks a replicate at most -- and as many as keep a
     // block's draws under 2^31
-    const char *e = std::getenv("PA_BOOT_LDS");
-    const bool lds = nc <= kBootLdsClasses && !(e && e[0] == '0');
+    const bool lds = nc <= kBootLdsClasses && !pa::env_is("PA_BOOT_LDS", '0');
     const uint64_t per_block = (uint64_t)kBlock * 64;
     const unsigned gx = (unsigned)std::max<uint64_t>(std::min<uint64_t>((N + per_block - 1) / per_block, 256),
                                                      (N + kBootBlockDraws - 1) / kBootBlockDraws);

@@ -987,10 +987,10 @@ size_t fast_lds_bytes(uint32_t G, int wpl, bool need_q) {
 // The environment switches of the align passes (tests and A/B runs), all read
 // here and nowhere else: a pass makes one Switches at its top, on every call --
 // tests flip them between two calls of one process, so nothing is kept.
-const char *env(const char *name) { return std::getenv(name); }
-bool env_is(const char *name, char c) { const char *e = env(name); return e && e[0] == c; }
-uint64_t env_u64(const char *name, uint64_t unset) { const char *e = env(name); return e ? std::strtoull(e, nullptr, 10) : unset; }
-int env_int(const char *name, int unset) { const char *e = env(name); return e ? std::atoi(e) : unset; }
+using pa::env;
+using pa::env_int;
+using pa::env_is;
+using pa::env_u64;
 int env_01(const char *name) { const char *e = env(name); return e ? e[0] == '1' : -1; }  // -1: unset
 
 struct Switches {

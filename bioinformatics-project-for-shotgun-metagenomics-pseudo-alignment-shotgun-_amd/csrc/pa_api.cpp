@@ -148,15 +148,16 @@ pa_status pa_runtime_start(int32_t device) {
     g_runtime_starter.started = true;
     g_runtime_starter.th = std::thread([device] {
         const auto t0 = std::chrono::steady_clock::now();
-        const char *w = std::getenv("PA_RUNTIME_WARM");  // 0: the context only (A/B)
-        if (hipSetDevice(device) == hipSuccess && hipFree(nullptr) == hipSuccess && !(w && w[0] == '0')) {
+        // (PA_RUNTIME_WARM=0: the context only, A/B)
+        if (hipSetDevice(device) == hipSuccess && hipFree(nullptr) == hipSuccess &&
+            !pa::env_is("PA_RUNTIME_WARM", '0')) {
             pa::warm_index(nullptr);  // the code objects too, not at the first real launch
             pa::warm_align(nullptr);
             pa::warm_fastq(nullptr);
             pa::warm_dump(nullptr);
             hipDeviceSynchronize();
         }
-        if (const char *e = std::getenv("PA_CLI_TIMING"); e && e[0] == '1')
+        if (pa::env_is("PA_CLI_TIMING", '1'))
             fprintf(stderr, "[pa_runtime] HIP runtime started in %.1f ms\n",
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     });

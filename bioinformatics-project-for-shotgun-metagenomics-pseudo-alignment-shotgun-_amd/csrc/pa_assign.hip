@@ -103,8 +103,7 @@ pa_status assign_pass_device(pa_index *idx, const pa_reads *r, const DevParams &
     as.len = out.len;
     as.g = (uint32_t *)(blk + b_g);
     as.scratch = blk + b_scr;
-    const char *e = std::getenv("PA_ASSIGN");
-    as.lane = !(e && e[0] == '0');
+    as.lane = !pa::env_is("PA_ASSIGN", '0');
     unsigned long long *d_cnt = (unsigned long long *)(blk + b_cnt);
     // g and type (adjacent) unset; the scratch counters and the count zero; len[n] = 0 (the scan's last input)
     PA_HIP(hipMemsetAsync(blk + b_g, 0xFF, n * 5, st));

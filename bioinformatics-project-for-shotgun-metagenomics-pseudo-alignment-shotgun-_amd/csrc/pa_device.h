@@ -121,7 +121,8 @@ __device__ __forceinline__ void key_push(Key<NW> &k, uint32_t c, uint64_t mask0)
     k.w[0] &= mask0;
 }
 
-__device__ __forceinline__ uint64_t mask0_of(int k, int nw) {
+// The bits of a key's top word (2k bits in nw words); the host's launches pass it to the kernels.
+__host__ __device__ __forceinline__ uint64_t mask0_of(int k, int nw) {
     int bits = 2 * k - 64 * (nw - 1);
     return bits >= 64 ? ~0ull : ((1ull << bits) - 1);
 }
@@ -387,7 +388,7 @@ __device__ __forceinline__ void bloom_word(uint64_t key, int k, uint32_t lg, uin
     const uint32_t mn = k == 31 ? key_minimizer_c<31>(key) : key_minimizer(key, k);
     w = (bloom_block(mn, lg) << kBloomLgBW) | (h >> (32 - kBloomLgBW));
 }
-// The build-time filter of k_nb_build / k_nb_first (its own filter, freed
+// The build-time filter of k_nb_first (its own filter, freed
 // after): blocked by a minimizer of a cheaper order -- the 15-mer XOR a fixed
 // random pattern, one VALU op instead of mm_order's four -- since those kernels
 // compute ~93 of them per window and are VALU-bound as much as memory-bound.

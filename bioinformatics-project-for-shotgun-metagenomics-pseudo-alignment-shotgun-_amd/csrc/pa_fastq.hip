@@ -492,11 +492,6 @@ pa_status parse_align_window(ParseBufs &B, const uint8_t *D, uint64_t lo, uint64
     return PA_OK;
 }
 
-bool env_on(const char *name) {
-    const char *e = std::getenv(name);
-    return e && e[0] == '1';
-}
-
 }  // namespace pa
 
 // ---- prefetch: the whole file into device memory, in the background ---------------
@@ -756,7 +751,7 @@ void fastq_prefetch_free(pa_fastq_prefetch *pf) {
 // index's align-side view made while the copies run.
 pa_status align_fastq_prefetched(pa_index *idx, pa_fastq_prefetch *pf, const DevParams &prm, uint64_t base,
                                  pa_result *acc, hipStream_t st, uint64_t *n_reads) {
-    const bool timing = env_on("PA_STREAM_TIMING");
+    const bool timing = pa::env_is("PA_STREAM_TIMING", '1');
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
         return std::chrono::duration<double, std::milli>(b - a).count();
@@ -828,7 +823,7 @@ pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm
                            uint64_t length, std::vector<uint64_t> *ids_out) {
     ErrOp op("pa_align_fastq_file");
     // PA_STREAM_TIMING=1: where the time goes (stderr)
-    const bool timing = env_on("PA_STREAM_TIMING");
+    const bool timing = pa::env_is("PA_STREAM_TIMING", '1');
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
         return std::chrono::duration<double, std::milli>(b - a).count();

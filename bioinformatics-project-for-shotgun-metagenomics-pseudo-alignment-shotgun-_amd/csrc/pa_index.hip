@@ -4,35 +4,57 @@
 // Index layout in HBM
 //   table          open addressing, linear probing, `cap` slots of
 //                  {uint64 key[NW]; uint32 cls; uint32 tpos} (16 B for k <= 31),
-//                  load factor <= 0.5 (cap = 2 x genome windows).
+//                  whole 64-B lines.  4 slots per genome window when that fits
+//                  a third of the free memory, else 2; a reference too large
+//                  for either is sized on a HyperLogLog estimate of its
+//                  distinct k-mers, 4 / 2.5 / 2 / 1.43 slots per k-mer
+//                  (pa_index_plan.h holds every sizing rule of this file).
 //   classes        the genome SET of a k-mer (the keys of kmers[kmer] in the
 //                  reference) is a "class": cls < G means the singleton {cls};
 //                  cls >= G is a deduplicated multi-genome set stored as the
 //                  record class_genomes[cls - G] = [size, ascending genomes...]
 //                  (one contiguous read in the align kernels; the size serves
 //                  --max-genomes).
-//   tiling         (k <= 31, < 2^32 bases) the genomes concatenated in FASTA
-//                  order as a 2-bit string `tile_pk` plus `tile_cls[t]` = class
-//                  of the k-mer starting at concatenated position t (NONE if no
-//                  indexed window starts there: N bases, genome ends).  A slot's
-//                  tpos is the first position of its key.  A read that matches
-//                  a genome stretch is then resolved by ONE table probe plus a
-//                  contiguous read of tile_cls / tile_pk (pa_fast.h), each
-//                  window still verified base for base against the genome.
+//   tiling         (k <= 95, every genome < 2^32 bases) the genomes concatenated
+//                  in FASTA order as a 2-bit string `tile_pk` plus `tile_cls[t]`
+//                  = class of the k-mer starting at concatenated position t
+//                  (NONE if no indexed window starts there: N bases, genome
+//                  ends).  A slot's tpos is the first position of its key.  A
+//                  read that matches a genome stretch is then resolved by ONE
+//                  table probe plus a contiguous read of the tiling (pa_lane.h),
+//                  each window still verified base for base against the genome.
+//   align view     on top of the tiling, each optional and sized by the free
+//                  memory: walk blocks, one-substitution neighbour words, the
+//                  Bloom filter of the keys, the minimizer bitmap, the
+//                  reverse-complement plane and neighbour words.
 //
-// Build pipeline (all stream-ordered, one host sync at the end)
-//   1. ASCII -> 2-bit codes (4 = anything else, e.g. 'N').
-//   2. per genome in FASTA order: insert every N-free window (atomicCAS claim),
-//      count distinct genomes per slot with a per-slot "last genome" atomicMax
-//      (launch order = FASTA order makes this exact), remember the first genome.
-//   3. singletons get cls = genome; multi slots get a bump-allocated list.
-//   4. per genome again: append g to the list of every multi slot it touches
-//      (ascending order for free, again from launch order).
-//   5. hash every multi list, dedup lists through a second hash table, verify
-//      each list against its class representative element by element (a hash
-//      collision is reported as PA_EINTERNAL, never merged silently), assign
-//      class ids and copy representative lists into class_genomes.
-//   6. tiling: pack the genomes, then per genome look up every window's class.
+// Build pipeline (stream-ordered; the host waits where it needs a count)
+//   index_build    1. ASCII -> 2-bit codes (4 = anything else, e.g. 'N'); a
+//                     both-strand index writes g + N + reverse complement(g).
+//                  2. the table's capacity (above), the table.
+//   build_nw       3. per genome in FASTA order: insert every N-free window
+//                     (atomicCAS claim), count distinct genomes per slot with a
+//                     per-slot "last genome" atomicMax (launch order = FASTA
+//                     order makes this exact), remember the first genome.
+//                  4. singletons get cls = genome; multi slots get a
+//                     bump-allocated list (k_build_prep; the host reads the
+//                     counts).
+//                  5. per genome again: append g to the list of every multi slot
+//                     it touches (ascending order for free, from launch order).
+//                  6. hash every multi list, dedup lists through a second hash
+//                     table that grows on overflow, verify each list against its
+//                     class representative element by element (a hash collision
+//                     is PA_EINTERNAL, never merged silently), assign class ids
+//                     and copy representative lists into class_genomes; then the
+//                     slots of a probe run in home order (k_table_order,
+//                     PA_TABLE_ORDER).
+//   index_prepare  7. the align view, one named step each (tile_* below): at the
+//                     end of the build, or deferred (PA_BUILD_DEFER_TILES) to
+//                     pa_index_prepare / the first align; the neighbour words may
+//                     wait further, for the reads that repay them
+//                     (index_note_reads).
+// What an index owns is listed once: release_align_view (pa_internal.h) for
+// step 7's buffers and state, index_release for the rest.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,28 +68,29 @@
 #include <vector>
 
 #include "pa_device.h"
+#include "pa_index_plan.h"
 #include "pa_internal.h"
 
 using namespace pad;
+namespace plan = pa::plan;
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kRun = 16;  // windows per thread in the genome scans
-// PA_BATCHED_INSERT=0 (compile time): the round-5 one-window-at-a-time insert
-// and fill passes for single-word keys (A/B)
-#ifndef PA_BATCHED_INSERT
-#define PA_BATCHED_INSERT 1
-#endif
-constexpr bool kBatchedInsert = PA_BATCHED_INSERT != 0;
+
+using pa::env;
+using pa::env_int;
+using pa::env_is;
+using pa::env_u64;
 
 // Windows per thread of the per-genome build scans (insert, fill, tile
-// classes): PA_BUILD_RUN overrides (A/B).  Fewer per thread = more threads in
-// flight per genome launch (the scans are chains of dependent random atomics).
+// classes): PA_BUILD_RUN overrides (A/B; read once per process).  Fewer per
+// thread = more threads in flight per genome launch (the scans are chains of
+// dependent random atomics).
 inline int build_run() {
     static const int r = [] {
-        const char *e = std::getenv("PA_BUILD_RUN");
-        const int v = e ? std::atoi(e) : 0;
+        const int v = env_int("PA_BUILD_RUN", 0);
         return v > 0 && v <= 256 ? v : kRun;
     }();
     return r;
@@ -79,9 +102,7 @@ struct PhaseTimer {
     hipStream_t st;
     std::chrono::steady_clock::time_point t0, t;
     std::string out;
-    explicit PhaseTimer(hipStream_t s) : st(s) {
-        const char *e = std::getenv("PA_CLI_TIMING");
-        on = e && e[0] == '1';
+    explicit PhaseTimer(hipStream_t s) : on(env_is("PA_CLI_TIMING", '1')), st(s) {
         t0 = t = std::chrono::steady_clock::now();
     }
     void mark(const char *name) {
@@ -117,16 +138,29 @@ inline void phase_mark(const char *name) {
              sf / 1073741824.0);
     t_phase->out += b;
 }
-struct PhaseScope {
+// The phases of one entry point (index_build, index_prepare, the neighbour
+// bits made later): those of the timed build that called it, else of a timer
+// of its own, printed when the guard goes.
+struct TimedPhases {
+    std::unique_ptr<PhaseTimer> own;
     PhaseTimer *prev;
-    explicit PhaseScope(PhaseTimer *t) : prev(t_phase) { t_phase = t->on ? t : nullptr; }
-    ~PhaseScope() { t_phase = prev; }
+    explicit TimedPhases(hipStream_t st) : prev(t_phase) {
+        if (t_phase) return;
+        own.reset(new PhaseTimer(st));
+        t_phase = own->on ? own.get() : nullptr;
+    }
+    ~TimedPhases() { t_phase = prev; }
+    void mark(const char *name) {  // index_build's own phases: the time only
+        if (own) own->mark(name);
+    }
 };
 
 inline unsigned grid_for(uint64_t n, unsigned block = kBlock) {
     uint64_t g = (n + block - 1) / block;
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(g, 1u << 30));
 }
+// ... of the grid-stride scans (tables, tilings): at most 65536 blocks
+inline unsigned scan_grid(uint64_t n) { return std::min(grid_for(n), 65536u); }
 
 // ASCII -> 2-bit codes (4: N); *bad = the first byte outside A C G T N (the
 // FASTA grammar's genome alphabet), ~0 if none.
@@ -1123,107 +1157,10 @@ __global__ __launch_bounds__(256) void k_tile_rep(const uint64_t *__restrict__ p
 // REVERSE COMPLEMENTS, for k_align_lane_rc's reverse-strand walk -- a read
 // window that is the reverse complement of the genome's k-mer but for one base
 // is then resolved by one bit, as a forward one by tile_nb.
-__global__ void k_nb_build(const uint64_t *__restrict__ pk, const uint32_t *__restrict__ tile_cls, uint64_t n, int k,
-                           const Slot<1> *__restrict__ table, HomeCfg hc, uint32_t G, NbW nbw, int full,
-                           const uint32_t *__restrict__ class_genomes, const uint64_t *__restrict__ goff, int local,
-                           int pass, const uint64_t *__restrict__ bloom, uint32_t bloom_lg, int rc) {
-    // full: 64-bit words, present | specific << 32; else 32-bit words, present (nbw: one or two pieces)
-    const int sh = 64 - 2 * k;
-    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (; t < n; t += stride) {
-        if (tile_cls[t] == NONE) continue;
-        const uint64_t K = get64_at(pk, 2 * t) >> sh;
-        Key<1> kk;
-        kk.w[0] = K;
-        uint64_t slot;
-        uint32_t cls, tpos;
-        if (!table_find<1, true>(table, hc.cap, kk, home_of<1>(kk, key_hash(kk), hc), slot, cls, tpos)) continue;
-        const uint64_t fo = first_pos(cls, tpos, G, class_genomes, goff, local != 0);
-        if ((fo == t) != (pass == 0)) continue;
-        if (pass == 1) {  // copy the first occurrence's bits of this window
-            for (int j = 0; j < k; j++) {
-#pragma unroll
-                for (int b = 0; b < 3; b++) {
-                    if (full) {
-                        const unsigned long long m = *nbw.word<unsigned long long>(3 * (fo + j) + b) & (0x100000001ull << (k - 1 - j));
-                        if (m) atomicOr(nbw.word<unsigned long long>(3 * (t + j) + b), m);
-                    } else {
-                        const uint32_t m = *nbw.word<uint32_t>(3 * (fo + j) + b) & (1u << (k - 1 - j));
-                        if (m) atomicOr(nbw.word<uint32_t>(3 * (t + j) + b), m);
-                    }
-                }
-            }
-            continue;
-        }
-        for (int j = 0; j < k; j++) {
-            const int bs = 2 * (k - 1 - j);
-            const uint64_t cj = (K >> bs) & 3;
-            uint64_t keys[3];
-            uint32_t cls3[3];
-#pragma unroll
-            for (int b = 0; b < 3; b++) {
-                keys[b] = K ^ ((cj ^ ((cj + 1 + b) & 3)) << bs);
-                if (rc) keys[b] = rc_key(keys[b], k);  // (tile_rcnb: the neighbour's reverse complement)
-            }
-            uint32_t act = 7u;
-            if (bloom) {  // surely absent neighbours are not probed
-#pragma unroll
-                for (int b = 0; b < 3; b++) {
-                    uint64_t wi, bm;
-                    bloom_word_nb(keys[b], k, bloom_lg, wi, bm);
-                    if ((bloom[wi] & bm) != bm) act &= ~(1u << b);
-                }
-                if (!act) continue;
-            }
-            const uint32_t f = probe_lines<3>(table, hc, keys, cls3, act);  // the substitutions together
-#pragma unroll
-            for (int b = 0; b < 3; b++) {
-                if (!((f >> b) & 1u)) continue;
-                if (full)
-                    atomicOr(nbw.word<unsigned long long>(3 * (t + j) + b), (cls3[b] < G ? 0x100000001ull : 1ull) << (k - 1 - j));
-                else
-                    atomicOr(nbw.word<uint32_t>(3 * (t + j) + b), 1u << (k - 1 - j));
-            }
-        }
-    }
-}
-
-// Pass 1 of k_nb_build on its own (the probe loop of pass 0 holds 108 VGPRs;
-// this copy needs a third of them, so twice the waves hide its latency):
-// every occurrence t of a k-mer other than its first copies the first
-// occurrence's bits, k consecutive words per substitution (bit k - 1 - j of
-// word 3 (fo + j) + b to the same bit of word 3 (t + j) + b).
-__global__ void k_nb_copy(const uint64_t *__restrict__ pk, const uint32_t *__restrict__ tile_cls, uint64_t n, int k,
-                          const Slot<1> *__restrict__ table, HomeCfg hc, uint32_t G, NbW nbw, int full,
-                          const uint32_t *__restrict__ class_genomes, const uint64_t *__restrict__ goff, int local) {
-    const int sh = 64 - 2 * k;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) {
-        if (tile_cls[t] == NONE) continue;
-        Key<1> kk;
-        kk.w[0] = get64_at(pk, 2 * t) >> sh;
-        uint64_t slot;
-        uint32_t cls, tpos;
-        if (!table_find<1, true>(table, hc.cap, kk, home_of<1>(kk, key_hash(kk), hc), slot, cls, tpos)) continue;
-        const uint64_t fo = first_pos(cls, tpos, G, class_genomes, goff, local != 0);
-        if (fo == t) continue;
-        for (int j = 0; j < k; j++) {
-#pragma unroll
-            for (int b = 0; b < 3; b++) {
-                if (full) {
-                    const unsigned long long m = *nbw.word<unsigned long long>(3 * (fo + j) + b) & (0x100000001ull << (k - 1 - j));
-                    if (m) atomicOr(nbw.word<unsigned long long>(3 * (t + j) + b), m);
-                } else {
-                    const uint32_t m = *nbw.word<uint32_t>(3 * (fo + j) + b) & (1u << (k - 1 - j));
-                    if (m) atomicOr(nbw.word<uint32_t>(3 * (t + j) + b), m);
-                }
-            }
-        }
-    }
-}
-
-// Pass 0 of k_nb_build in POSITION order: a wave takes 64 consecutive windows
+// full: 64-bit words, present | specific << 32; else 32-bit words, present
+// (nbw: the words in one or two pieces).
+//
+// k_nb_first is pass 0, in POSITION order: a wave takes 64 consecutive windows
 // and walks their 64 k (window, substituted position) pairs ordered by the
 // substituted position p, 64 pairs per step, instead of one window per lane
 // and one offset j per step.  The neighbours of the windows around one p
@@ -1231,15 +1168,11 @@ __global__ void k_nb_copy(const uint64_t *__restrict__ pk, const uint32_t *__res
 // memory instruction of the wave touches ~7 distinct Bloom blocks instead of
 // ~40 (scripts/nb_model.py).  The pair of lane l at step s is the entry
 // s 64 + l of the block's decode table (LDS, by p then window); the window's
-// key comes from the lane that owns it (a cross-lane read).  Same bits as
-// k_nb_build's pass 0, set by the same atomics.  C5: 4.21 -> 3.55 s -- the
-// pass is bound by the minimizers' VALU (93 per window) as much as by its
-// Bloom lines; listing the filter's positives in LDS and probing them in one
-// batch per tile (occupancy 3 instead of 4) measured 4.56 s.
-#ifndef PA_NB_FIRST_ORDER
-#define PA_NB_FIRST_ORDER 1  // 0: pass 0 by k_nb_build (one window per lane; A/B)
-#endif
-constexpr bool kNbFirstOrder = PA_NB_FIRST_ORDER != 0;
+// key comes from the lane that owns it (a cross-lane read).  Against one
+// window per lane, the same bits set by the same atomics, C5: 4.21 -> 3.55 s
+// -- the pass is bound by the minimizers' VALU (93 per window) as much as by
+// its Bloom lines; listing the filter's positives in LDS and probing them in
+// one batch per tile (occupancy 3 instead of 4) measured 4.56 s.
 constexpr int kNbFirstChunk = 2;  // steps whose Bloom words are in flight together
 __global__ __launch_bounds__(256) void k_nb_first(const uint64_t *__restrict__ pk, const uint32_t *__restrict__ tile_cls,
                                                   uint64_t n, int k, const Slot<1> *__restrict__ table, HomeCfg hc,
@@ -1328,6 +1261,40 @@ __global__ __launch_bounds__(256) void k_nb_first(const uint64_t *__restrict__ p
     }
 }
 
+// Pass 1 of the neighbour bits (k_nb_first states the scheme) on its own (the probe loop of pass 0 holds 108 VGPRs;
+// this copy needs a third of them, so twice the waves hide its latency):
+// every occurrence t of a k-mer other than its first copies the first
+// occurrence's bits, k consecutive words per substitution (bit k - 1 - j of
+// word 3 (fo + j) + b to the same bit of word 3 (t + j) + b).
+__global__ void k_nb_copy(const uint64_t *__restrict__ pk, const uint32_t *__restrict__ tile_cls, uint64_t n, int k,
+                          const Slot<1> *__restrict__ table, HomeCfg hc, uint32_t G, NbW nbw, int full,
+                          const uint32_t *__restrict__ class_genomes, const uint64_t *__restrict__ goff, int local) {
+    const int sh = 64 - 2 * k;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) {
+        if (tile_cls[t] == NONE) continue;
+        Key<1> kk;
+        kk.w[0] = get64_at(pk, 2 * t) >> sh;
+        uint64_t slot;
+        uint32_t cls, tpos;
+        if (!table_find<1, true>(table, hc.cap, kk, home_of<1>(kk, key_hash(kk), hc), slot, cls, tpos)) continue;
+        const uint64_t fo = first_pos(cls, tpos, G, class_genomes, goff, local != 0);
+        if (fo == t) continue;
+        for (int j = 0; j < k; j++) {
+#pragma unroll
+            for (int b = 0; b < 3; b++) {
+                if (full) {
+                    const unsigned long long m = *nbw.word<unsigned long long>(3 * (fo + j) + b) & (0x100000001ull << (k - 1 - j));
+                    if (m) atomicOr(nbw.word<unsigned long long>(3 * (t + j) + b), m);
+                } else {
+                    const uint32_t m = *nbw.word<uint32_t>(3 * (fo + j) + b) & (1u << (k - 1 - j));
+                    if (m) atomicOr(nbw.word<uint32_t>(3 * (t + j) + b), m);
+                }
+            }
+        }
+    }
+}
+
 // The same for two- and three-word keys (31 < k <= 95: pa_device.h
 // bloom_word2 / bloom_word3).
 template <int NW = 2>
@@ -1384,7 +1351,7 @@ __global__ void k_nb_sum3(const uint64_t *__restrict__ pk, const uint32_t *__res
     }
 }
 
-// The neighbour bits of two-word keys (31 < k <= 63; k_nb_build states the
+// The neighbour bits of two-word keys (31 < k <= 63; k_nb_first states the
 // scheme): bit i of nb[3 p + b] says whether the k-mer starting at p - k + 1 +
 // i with its base at p replaced by the b-th other base is in the index --
 // 64-bit words of present neighbours only (a present one is then probed by the
@@ -1692,12 +1659,24 @@ __global__ void k_synth_reads(const uint8_t *__restrict__ codes, const uint64_t 
     }
 }
 
+// The windows of every genome that has one, in FASTA order (the insert, fill
+// and HyperLogLog scans; the tile chunks): f(genome, its first base, windows).
+template <class F>
+void for_each_genome_windows(const pa_index *idx, int k, F &&f) {
+    for (uint32_t g = 0; g < idx->n_genomes; g++) {
+        const uint64_t len = idx->h_goff[g + 1] - idx->h_goff[g];
+        if (k <= 0 || (uint64_t)k > len) continue;
+        f(g, idx->h_goff[g], len - k + 1);
+    }
+}
+
+// Steps 3 to 6: the table's keys, classes and first occurrences.
 template <int NW>
 pa_status build_nw(pa_index *idx, hipStream_t st) {
     const uint32_t G = idx->n_genomes;
     const int k = (int)idx->k;
     const int wpt = build_run();
-    const uint64_t mask0 = (2 * k - 64 * (NW - 1)) >= 64 ? ~0ull : ((1ull << (2 * k - 64 * (NW - 1))) - 1);
+    const uint64_t mask0 = mask0_of(k, NW);
     const uint64_t cap = idx->cap;
     Slot<NW> *table = (Slot<NW> *)idx->table;
     uint32_t *lists = nullptr, *cs_id = nullptr, *err = nullptr, *lpos = nullptr;
@@ -1708,16 +1687,14 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
     PA_HIP(b.get(&off, cap * 8));
     PA_HIP(b.get(&cnt, 8 * 8));
     PA_HIP(b.get(&err, 4));
-    // each window's place in its slot's genome list, taken in pass 1 (4 B per
-    // base, while it fits an eighth of the free memory; PA_BUILD_LPOS=0: pass
-    // 2 takes the places by CAS, as for keys of more than one word)
+    // each window's place in its slot's genome list, taken in pass 1 (one-word
+    // keys, plan::lpos_fits; PA_BUILD_LPOS=0: pass 2 takes the places by CAS,
+    // as for keys of more than one word)
     {
-        const char *e = std::getenv("PA_BUILD_LPOS");
         size_t fb = 0, tb = 0;
         const uint64_t total = idx->h_goff[G];  // (lpos is indexed by the concatenated position, as codes)
-        if (NW == 1 && kBatchedInsert && total > 0 && !(e && e[0] == '0') &&
-            pa::dev_mem_info(&fb, &tb) == hipSuccess && total * 4 <= fb / 8 &&
-            pa::dev_malloc_try((void **)&lpos, total * 4) != hipSuccess) {
+        if (NW == 1 && total > 0 && !env_is("PA_BUILD_LPOS", '0') && pa::dev_mem_info(&fb, &tb) == hipSuccess &&
+            plan::lpos_fits(total, fb) && pa::dev_malloc_try((void **)&lpos, total * 4) != hipSuccess) {
             (void)hipGetLastError();
             lpos = nullptr;
         }
@@ -1725,22 +1702,19 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
     }
     PA_HIP(hipMemsetAsync(cnt, 0, 8 * 8, st));
     PA_HIP(hipMemsetAsync(err, 0, 4, st));
-    // pass 1
-    for (uint32_t g = 0; g < G; g++) {
-        uint64_t len = idx->h_goff[g + 1] - idx->h_goff[g];
-        if (k <= 0 || (uint64_t)k > len) continue;
-        uint64_t nwin = len - k + 1;
-        if (NW == 1 && kBatchedInsert)
-            hipLaunchKernelGGL(k_build_insert1, dim3(grid_for((nwin + wpt - 1) / wpt)), dim3(kBlock), 0, st,
-                               idx->codes, idx->h_goff[g], nwin, k, mask0, g, (Slot<1> *)table, idx->home, cnt + 0,
-                               err, wpt, lpos);
+    // pass 1 (one-word keys: a batch of windows per thread; wider keys one window at a time)
+    for_each_genome_windows(idx, k, [&](uint32_t g, uint64_t start, uint64_t nwin) {
+        const dim3 grid(grid_for((nwin + wpt - 1) / wpt));
+        if constexpr (NW == 1)
+            hipLaunchKernelGGL(k_build_insert1, grid, dim3(kBlock), 0, st, idx->codes, start, nwin, k, mask0, g, table,
+                               idx->home, cnt + 0, err, wpt, lpos);
         else
-            hipLaunchKernelGGL(k_build_insert<NW>, dim3(grid_for((nwin + wpt - 1) / wpt)), dim3(kBlock), 0, st,
-                               idx->codes, idx->h_goff[g], nwin, k, mask0, g, table, idx->home, cnt + 0, err, wpt);
-    }
+            hipLaunchKernelGGL(k_build_insert<NW>, grid, dim3(kBlock), 0, st, idx->codes, start, nwin, k, mask0, g,
+                               table, idx->home, cnt + 0, err, wpt);
+    });
     PA_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_build_prep<NW>, dim3(grid_for(cap, kBlock) > 65536 ? 65536 : grid_for(cap)), dim3(kBlock), 0,
-                       st, table, cap, off, cnt + 1, cnt + 2, lpos != nullptr ? 1 : 0);
+    hipLaunchKernelGGL(k_build_prep<NW>, dim3(scan_grid(cap)), dim3(kBlock), 0, st, table, cap, off, cnt + 1, cnt + 2,
+                       lpos != nullptr ? 1 : 0);
     PA_HIP(hipGetLastError());
     unsigned long long h_cnt[8];
     uint32_t h_err = 0;
@@ -1756,19 +1730,15 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
     idx->n_multi = 0;
     if (n_multi > 0) {
         PA_HIP(b.get(&lists, list_total * 4));
-        for (uint32_t g = 0; g < G; g++) {
-            uint64_t len = idx->h_goff[g + 1] - idx->h_goff[g];
-            if ((uint64_t)k > len) continue;
-            uint64_t nwin = len - k + 1;
-            if (NW == 1 && kBatchedInsert)
-                hipLaunchKernelGGL(k_build_fill1, dim3(grid_for((nwin + wpt - 1) / wpt)), dim3(kBlock), 0, st,
-                                   idx->codes, idx->h_goff[g], nwin, k, mask0, g, (Slot<1> *)table, idx->home, G, off,
-                                   lists, wpt, lpos);
+        for_each_genome_windows(idx, k, [&](uint32_t g, uint64_t start, uint64_t nwin) {
+            const dim3 grid(grid_for((nwin + wpt - 1) / wpt));
+            if constexpr (NW == 1)
+                hipLaunchKernelGGL(k_build_fill1, grid, dim3(kBlock), 0, st, idx->codes, start, nwin, k, mask0, g, table,
+                                   idx->home, G, off, lists, wpt, lpos);
             else
-                hipLaunchKernelGGL(k_build_fill<NW>, dim3(grid_for((nwin + wpt - 1) / wpt)), dim3(kBlock), 0, st,
-                                   idx->codes, idx->h_goff[g], nwin, k, mask0, g, table, idx->home, G, off, lists,
-                                   wpt);
-        }
+                hipLaunchKernelGGL(k_build_fill<NW>, grid, dim3(kBlock), 0, st, idx->codes, start, nwin, k, mask0, g,
+                                   table, idx->home, G, off, lists, wpt);
+        });
         PA_HIP(hipGetLastError());
         // distinct genome sets: a hash over the multi slots' genome lists.  A
         // reference has few distinct sets (C2: 342, 2000 genomes in families:
@@ -1776,12 +1746,12 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
         // starts at 16 M entries and grows on overflow, up to 2 per k-mer
         const uint64_t cs_max = 2 * n_multi + 64;
         uint64_t cs_cap = std::min<uint64_t>(cs_max, (1ull << 24) + 64);
-        unsigned sgrid = grid_for(cap) > 65536 ? 65536 : grid_for(cap);
+        unsigned sgrid = scan_grid(cap);
         int cache_pos = 0;
         for (;;) {
             PA_HIP(b.get(&cs_key, cs_cap * 8));
             PA_HIP(b.get(&cs_rep, cs_cap * 8));
-            hipLaunchKernelGGL(k_fill_u64, dim3(grid_for(cs_cap) > 65536 ? 65536 : grid_for(cs_cap)), dim3(kBlock), 0,
+            hipLaunchKernelGGL(k_fill_u64, dim3(scan_grid(cs_cap)), dim3(kBlock), 0,
                                st, cs_key, cs_cap, EMPTY);
             cache_pos = (uint64_t)G + cs_cap < 0xFFF00000ull ? 1 : 0;  // (G + position below pass 2's marks)
             hipLaunchKernelGGL(k_class_insert<NW>, dim3(sgrid), dim3(kBlock), 0, st, table, cap, G, off, lists,
@@ -1805,7 +1775,7 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
         PA_HIP(pa::dev_malloc(&idx->class_size, max_cls * 4));
         PA_HIP(pa::dev_malloc(&idx->class_off, max_cls * 8));
         PA_HIP(b.get(&rep_of, max_cls * 8));
-        hipLaunchKernelGGL(k_class_number<NW>, dim3(grid_for(cs_cap) > 65536 ? 65536 : grid_for(cs_cap)), dim3(kBlock),
+        hipLaunchKernelGGL(k_class_number<NW>, dim3(scan_grid(cs_cap)), dim3(kBlock),
                            0, st, cs_key, cs_rep, cs_id, cs_cap, (const Slot<NW> *)table, idx->class_size,
                            idx->class_off, rep_of, cnt + 3, cnt + 4);
         PA_HIP(hipGetLastError());
@@ -1843,7 +1813,7 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
             pa::set_error("index build: hash table full (internal error)");
             return PA_EINTERNAL;
         }
-        hipLaunchKernelGGL(k_table_order<NW>, dim3(grid_for(cap) > 65536 ? 65536 : grid_for(cap)), dim3(kBlock), 0, st,
+        hipLaunchKernelGGL(k_table_order<NW>, dim3(scan_grid(cap)), dim3(kBlock), 0, st,
                            table, idx->home);
         PA_HIP(hipGetLastError());
     }
@@ -1852,18 +1822,123 @@ pa_status build_nw(pa_index *idx, hipStream_t st) {
     return PA_OK;
 }
 
-// Step 6, the align-side view of the index (k <= 31, references whose
-// genomes are each < 2^32 bases): the genome tiling, flag planes and walk
-// blocks, neighbour bits and the Bloom filter.  Made after the build scratch
-// is freed -- at the end of pa_index_build, or deferred (PA_BUILD_DEFER_TILES)
-// to pa_index_prepare / the first align call, so that an index used only for
-// EXTSIM statistics (src/kmer.py:152-263) never pays for it.
-// One-substitution neighbour bits of the genome tiling (k_nb_build, tile_nb):
-// 24 B per base, made once per index (C2: ~50 ms of kernels, ~0.12 s with the
-// allocation) -- they repay themselves after ~4 reads per genome base.
-pa_status build_nb2(pa_index *idx, hipStream_t st);
+// ---- step 7: the align-side view -------------------------------------------
+// The genome tiling, flag planes and walk blocks, neighbour words and the
+// Bloom filter (keys of one to three words, references whose genomes are each
+// < 2^32 bases).  Made after the build scratch is freed -- at the end of
+// pa_index_build, or deferred (PA_BUILD_DEFER_TILES) to pa_index_prepare / the
+// first align call, so that an index used only for EXTSIM statistics
+// (src/kmer.py:152-263) never pays for it.
+// One function per part: it allocates, launches, sets its own fields of the
+// index and adds its own device_bytes; what a failed one leaves behind goes
+// with release_align_view.  The ORDER of the allocations and frees is part of
+// the behaviour -- where a buffer lands in the slab pool has moved align speed
+// by 10 % (plan::table_cap_distinct) -- so no part moves past another.
 
-pa_status build_nb3(pa_index *idx, hipStream_t st);
+// f(int_c<NW>) for the key widths that have a tiling
+template <class F>
+auto with_tile_nw(int nw, F &&f) {
+    return pa::with_int<3, 2, 1>(nw, f);
+}
+
+// The keys of the table into a Bloom filter of 2^lg words: the align-side one
+// (bloom_word), or (nb) the neighbour-bit build's own (bloom_word_nb).
+void bloom_fill(const pa_index *idx, hipStream_t st, uint64_t *bloom, uint32_t lg, bool nb) {
+    const dim3 grid(scan_grid(idx->cap)), block(kBlock);
+    if (idx->nw == 1 && nb)
+        hipLaunchKernelGGL(k_bloom_build<true>, grid, block, 0, st, (const Slot<1> *)idx->table, idx->cap, bloom, lg,
+                           (int)idx->k);
+    else if (idx->nw == 1)
+        hipLaunchKernelGGL(k_bloom_build<false>, grid, block, 0, st, (const Slot<1> *)idx->table, idx->cap, bloom, lg,
+                           (int)idx->k);
+    else if (idx->nw == 2)
+        hipLaunchKernelGGL(k_bloom_build2<2>, grid, block, 0, st, (const Slot<2> *)idx->table, idx->cap, bloom, lg);
+    else
+        hipLaunchKernelGGL(k_bloom_build2<3>, grid, block, 0, st, (const Slot<3> *)idx->table, idx->cap, bloom, lg);
+}
+
+// The tiling itself: the genomes packed (tile_pk) and every window's class
+// (tile_cls), every genome's chunks in one launch (k_tile_cls_all).
+pa_status tile_classes(pa_index *idx, hipStream_t st) {
+    const uint32_t G = idx->n_genomes;
+    const int k = (int)idx->k, wpt = build_run();
+    const uint64_t n = idx->tile_n, nwords = n / 32 + 32;  // padded: the walk reads up to 18 words past a position
+    PA_HIP(pa::dev_malloc(&idx->tile_cls, n * 4));
+    PA_HIP(pa::dev_malloc(&idx->tile_pk, nwords * 8));
+    idx->device_bytes += n * 4 + nwords * 8;
+    PA_HIP(hipMemsetAsync(idx->tile_cls, 0xFF, n * 4, st));
+    hipLaunchKernelGGL(k_tile_pack, dim3(scan_grid(nwords)), dim3(kBlock), 0, st, idx->codes, n, idx->tile_pk, nwords);
+    std::vector<uint64_t> ts(G + 1, 0);  // chunks before genome g
+    for_each_genome_windows(idx, k, [&](uint32_t g, uint64_t, uint64_t nwin) { ts[g + 1] = (nwin + wpt - 1) / wpt; });
+    for (uint32_t g = 0; g < G; g++) ts[g + 1] += ts[g];
+    pa::Bufs b(st);
+    uint64_t *d_ts = nullptr;
+    PA_HIP(b.get(&d_ts, (G + 1) * 8));
+    PA_HIP(hipMemcpyAsync(d_ts, ts.data(), (G + 1) * 8, hipMemcpyHostToDevice, st));
+    if (ts[G] > 0) {
+        with_tile_nw(idx->nw, [&](auto w) {
+            hipLaunchKernelGGL(k_tile_cls_all<w()>, dim3(grid_for(ts[G])), dim3(kBlock), 0, st, idx->codes, idx->goff, d_ts,
+                               G, k, mask0_of(k, w()), (Slot<w()> *)idx->table, idx->home, idx->tile_cls,
+                               idx->class_genomes, idx->tpos_local, wpt);
+        });
+        PA_HIP(hipGetLastError());
+    }
+    return PA_OK;
+}
+
+// Below 2^33 bases: first occurrences as 33-bit concatenated positions
+// (PA_TPOS_HI=0 keeps them genome-local: tests of that layout).
+pa_status tile_first_concat(pa_index *idx, hipStream_t st) {
+    if (!idx->tpos_local || idx->h_goff[idx->n_genomes] >= (1ull << 33) || env_is("PA_TPOS_HI", '0')) return PA_OK;
+    with_tile_nw(idx->nw, [&](auto w) {
+        hipLaunchKernelGGL(k_tpos_concat<w()>, dim3(scan_grid(idx->cap)), dim3(kBlock), 0, st,
+                           (Slot<w()> *)idx->table, idx->cap, idx->n_genomes, idx->class_genomes, idx->goff);
+    });
+    PA_HIP(hipGetLastError());
+    idx->tpos_local = 0;
+    phase_mark("first occurrences concatenated");
+    return PA_OK;
+}
+
+// The genome of every 2^16-th position (tile_gblk): genome_of is then one or two goff steps.
+pa_status tile_genome_blocks(pa_index *idx, hipStream_t st) {
+    const uint32_t G = idx->n_genomes;
+    const uint64_t nb = (idx->tile_n >> 16) + 2;
+    std::vector<uint32_t> gb(nb);
+    for (uint64_t j = 0; j < nb; j++) {
+        const uint64_t pos = j << 16;
+        uint32_t g = (uint32_t)(std::upper_bound(idx->h_goff.begin(), idx->h_goff.begin() + G + 1, pos) -
+                                idx->h_goff.begin());
+        g = g == 0 ? 0 : g - 1;
+        gb[j] = g >= G ? G - 1 : g;
+    }
+    PA_HIP(pa::dev_malloc(&idx->tile_gblk, nb * 4));
+    idx->device_bytes += nb * 4;
+    PA_HIP(hipMemcpyAsync(idx->tile_gblk, gb.data(), nb * 4, hipMemcpyHostToDevice, st));
+    PA_HIP(hipStreamSynchronize(st));
+    return PA_OK;
+}
+
+// The lane kernels' view: the repeat flags (k_tile_rep) and the walk blocks (tile_lw).
+pa_status tile_walk_blocks(pa_index *idx, hipStream_t st) {
+    const uint64_t n = idx->tile_n;
+    const int k = (int)idx->k;
+    with_tile_nw(idx->nw, [&](auto w) {
+        hipLaunchKernelGGL(k_tile_rep<w()>, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 20)), dim3(256), 0,
+                           st, idx->tile_pk, idx->tile_cls, n, k);
+    });
+    const uint64_t n_blocks = n / 64 + 8;  // padded: the 250-bp walk reads six blocks from any position
+    PA_HIP(pa::dev_malloc(&idx->tile_lw, n_blocks * 32));
+    hipLaunchKernelGGL(k_tile_walk, dim3((unsigned)std::min<uint64_t>((n_blocks + 3) / 4, 1u << 20)), dim3(256), 0, st,
+                       idx->tile_cls, idx->tile_pk, n, idx->n_genomes, idx->tile_lw, n_blocks);
+    idx->device_bytes += n_blocks * 32;
+    phase_mark("repeats + walk blocks");
+    return PA_OK;
+}
+
+// -- neighbour words (tile_nb): made once per index (C2: ~50 ms of kernels,
+// ~0.12 s with the allocation) -- they repay themselves after ~4 reads per
+// genome base.
 
 // The device view of an index's neighbour words (wb: 8 or 4 bytes per word).
 NbW nb_words(const pa_index *idx, uint64_t wb) {
@@ -1872,426 +1947,275 @@ NbW nb_words(const pa_index *idx, uint64_t wb) {
     return NbW{b0, (uint64_t)(uintptr_t)idx->tile_nb1 - idx->nb_split * wb, idx->nb_split};
 }
 
+// The neighbour-bit build's Bloom filter of the keys (plan::nb_bloom_lg, in
+// HBM, held by the caller's Bufs, which frees it): most of a window's 3k
+// neighbours are absent and share its Bloom line (minimizer-chosen), so a
+// probe costs an L2 hit instead of a table line.  nullptr when it does not fit
+// (or, one-word keys, with PA_NB_BLOOM=0: A/B).
+pa_status make_nb_bloom(pa_index *idx, hipStream_t st, pa::Bufs &b, uint64_t **out, uint32_t *out_lg) {
+    *out = nullptr;
+    *out_lg = 6;
+    if ((idx->nw == 1 && env_is("PA_NB_BLOOM", '0')) || idx->n_kmers == 0) return PA_OK;
+    size_t fb = 0, tb = 0;
+    if (pa::dev_mem_info(&fb, &tb) != hipSuccess) fb = 0;
+    const uint32_t lg = plan::nb_bloom_lg(idx->n_kmers, fb);
+    uint64_t *bb = nullptr;
+    if (lg == 0 || b.get(&bb, (1ull << lg) * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        return PA_OK;
+    }
+    PA_HIP(hipMemsetAsync(bb, 0, (1ull << lg) * 8, st));
+    if (idx->nw == 1)  // (the one-word build's phases are timed one by one)
+        phase_mark(lg >= 30 ? "nb: Bloom alloc (lg >= 30)" : "nb: Bloom alloc (lg < 30)");
+    bloom_fill(idx, st, bb, lg, true);
+    PA_HIP(hipGetLastError());
+    *out = bb;
+    *out_lg = lg;
+    return PA_OK;
+}
+
+// The two passes of one-word keys' neighbour words (k_nb_first, k_nb_copy):
+// the forward words (rc = 0, full or present only) or tile_rcnb (rc = 1).
+void nb_passes(const pa_index *idx, hipStream_t st, const NbW &words, int full, const uint64_t *bb, uint32_t bb_lg,
+               int rc) {
+    const uint64_t n = idx->tile_n;
+    const Slot<1> *table = (const Slot<1> *)idx->table;
+    hipLaunchKernelGGL(k_nb_first, dim3(scan_grid(n)), dim3(kBlock), 0, st, idx->tile_pk, idx->tile_cls, n, (int)idx->k,
+                       table, idx->home, idx->n_genomes, words, full, idx->class_genomes, idx->goff, idx->tpos_local, bb,
+                       bb_lg, rc);
+    if (!rc) phase_mark("nb: first occurrences");
+    hipLaunchKernelGGL(k_nb_copy, dim3(scan_grid(n)), dim3(kBlock), 0, st, idx->tile_pk, idx->tile_cls, n, (int)idx->k,
+                       table, idx->home, idx->n_genomes, words, full, idx->class_genomes, idx->goff, idx->tpos_local);
+    if (!rc) phase_mark("nb: copies");
+}
+
 // The reverse-complement neighbour bits (tile_rcnb, 12 B per base) when they
 // leave a quarter of the free memory; bb: the build-time Bloom filter of the
 // keys (nullable: every neighbour probed).
 pa_status build_rcnb(pa_index *idx, hipStream_t st, const uint64_t *bb, uint32_t bb_lg) {
     const uint64_t n = idx->tile_n;
-    const int k = (int)idx->k;
-    const uint32_t G = idx->n_genomes;
-    const Slot<1> *table = (const Slot<1> *)idx->table;
     idx->rcnb_pending = 0;
     size_t fr_b = 0, tr_b = 0;
-    if (!(pa::dev_mem_info(&fr_b, &tr_b) == hipSuccess && n * 12 <= fr_b / 4 * 3 &&
+    if (!(pa::dev_mem_info(&fr_b, &tr_b) == hipSuccess && plan::leaves_quarter(n * 12, fr_b) &&
           pa::dev_malloc(&idx->tile_rcnb, n * 12 + 64) == hipSuccess)) {
         (void)hipGetLastError();
         idx->tile_rcnb = nullptr;
         return PA_OK;  // (no room: the seedless reads are walked without them)
     }
     PA_HIP(hipMemsetAsync(idx->tile_rcnb, 0, n * 12 + 64, st));
-    const NbW rc_words{(uint64_t)(uintptr_t)idx->tile_rcnb, 0, ~0ull};
-    for (int pass = 0; pass < 2; pass++)
-        if (pass == 0 && kNbFirstOrder)
-            hipLaunchKernelGGL(k_nb_first, dim3(grid_for(n) > 65536 ? 65536 : grid_for(n)), dim3(kBlock), 0, st,
-                               idx->tile_pk, idx->tile_cls, n, k, table, idx->home, G, rc_words, 0,
-                               idx->class_genomes, idx->goff, idx->tpos_local, bb, bb_lg, 1);
-        else if (pass == 1)
-            hipLaunchKernelGGL(k_nb_copy, dim3(grid_for(n) > 65536 ? 65536 : grid_for(n)), dim3(kBlock), 0, st,
-                               idx->tile_pk, idx->tile_cls, n, k, table, idx->home, G, rc_words, 0,
-                               idx->class_genomes, idx->goff, idx->tpos_local);
-        else
-            hipLaunchKernelGGL(k_nb_build, dim3(grid_for(n) > 65536 ? 65536 : grid_for(n)), dim3(kBlock), 0, st,
-                               idx->tile_pk, idx->tile_cls, n, k, table, idx->home, G, rc_words, 0,
-                               idx->class_genomes, idx->goff, idx->tpos_local, pass, bb, bb_lg, 1);
+    nb_passes(idx, st, NbW{(uint64_t)(uintptr_t)idx->tile_rcnb, 0, ~0ull}, 0, bb, bb_lg, 1);
     PA_HIP(hipGetLastError());
     idx->device_bytes += n * 12;
     phase_mark("nb: reverse complements");
     return PA_OK;
 }
 
-// The neighbour-bit build's Bloom filter of the keys (~16 bits per key in HBM,
-// held by the caller's Bufs): most of a window's 3k neighbours are absent and share
-// its Bloom line (minimizer-chosen), so a probe costs an L2 hit instead of a
-// table line.  nullptr when it does not fit (or PA_NB_BLOOM=0).
-pa_status make_nb_bloom(pa_index *idx, hipStream_t st, pa::Bufs &b, uint64_t **out, uint32_t *out_lg) {
-    *out = nullptr;
-    *out_lg = 6;
+// Room for `words` neighbour words of wb bytes: one piece where the pool or
+// the free device memory has room for it; else two pieces (plan::nb_split) --
+// the first in the pool's largest free range, the second in the free device
+// memory -- when both fit without giving idle slabs back; else one piece
+// whatever it costs.  PA_NB_SPLIT=1 forces two halves (tests).
+pa_status nb_alloc_words(pa_index *idx, uint64_t words, uint64_t wb) {
+    const bool force_split = env_is("PA_NB_SPLIT", '1');
+    if (!force_split && pa::dev_malloc_try(&idx->tile_nb, words * wb + 64) == hipSuccess) return PA_OK;
+    (void)hipGetLastError();
+    idx->tile_nb = nullptr;
+    const plan::NbSplit sp = plan::nb_split(words, wb, pa::dev_pool_largest_free(), force_split);
+    if (sp.usable) {
+        if (pa::dev_malloc_try(&idx->tile_nb, sp.first * wb + 64) == hipSuccess &&
+            pa::dev_malloc_try(&idx->tile_nb1, (words - sp.first) * wb + 64) == hipSuccess) {
+            idx->nb_split = sp.first;
+            return PA_OK;
+        }
+        (void)hipGetLastError();
+        pa::dev_release(idx->tile_nb);
+        pa::dev_release(idx->tile_nb1);
+        idx->nb_split = ~0ull;
+    }
+    PA_HIP(pa::dev_malloc(&idx->tile_nb, words * wb + 64));
+    return PA_OK;
+}
+
+// One-word keys: 3 words per base (plan::nb_word_bytes: present | specific,
+// present only, or none), then the reverse-complement bits' turn.
+pa_status build_nb1(pa_index *idx, hipStream_t st) {
+    const uint64_t n = idx->tile_n, words = 3 * n;
+    pa::Bufs b(st);
+    size_t free_b = 0, total_b = 0;
+    if (pa::dev_mem_info(&free_b, &total_b) != hipSuccess) return PA_OK;
+    const uint64_t wb = plan::nb_word_bytes(n, free_b, env_is("PA_NB_HALF", '1'), idx->force_large != 0);
+    if (wb == 0) return PA_OK;
+    const int full = wb == 8 ? 1 : 0;
+    PA_TRY(nb_alloc_words(idx, words, wb));
+    phase_mark(idx->tile_nb1 ? "nb: alloc (two pieces)" : "nb: alloc");
+    if (idx->tile_nb1) {
+        PA_HIP(hipMemsetAsync(idx->tile_nb, 0, idx->nb_split * wb + 64, st));
+        PA_HIP(hipMemsetAsync(idx->tile_nb1, 0, (words - idx->nb_split) * wb + 64, st));
+    } else {
+        PA_HIP(hipMemsetAsync(idx->tile_nb, 0, words * wb + 64, st));
+    }
+    phase_mark("nb: clear");
     uint64_t *bb = nullptr;
     uint32_t bb_lg = 6;
-    const char *nbb = std::getenv("PA_NB_BLOOM");
-    if ((nbb && nbb[0] == '0') || idx->n_kmers == 0) return PA_OK;
-    while (bb_lg < 33 && (1ull << bb_lg) * 4 < idx->n_kmers) bb_lg++;  // (bloom_block: lg <= 33)
-    size_t fb = 0, tb = 0;
-    if (pa::dev_mem_info(&fb, &tb) != hipSuccess) fb = 0;
-    while (bb_lg > 6 && (1ull << bb_lg) * 8 > fb / 4) bb_lg--;
-    if ((1ull << bb_lg) * 64 < idx->n_kmers * 8 || b.get(&bb, (1ull << bb_lg) * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return PA_OK;
+    PA_TRY(make_nb_bloom(idx, st, b, &bb, &bb_lg));
+    phase_mark("nb: build Bloom");
+    nb_passes(idx, st, nb_words(idx, wb), full, bb, bb_lg, 0);
+    // the reverse-complement neighbour bits (tile_rcnb, 12 B per base):
+    // only reads with no forward seed use them (k_align_lane_rc), so by
+    // default they are left for the first align pass that queues enough
+    // such reads (index_rcnb_wanted: C4's forward reads never do, and
+    // its serving index skips their 0.35 s); PA_RCNB_EAGER=1 makes them
+    // now, PA_NO_RCNB=1 never
+    if (idx->k <= 31 && !env_is("PA_NO_RCNB", '1')) {
+        if (env_is("PA_RCNB_EAGER", '1'))
+            PA_TRY(build_rcnb(idx, st, bb, bb_lg));
+        else
+            idx->rcnb_pending = 1;
     }
-    PA_HIP(hipMemsetAsync(bb, 0, (1ull << bb_lg) * 8, st));
-    phase_mark(bb_lg >= 30 ? "nb: Bloom alloc (lg >= 30)" : "nb: Bloom alloc (lg < 30)");
-    hipLaunchKernelGGL(k_bloom_build<true>, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
-                       dim3(kBlock), 0, st, (const Slot<1> *)idx->table, idx->cap, bb, bb_lg, (int)idx->k);
-    PA_HIP(hipGetLastError());
-    *out = bb;
-    *out_lg = bb_lg;
+    PA_HIP(b.free(bb));
+    idx->nb_spec = full;
+    idx->device_bytes += words * wb;
     return PA_OK;
 }
 
-pa_status build_nb(pa_index *idx, hipStream_t st) {
-    if (idx->nw == 2) return build_nb2(idx, st);
-    if (idx->nw == 3) return build_nb3(idx, st);
-    const uint64_t n = idx->tile_n;
-    const int k = (int)idx->k;
-    const uint32_t G = idx->n_genomes;
-    Slot<1> *table = (Slot<1> *)idx->table;
-    pa::Bufs b(st);
-    // one-substitution neighbours: 24 B per base (present | specific) when
-    // that leaves a quarter of the free memory, else 12 B (present only:
-    // a present neighbour is then probed), else none; PA_NO_NB=1 skips
-    // them, PA_NB_HALF=1 forces the 12-B form (A/B measurements, tests)
-    size_t free_b = 0, total_b = 0;
-    const char *no_nb = std::getenv("PA_NO_NB"), *nb_half = std::getenv("PA_NB_HALF");
-    if (!(no_nb && no_nb[0] == '1') && pa::dev_mem_info(&free_b, &total_b) == hipSuccess) {
-        const bool full = n * 24 <= free_b / 4 * 3 && !(nb_half && nb_half[0] == '1') && !idx->force_large;
-        const uint64_t wb = full ? 8 : 4;
-        if (n * 3 * wb <= free_b / 4 * 3) {
-            // one piece where the pool or the free device memory has room for
-            // it; else two pieces -- the first in the pool's largest free
-            // range, the second in the free device memory -- when both fit
-            // without giving idle slabs back (the driver's reclaim of memory
-            // freed earlier runs ~60 GB/s: 1.9 s for C5's words after EXTSIM);
-            // else one piece whatever it costs.  PA_NB_SPLIT=1 forces two
-            // halves (tests)
-            const uint64_t words = 3 * n;
-            const char *fs = std::getenv("PA_NB_SPLIT");
-            const bool force_split = fs && fs[0] == '1';
-            hipError_t ea = force_split ? hipErrorOutOfMemory : pa::dev_malloc_try(&idx->tile_nb, words * wb + 64);
-            // the first piece as large as the pool's largest free range (the
-            // second then from the free device memory), at least an eighth
-            const uint64_t lf = pa::dev_pool_largest_free();
-            uint64_t split_w = force_split ? words / 2 : (lf > (2ull << 20) ? (lf - (2ull << 20)) / wb : 0);
-            split_w = std::min<uint64_t>(split_w, words - words / 8);
-            if (ea != hipSuccess && split_w >= words / 8) {
-                (void)hipGetLastError();
-                idx->tile_nb = nullptr;
-                if (pa::dev_malloc_try(&idx->tile_nb, split_w * wb + 64) == hipSuccess &&
-                    pa::dev_malloc_try(&idx->tile_nb1, (words - split_w) * wb + 64) == hipSuccess) {
-                    idx->nb_split = split_w;
-                } else {
-                    (void)hipGetLastError();
-                    pa::dev_free(idx->tile_nb);
-                    pa::dev_free(idx->tile_nb1);
-                    idx->tile_nb = idx->tile_nb1 = nullptr;
-                    idx->nb_split = ~0ull;
-                    PA_HIP(pa::dev_malloc(&idx->tile_nb, words * wb + 64));
-                }
-            } else if (ea != hipSuccess) {
-                (void)hipGetLastError();
-                PA_HIP(pa::dev_malloc(&idx->tile_nb, words * wb + 64));
-            }
-            phase_mark(idx->tile_nb1 ? "nb: alloc (two pieces)" : "nb: alloc");
-            if (idx->tile_nb1) {
-                PA_HIP(hipMemsetAsync(idx->tile_nb, 0, idx->nb_split * wb + 64, st));
-                PA_HIP(hipMemsetAsync(idx->tile_nb1, 0, (words - idx->nb_split) * wb + 64, st));
-            } else {
-                PA_HIP(hipMemsetAsync(idx->tile_nb, 0, words * wb + 64, st));
-            }
-            phase_mark("nb: clear");
-            const NbW nbw = nb_words(idx, wb);
-            // a build-time Bloom filter of the keys (~16 bits per key, in
-            // HBM; freed below): most of the 3k neighbours of a window are
-            // absent and share the window's Bloom line (minimizer-chosen),
-            // so a probe costs an L2 hit instead of a table line.
-            // PA_NB_BLOOM=0 turns it off (A/B)
-            uint64_t *bb = nullptr;
-            uint32_t bb_lg = 6;
-            PA_TRY(make_nb_bloom(idx, st, b, &bb, &bb_lg));
-            phase_mark("nb: build Bloom");
-            for (int pass = 0; pass < 2; pass++) {
-                if (pass == 0 && kNbFirstOrder)
-                    hipLaunchKernelGGL(k_nb_first, dim3(grid_for(n) > 65536 ? 65536 : grid_for(n)), dim3(kBlock), 0,
-                                       st, idx->tile_pk, idx->tile_cls, n, k, (const Slot<1> *)table, idx->home, G,
-                                       nbw, full ? 1 : 0, idx->class_genomes, idx->goff, idx->tpos_local,
-                                       bb, bb_lg, 0);
-                else if (pass == 1)
-                    hipLaunchKernelGGL(k_nb_copy, dim3(grid_for(n) > 65536 ? 65536 : grid_for(n)), dim3(kBlock), 0,
-                                       st, idx->tile_pk, idx->tile_cls, n, k, (const Slot<1> *)table, idx->home, G,
-                                       nbw, full ? 1 : 0, idx->class_genomes, idx->goff, idx->tpos_local);
-                else
-                    hipLaunchKernelGGL(k_nb_build, dim3(grid_for(n) > 65536 ? 65536 : grid_for(n)), dim3(kBlock), 0,
-                                       st, idx->tile_pk, idx->tile_cls, n, k, (const Slot<1> *)table, idx->home, G,
-                                       nbw, full ? 1 : 0, idx->class_genomes, idx->goff, idx->tpos_local,
-                                       pass, bb, bb_lg, 0);
-                phase_mark(pass == 0 ? "nb: first occurrences" : "nb: copies");
-            }
-            // the reverse-complement neighbour bits (tile_rcnb, 12 B per base):
-            // only reads with no forward seed use them (k_align_lane_rc), so by
-            // default they are left for the first align pass that queues enough
-            // such reads (index_rcnb_wanted: C4's forward reads never do, and
-            // its serving index skips their 0.35 s); PA_RCNB_EAGER=1 makes them
-            // now, PA_NO_RCNB=1 never
-            const char *no_rcnb = std::getenv("PA_NO_RCNB"), *eager = std::getenv("PA_RCNB_EAGER");
-            if (k <= 31 && !(no_rcnb && no_rcnb[0] == '1')) {
-                if (eager && eager[0] == '1')
-                    PA_TRY(build_rcnb(idx, st, bb, bb_lg));
-                else
-                    idx->rcnb_pending = 1;
-            }
-            PA_HIP(b.free(bb));
-            idx->nb_spec = full ? 1 : 0;
-            idx->device_bytes += n * 3 * wb;
-        }
-    }
-    idx->nb_pending = 0;
-    return PA_OK;
-}
-
-// Neighbour bits of two-word keys (k_nb_build2): 24 B per base (64-bit
-// present words) when that leaves a quarter of the free memory; no
-// reverse-complement bits (single-word keys only).
+// Two-word keys (k_nb_build2): 24 B per base (64-bit present words) when that
+// leaves a quarter of the free memory; no reverse-complement bits.
 pa_status build_nb2(pa_index *idx, hipStream_t st) {
     const uint64_t n = idx->tile_n;
-    const int k = (int)idx->k;
-    const char *no_nb = std::getenv("PA_NO_NB");
     size_t free_b = 0, total_b = 0;
-    if (!(no_nb && no_nb[0] == '1') && pa::dev_mem_info(&free_b, &total_b) == hipSuccess && n * 24 <= free_b / 4 * 3) {
-        PA_HIP(pa::dev_malloc(&idx->tile_nb, n * 24 + 64));
-        PA_HIP(hipMemsetAsync(idx->tile_nb, 0, n * 24 + 64, st));
-        pa::Bufs b(st);
-        uint64_t *bb = nullptr;  // the build-time Bloom filter, 16 bits per key (freed below)
-        uint32_t bb_lg = 6;
-        if (idx->n_kmers > 0) {
-            while (bb_lg < 33 && (1ull << bb_lg) * 4 < idx->n_kmers) bb_lg++;
-            size_t fb = 0, tb = 0;
-            if (pa::dev_mem_info(&fb, &tb) != hipSuccess) fb = 0;
-            while (bb_lg > 6 && (1ull << bb_lg) * 8 > fb / 4) bb_lg--;
-            if ((1ull << bb_lg) * 64 >= idx->n_kmers * 8 && b.get(&bb, (1ull << bb_lg) * 8) == hipSuccess) {
-                PA_HIP(hipMemsetAsync(bb, 0, (1ull << bb_lg) * 8, st));
-                hipLaunchKernelGGL(k_bloom_build2<2>, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
-                                   dim3(kBlock), 0, st, (const Slot<2> *)idx->table, idx->cap, bb, bb_lg);
-            } else {
-                bb = nullptr;
-            }
-        }
-        for (int pass = 0; pass < 2; pass++)
-            hipLaunchKernelGGL(k_nb_build2, dim3(grid_for(n) > 65536 ? 65536 : grid_for(n)), dim3(kBlock), 0, st,
-                               idx->tile_pk, idx->tile_cls, n, k, (const Slot<2> *)idx->table, idx->home,
-                               idx->n_genomes, (unsigned long long *)idx->tile_nb, idx->class_genomes, idx->goff,
-                               idx->tpos_local, pass, bb, bb_lg);
-        PA_HIP(hipGetLastError());
-        PA_HIP(b.free(bb));
-        idx->nb_spec = 0;
-        idx->device_bytes += n * 24;
-        phase_mark("nb: two-word keys");
-    }
-    idx->nb_pending = 0;
+    if (pa::dev_mem_info(&free_b, &total_b) != hipSuccess || !plan::leaves_quarter(n * 24, free_b)) return PA_OK;
+    PA_HIP(pa::dev_malloc(&idx->tile_nb, n * 24 + 64));
+    PA_HIP(hipMemsetAsync(idx->tile_nb, 0, n * 24 + 64, st));
+    pa::Bufs b(st);
+    uint64_t *bb = nullptr;
+    uint32_t bb_lg = 6;
+    PA_TRY(make_nb_bloom(idx, st, b, &bb, &bb_lg));
+    for (int pass = 0; pass < 2; pass++)
+        hipLaunchKernelGGL(k_nb_build2, dim3(scan_grid(n)), dim3(kBlock), 0, st, idx->tile_pk, idx->tile_cls, n,
+                           (int)idx->k, (const Slot<2> *)idx->table, idx->home, idx->n_genomes,
+                           (unsigned long long *)idx->tile_nb, idx->class_genomes, idx->goff, idx->tpos_local, pass, bb,
+                           bb_lg);
+    PA_HIP(hipGetLastError());
+    PA_HIP(b.free(bb));
+    idx->nb_spec = 0;
+    idx->device_bytes += n * 24;
+    phase_mark("nb: two-word keys");
     return PA_OK;
 }
 
-// Neighbour summaries of three-word keys (k_nb_sum3): 0.5 B per base.
+// Three-word keys: neighbour summaries (k_nb_sum3), 0.5 B per base, in at most a quarter of the free memory.
 pa_status build_nb3(pa_index *idx, hipStream_t st) {
-    const uint64_t n = idx->tile_n;
-    const char *no_nb = std::getenv("PA_NO_NB");
-    const uint64_t bytes = (n / 8 + 64) * 4;
+    const uint64_t n = idx->tile_n, bytes = (n / 8 + 64) * 4;
     size_t free_b = 0, total_b = 0;
-    if (!(no_nb && no_nb[0] == '1') && pa::dev_mem_info(&free_b, &total_b) == hipSuccess && bytes <= free_b / 4) {
-        PA_HIP(pa::dev_malloc(&idx->tile_nb, bytes));
-        PA_HIP(hipMemsetAsync(idx->tile_nb, 0, bytes, st));
-        pa::Bufs b(st);
-        uint64_t *bb = nullptr;  // the build-time Bloom filter, 16 bits per key (freed below)
-        uint32_t bb_lg = 6;
-        if (idx->n_kmers > 0) {
-            while (bb_lg < 33 && (1ull << bb_lg) * 4 < idx->n_kmers) bb_lg++;
-            size_t fb = 0, tb = 0;
-            if (pa::dev_mem_info(&fb, &tb) != hipSuccess) fb = 0;
-            while (bb_lg > 6 && (1ull << bb_lg) * 8 > fb / 4) bb_lg--;
-            if ((1ull << bb_lg) * 64 >= idx->n_kmers * 8 && b.get(&bb, (1ull << bb_lg) * 8) == hipSuccess) {
-                PA_HIP(hipMemsetAsync(bb, 0, (1ull << bb_lg) * 8, st));
-                hipLaunchKernelGGL(k_bloom_build2<3>, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
-                                   dim3(kBlock), 0, st, (const Slot<3> *)idx->table, idx->cap, bb, bb_lg);
-            } else {
-                bb = nullptr;
-            }
-        }
-        hipLaunchKernelGGL(k_nb_sum3, dim3(grid_for(n) > 65536 ? 65536 : grid_for(n)), dim3(kBlock), 0, st,
-                           idx->tile_pk, idx->tile_cls, n, (int)idx->k, (const Slot<3> *)idx->table, idx->home,
-                           (uint32_t *)idx->tile_nb, bb, bb_lg);
-        PA_HIP(hipGetLastError());
-        PA_HIP(b.free(bb));
-        idx->nb_spec = 0;
-        idx->device_bytes += bytes;
-        phase_mark("nb: three-word summaries");
-    }
+    if (pa::dev_mem_info(&free_b, &total_b) != hipSuccess || bytes > free_b / 4) return PA_OK;
+    PA_HIP(pa::dev_malloc(&idx->tile_nb, bytes));
+    PA_HIP(hipMemsetAsync(idx->tile_nb, 0, bytes, st));
+    pa::Bufs b(st);
+    uint64_t *bb = nullptr;
+    uint32_t bb_lg = 6;
+    PA_TRY(make_nb_bloom(idx, st, b, &bb, &bb_lg));
+    hipLaunchKernelGGL(k_nb_sum3, dim3(scan_grid(n)), dim3(kBlock), 0, st, idx->tile_pk, idx->tile_cls, n, (int)idx->k,
+                       (const Slot<3> *)idx->table, idx->home, (uint32_t *)idx->tile_nb, bb, bb_lg);
+    PA_HIP(hipGetLastError());
+    PA_HIP(b.free(bb));
+    idx->nb_spec = 0;
+    idx->device_bytes += bytes;
+    phase_mark("nb: three-word summaries");
+    return PA_OK;
+}
+
+// The neighbour words of the index's key width; PA_NO_NB=1: none (A/B, tests).
+pa_status build_nb(pa_index *idx, hipStream_t st) {
+    if (!env_is("PA_NO_NB", '1'))
+        PA_TRY(idx->nw == 3 ? build_nb3(idx, st) : idx->nw == 2 ? build_nb2(idx, st) : build_nb1(idx, st));
     idx->nb_pending = 0;
     return PA_OK;
 }
 
-template <int NW>
-pa_status build_tiles_nw(pa_index *idx, hipStream_t st) {
-    const uint32_t G = idx->n_genomes;
-    const int k = (int)idx->k;
-    const int wpt = build_run();
-    const uint64_t mask0 = (2 * k - 64 * (NW - 1)) >= 64 ? ~0ull : ((1ull << (2 * k - 64 * (NW - 1))) - 1);
-    Slot<NW> *table = (Slot<NW> *)idx->table;
-    if (idx->tile_n > 0) {  // tiles: 6.5 B per base (class, flags, set sizes, 2-bit string), + margin
-        size_t free_b = 0, total_b = 0;
-        if (pa::dev_mem_info(&free_b, &total_b) != hipSuccess || idx->tile_n * 7 + (2ull << 30) > free_b) idx->tile_n = 0;
+// The align-side Bloom filter of the keys (plan::align_bloom_lg_*: in the
+// memory-side cache, else in HBM, else none).
+pa_status tile_bloom(pa_index *idx, hipStream_t st) {
+    plan::BloomSwitches sw;
+    sw.mb_set = env("PA_BLOOM_MB") != nullptr;
+    sw.mb = env_u64("PA_BLOOM_MB", 128);
+    sw.hbm_off = env_is("PA_BLOOM_HBM", '0');
+    sw.force_large = idx->force_large != 0;
+    uint32_t lg = plan::align_bloom_lg_cache(idx->n_kmers, sw);
+    size_t fb = 0, tb = 0;
+    if (!lg && plan::align_bloom_hbm_wanted(idx->n_kmers, sw) && pa::dev_mem_info(&fb, &tb) == hipSuccess)
+        lg = plan::align_bloom_lg_hbm(idx->n_kmers, fb);
+    if (lg) {
+        PA_HIP(pa::dev_malloc(&idx->bloom, (1ull << lg) * 8));
+        PA_HIP(hipMemsetAsync(idx->bloom, 0, (1ull << lg) * 8, st));
+        bloom_fill(idx, st, idx->bloom, lg, false);
+        idx->bloom_lg = lg;
+        idx->device_bytes += (1ull << lg) * 8;
     }
-    if (idx->tile_n > 0) {  // step 6: genome tiling
-        const uint64_t n = idx->tile_n, nwords = n / 32 + 32;  // padded: the walk reads up to 18 words past a position
-        PA_HIP(pa::dev_malloc(&idx->tile_cls, n * 4));
-        PA_HIP(pa::dev_malloc(&idx->tile_pk, nwords * 8));
-        PA_HIP(hipMemsetAsync(idx->tile_cls, 0xFF, n * 4, st));
-        hipLaunchKernelGGL(k_tile_pack, dim3(grid_for(nwords) > 65536 ? 65536 : grid_for(nwords)), dim3(kBlock), 0, st,
-                           idx->codes, n, idx->tile_pk, nwords);
-        {  // every genome's chunks in one launch (k_tile_cls_all)
-            std::vector<uint64_t> ts(G + 1, 0);
-            for (uint32_t g = 0; g < G; g++) {
-                const uint64_t len = idx->h_goff[g + 1] - idx->h_goff[g];
-                ts[g + 1] = ts[g] + ((uint64_t)k > len ? 0 : (len - k + 1 + wpt - 1) / wpt);
-            }
-            pa::Bufs b(st);
-            uint64_t *d_ts = nullptr;
-            PA_HIP(b.get(&d_ts, (G + 1) * 8));
-            PA_HIP(hipMemcpyAsync(d_ts, ts.data(), (G + 1) * 8, hipMemcpyHostToDevice, st));
-            if (ts[G] > 0) {
-                hipLaunchKernelGGL(k_tile_cls_all<NW>, dim3(grid_for(ts[G])), dim3(kBlock), 0, st, idx->codes, idx->goff,
-                                   d_ts, G, k, mask0, table, idx->home, idx->tile_cls, idx->class_genomes,
-                                   idx->tpos_local, wpt);
-                PA_HIP(hipGetLastError());
-            }
-        }
-        phase_mark("tile classes");
-        // below 2^33 bases: first occurrences as 33-bit concatenated positions
-        // (PA_TPOS_HI=0 keeps them genome-local: tests of that layout)
-        const char *thi = std::getenv("PA_TPOS_HI");
-        if (idx->tpos_local && idx->h_goff[G] < (1ull << 33) && !(thi && thi[0] == '0')) {
-            hipLaunchKernelGGL(k_tpos_concat<NW>, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
-                               dim3(kBlock), 0, st, table, idx->cap, G, idx->class_genomes, idx->goff);
-            PA_HIP(hipGetLastError());
-            idx->tpos_local = 0;
-            phase_mark("first occurrences concatenated");
-        }
-        {  // genome of every 2^16-th position: genome_of is then one or two goff steps
-            const uint64_t nb_ = (n >> 16) + 2;
-            std::vector<uint32_t> gb(nb_);
-            for (uint64_t j = 0; j < nb_; j++) {
-                const uint64_t pos = j << 16;
-                uint32_t g = (uint32_t)(std::upper_bound(idx->h_goff.begin(), idx->h_goff.begin() + G + 1, pos) -
-                                        idx->h_goff.begin());
-                g = g == 0 ? 0 : g - 1;
-                gb[j] = g >= G ? G - 1 : g;
-            }
-            PA_HIP(pa::dev_malloc(&idx->tile_gblk, nb_ * 4));
-            PA_HIP(hipMemcpyAsync(idx->tile_gblk, gb.data(), nb_ * 4, hipMemcpyHostToDevice, st));
-            PA_HIP(hipStreamSynchronize(st));
-            idx->device_bytes += nb_ * 4;
-        }
-        // the lane kernels' view: keys of one word (k <= 31) or two (k <= 63)
-        const bool lane_view = NW <= 3 && k <= 32 * NW - 1;
-        if (lane_view)
-            hipLaunchKernelGGL(k_tile_rep<NW <= 3 ? NW : 1>, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 20)),
-                               dim3(256), 0, st, idx->tile_pk, idx->tile_cls, n, k);
-        if (lane_view) {
-            const uint64_t n_blocks = n / 64 + 8;  // padded: the 250-bp walk reads six blocks from any position
-            PA_HIP(pa::dev_malloc(&idx->tile_lw, n_blocks * 32));
-            hipLaunchKernelGGL(k_tile_walk, dim3((unsigned)std::min<uint64_t>((n_blocks + 3) / 4, 1u << 20)), dim3(256),
-                               0, st, idx->tile_cls, idx->tile_pk, n, G, idx->tile_lw, n_blocks);
-            idx->device_bytes += n_blocks * 32;
-            phase_mark("repeats + walk blocks");
-            // one-substitution neighbours (build_nb): now, or -- when the caller
-            // expects too few reads to repay them -- on the align that brings the
-            // reads past that point (index_maybe_nb)
-            if (idx->nb_skip) {
-                idx->nb_pending = 1;
-            } else {
-                PA_TRY(build_nb(idx, st));
-            }
-            phase_mark("neighbour bits");
-            // the Bloom filter of the keys, for the lane kernel's probes of windows
-            // off the walk (almost all absent).  In the memory-side cache: 16 bits
-            // per key up to PA_BLOOM_MB (default 128: with minimizer blocks of 16 B
-            // a run of ~9 keys shares one block, so the filter needs the room --
-            // at 64 MB c2rc's k_align_lane_na took 3.78 ms, at 128 MB 3.24; 0: none),
-            // fewer down to 8
-            // bits per key.  A reference too large for that gets one in HBM, 16
-            // (down to 8) bits per key in at most 1/8 of the free memory
-            // (PA_BLOOM_HBM=0: none): the off-walk windows of a read cluster
-            // around its mismatches and share minimizer lines, so one Bloom line
-            // answers several table lines (C4 2.94 -> 3.30, C5 2.32 -> 2.70 G
-            // reads/s; C2 keeps the cache-sized one: 3.49 vs 3.41 with 134 MB).
-            // The large-reference layout (PA_LAYOUT=large) takes the HBM form.
-            {
-                const char *bm = std::getenv("PA_BLOOM_MB"), *bh = std::getenv("PA_BLOOM_HBM");
-                const uint64_t cap_b = idx->force_large ? 0ull : (bm ? (uint64_t)std::strtoull(bm, nullptr, 10) : 128ull) << 20;
-                uint32_t lg16 = 6;  // 16 bits per key
-                while (lg16 < 33 && (1ull << lg16) * 64 < idx->n_kmers * 16) lg16++;  // (bloom_block: lg <= 33)
-                uint32_t lg = lg16;
-                while (lg > 6 && (1ull << lg) * 8 > cap_b) lg--;
-                bool ok = cap_b > 0 && idx->n_kmers > 0 && (1ull << lg) * 64 >= idx->n_kmers * 8 && (1ull << lg) * 8 <= cap_b;
-                if (!ok && idx->n_kmers > 0 && !(bh && bh[0] == '0') && (!bm || idx->force_large)) {
-                    size_t fb = 0, tb = 0;
-                    if (pa::dev_mem_info(&fb, &tb) == hipSuccess) {
-                        lg = lg16;  // 16 bits per key, fewer down to 8 if it must, in at most 1/8 of the free memory
-                        while (lg > 6 && (1ull << lg) * 8 > fb / 8) lg--;
-                        ok = (1ull << lg) * 64 >= idx->n_kmers * 8;
-                    }
-                }
-                if (ok) {
-                    PA_HIP(pa::dev_malloc(&idx->bloom, (1ull << lg) * 8));
-                    PA_HIP(hipMemsetAsync(idx->bloom, 0, (1ull << lg) * 8, st));
-                    if (NW == 1)
-                        hipLaunchKernelGGL(k_bloom_build<false>, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
-                                           dim3(kBlock), 0, st, (const Slot<1> *)table, idx->cap, idx->bloom, lg, k);
-                    else if (NW == 2)
-                        hipLaunchKernelGGL(k_bloom_build2<2>, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
-                                           dim3(kBlock), 0, st, (const Slot<2> *)table, idx->cap, idx->bloom, lg);
-                    else
-                        hipLaunchKernelGGL(k_bloom_build2<3>, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
-                                           dim3(kBlock), 0, st, (const Slot<3> *)table, idx->cap, idx->bloom, lg);
-                    idx->bloom_lg = lg;
-                    idx->device_bytes += (1ull << lg) * 8;
-                }
-                phase_mark("Bloom");
-            }
-            {  // the minimizer presence bitmap: 2^25 bits (4 MiB, the size of an XCD's L2)
-               // for references of up to ~30 M distinct minimizers (distinct
-               // k-mers / 9: a minimizer covers ~9 of a genome's k-mers), so
-               // that fewer than ~1 / 4 of the bits are set; none above (C4, C5)
-               // or with PA_NO_MM=1
-                const char *nm = std::getenv("PA_NO_MM");
-                const uint32_t lg = 25;
-                if (NW == 1 && !(nm && nm[0] == '1') && idx->bloom && idx->n_kmers / 9 <= (1ull << lg) / 4 &&
-                    pa::dev_malloc(&idx->mm_bits, (1ull << lg) / 8) == hipSuccess) {
-                    PA_HIP(hipMemsetAsync(idx->mm_bits, 0, (1ull << lg) / 8, st));
-                    hipLaunchKernelGGL(k_mm_build, dim3(grid_for(idx->cap) > 65536 ? 65536 : grid_for(idx->cap)),
-                                       dim3(kBlock), 0, st, (const Slot<1> *)table, idx->cap, idx->mm_bits, lg, k);
-                    idx->mm_lg = lg;
-                    idx->device_bytes += (1ull << lg) / 8;
-                } else {
-                    idx->mm_bits = nullptr;
-                }
-                phase_mark("minimizer bitmap");
-            }
-            {  // the reverse-complement plane (k_tile_rcp), 1 bit per base; PA_NO_RCP=1: none
-                const char *nr = std::getenv("PA_NO_RCP");
-                const uint64_t n_blocks = n / 64 + 5;  // padded like the walk blocks
-                if (NW == 1 && !(nr && nr[0] == '1') && pa::dev_malloc(&idx->tile_rcp, n_blocks * 8) == hipSuccess) {
-                    hipLaunchKernelGGL(k_tile_rcp, dim3((unsigned)std::min<uint64_t>((n_blocks + 3) / 4, 1u << 20)),
-                                       dim3(256), 0, st, idx->tile_cls, idx->tile_pk, n, k, (const Slot<1> *)table,
-                                       idx->home, idx->bloom, idx->bloom_lg, idx->tile_rcp, n_blocks);
-                    idx->device_bytes += n_blocks * 8;
-                } else {
-                    idx->tile_rcp = nullptr;
-                }
-                phase_mark("reverse-complement plane");
-            }
-        }
-        PA_HIP(hipGetLastError());
-        PA_HIP(hipStreamSynchronize(st));
-        idx->device_bytes += n * 4 + nwords * 8;
+    phase_mark("Bloom");
+    return PA_OK;
+}
+
+// The minimizer presence bitmap (one-word keys): 2^25 bits (4 MiB, the size of
+// an XCD's L2) for references of up to ~30 M distinct minimizers (distinct
+// k-mers / 9: a minimizer covers ~9 of a genome's k-mers), so that fewer than
+// ~1 / 4 of the bits are set; none above (C4, C5) or with PA_NO_MM=1.
+pa_status tile_minimizers(pa_index *idx, hipStream_t st) {
+    const uint32_t lg = 25;
+    if (idx->nw == 1 && !env_is("PA_NO_MM", '1') && idx->bloom && idx->n_kmers / 9 <= (1ull << lg) / 4 &&
+        pa::dev_malloc(&idx->mm_bits, (1ull << lg) / 8) == hipSuccess) {
+        PA_HIP(hipMemsetAsync(idx->mm_bits, 0, (1ull << lg) / 8, st));
+        hipLaunchKernelGGL(k_mm_build, dim3(scan_grid(idx->cap)), dim3(kBlock), 0, st, (const Slot<1> *)idx->table,
+                           idx->cap, idx->mm_bits, lg, (int)idx->k);
+        idx->mm_lg = lg;
+        idx->device_bytes += (1ull << lg) / 8;
+    } else {
+        idx->mm_bits = nullptr;
     }
+    phase_mark("minimizer bitmap");
+    return PA_OK;
+}
+
+// The reverse-complement plane (k_tile_rcp; one-word keys), 1 bit per base; PA_NO_RCP=1: none.
+pa_status tile_rc_plane(pa_index *idx, hipStream_t st) {
+    const uint64_t n_blocks = idx->tile_n / 64 + 5;  // padded like the walk blocks
+    if (idx->nw == 1 && !env_is("PA_NO_RCP", '1') && pa::dev_malloc(&idx->tile_rcp, n_blocks * 8) == hipSuccess) {
+        hipLaunchKernelGGL(k_tile_rcp, dim3((unsigned)std::min<uint64_t>((n_blocks + 3) / 4, 1u << 20)), dim3(256), 0, st,
+                           idx->tile_cls, idx->tile_pk, idx->tile_n, (int)idx->k, (const Slot<1> *)idx->table, idx->home,
+                           idx->bloom, idx->bloom_lg, idx->tile_rcp, n_blocks);
+        idx->device_bytes += n_blocks * 8;
+    } else {
+        idx->tile_rcp = nullptr;
+    }
+    phase_mark("reverse-complement plane");
+    return PA_OK;
+}
+
+// The parts in their order.  The tiling takes 6.5 B per base (class, flags,
+// set sizes, 2-bit string): without that and a 2 GiB margin free there is none.
+pa_status build_align_view(pa_index *idx, hipStream_t st) {
+    size_t free_b = 0, total_b = 0;
+    if (idx->tile_n > 0 &&
+        (pa::dev_mem_info(&free_b, &total_b) != hipSuccess || idx->tile_n * 7 + (2ull << 30) > free_b))
+        idx->tile_n = 0;
+    if (idx->tile_n == 0) return PA_OK;
+    PA_TRY(tile_classes(idx, st));
+    phase_mark("tile classes");
+    PA_TRY(tile_first_concat(idx, st));
+    PA_TRY(tile_genome_blocks(idx, st));
+    PA_TRY(tile_walk_blocks(idx, st));
+    // one-substitution neighbours (build_nb): now, or -- when the caller
+    // expects too few reads to repay them -- on the align that brings the
+    // reads past that point (index_note_reads)
+    if (idx->nb_skip)
+        idx->nb_pending = 1;
+    else
+        PA_TRY(build_nb(idx, st));
+    phase_mark("neighbour bits");
+    PA_TRY(tile_bloom(idx, st));
+    PA_TRY(tile_minimizers(idx, st));
+    PA_TRY(tile_rc_plane(idx, st));
+    PA_HIP(hipGetLastError());
+    PA_HIP(hipStreamSynchronize(st));
     return PA_OK;
 }
 
@@ -2299,9 +2223,8 @@ template <int NW>
 pa_status lookup_nw(const pa_index *idx, const uint8_t *d_kmers, uint64_t n, int64_t *d_cls, uint32_t *d_size,
                     hipStream_t st) {
     const int k = (int)idx->k;
-    const uint64_t mask0 = (2 * k - 64 * (NW - 1)) >= 64 ? ~0ull : ((1ull << (2 * k - 64 * (NW - 1))) - 1);
     hipLaunchKernelGGL(k_lookup<NW>, dim3(grid_for(n)), dim3(kBlock), 0, st, (const Slot<NW> *)idx->table, idx->home,
-                       d_kmers, n, k, mask0, idx->n_genomes, idx->class_genomes, d_cls, d_size);
+                       d_kmers, n, k, mask0_of(k, NW), idx->n_genomes, idx->class_genomes, d_cls, d_size);
     PA_HIP(hipGetLastError());
     return PA_OK;
 }
@@ -2320,86 +2243,50 @@ void extsim_slots_nw(const pa_index *idx, const uint32_t *d_group, uint32_t n_gr
 
 namespace pa {
 
+// Everything an index owns on the device: the align-side view
+// (release_align_view), the positions view, then the table, classes, codes and
+// align scratch.  Every pointer is null afterwards: a second call frees nothing.
 void index_release(pa_index *idx) {
     index_release_coverage(idx);
-    pa::dev_free(idx->table);
-    pa::dev_free(idx->class_off);
-    pa::dev_free(idx->class_size);
-    pa::dev_free(idx->class_genomes);
-    pa::dev_free(idx->class_mask);
-    pa::dev_free(idx->codes);
-    pa::dev_free(idx->goff);
-    pa::dev_free(idx->fwd_len);
-    idx->fwd_len = nullptr;
-    pa::dev_free(idx->tile_cls);
-    pa::dev_free(idx->tile_pk);
-    pa::dev_free(idx->tile_lw);
-    idx->tile_lw = nullptr;
-    pa::dev_free(idx->tile_big);
-    idx->tile_big = nullptr;
-    idx->tile_big_mg = -1;
-    pa::dev_free(idx->tile_nb);
-    idx->tile_nb = nullptr;
-    pa::dev_free(idx->tile_nb1);
-    idx->tile_nb1 = nullptr;
-    idx->nb_split = ~0ull;
-    pa::dev_free(idx->tile_rcnb);
-    idx->tile_rcnb = nullptr;
-    pa::dev_free(idx->tile_nbbig);
-    idx->tile_nbbig = nullptr;
-    idx->tile_nbbig_mg = -1;
-    pa::dev_free(idx->tile_nbm);
-    idx->tile_nbm = nullptr;
-    idx->tile_nbm_mg = -1;
-    pa::dev_free(idx->bloom);
-    idx->bloom = nullptr;
-    pa::dev_free(idx->tile_rcp);
-    idx->tile_rcp = nullptr;
-    pa::dev_free(idx->mm_bits);
-    idx->mm_bits = nullptr;
-    pa::dev_free(idx->tile_gblk);
-    idx->tile_gblk = nullptr;
-    idx->bloom_lg = 0;
-    idx->tile_cls = nullptr;
-    idx->tile_pk = nullptr;
-    pa::dev_free(idx->ws.ptr);
-    pa::dev_free(idx->queue);
-    pa::dev_free(idx->queue_hard);
-    pa::dev_free(idx->queue_na);
-    pa::dev_free(idx->queue_na2);
-    pa::dev_free(idx->queue_na_keys);
-    pa::dev_free(idx->queue_rc);
-    pa::dev_free(idx->queue_rc_anc);
-    idx->queue_na2 = nullptr;
-    idx->queue_na_keys = nullptr;
-    idx->queue_rc = nullptr;
-    idx->queue_rc_anc = nullptr;
-    pa::dev_free(idx->na_count);
-    pa::dev_free(idx->seg_cnt);
-    idx->seg_cnt = nullptr;
-    pa::dev_free(idx->qmask);
-    pa::dev_free(idx->qdrop);
-    idx->qmask = nullptr;
-    idx->qdrop = nullptr;
+    release_align_view(idx);
+    dev_release(idx->table);
+    dev_release(idx->class_off);
+    dev_release(idx->class_size);
+    dev_release(idx->class_genomes);
+    dev_release(idx->class_mask);
+    dev_release(idx->codes);
+    dev_release(idx->goff);
+    dev_release(idx->fwd_len);
+    dev_release(idx->ws.ptr);
+    idx->ws.bytes = 0;
+    dev_release(idx->queue);
+    dev_release(idx->queue_hard);
+    dev_release(idx->queue_na);
+    dev_release(idx->queue_na2);
+    dev_release(idx->queue_na_keys);
+    dev_release(idx->queue_rc);
+    dev_release(idx->queue_rc_anc);
+    idx->queue_cap = 0;
+    dev_release(idx->na_count);
+    dev_release(idx->seg_cnt);
+    dev_release(idx->qmask);
+    dev_release(idx->qdrop);
     idx->qmask_cap = 0;
-    idx->queue_na = nullptr;
-    idx->na_count = nullptr;
-    pa::dev_free(idx->counters);
+    dev_release(idx->counters);
     for (auto e : idx->ev_start) hipEventDestroy(e);
     for (auto e : idx->ev_stop) hipEventDestroy(e);
     for (auto &e : idx->kev) {
         hipEventDestroy(e.start);
         hipEventDestroy(e.stop);
     }
+    idx->ev_start.clear();
+    idx->ev_stop.clear();
     idx->kev.clear();
-    idx->table = nullptr;
 }
 
 pa_status index_build_rcnb(pa_index *idx, hipStream_t st) {
     if (!idx->rcnb_pending) return PA_OK;
-    std::unique_ptr<PhaseTimer> own;
-    if (!t_phase) own.reset(new PhaseTimer(st));
-    PhaseScope ps(t_phase ? t_phase : own.get());
+    TimedPhases tp(st);
     Bufs b(st);
     uint64_t *bb = nullptr;
     uint32_t bb_lg = 6;
@@ -2417,41 +2304,73 @@ pa_status index_prepare(pa_index *idx, hipStream_t st, uint64_t reads_hint, bool
     if (!idx->tiles_pending) {  // (tiles made: the pending neighbour bits, if the reads still to come repay them)
         if (complete && idx->nb_pending &&
             (reads_hint == ~0ull || nb_repaid(idx->reads_seen + reads_hint, idx->tile_n, idx->nw))) {
-            std::unique_ptr<PhaseTimer> own;
-            if (!t_phase) own.reset(new PhaseTimer(st));
-            PhaseScope ps(t_phase ? t_phase : own.get());
+            TimedPhases tp(st);
             return build_nb(idx, st);
         }
         return PA_OK;
     }
     idx->tiles_pending = 0;
-    std::unique_ptr<PhaseTimer> own;  // (timed on its own unless a timed build called it)
-    if (!t_phase) own.reset(new PhaseTimer(st));
-    PhaseScope ps(t_phase ? t_phase : own.get());
+    TimedPhases tp(st);  // (timed on its own unless a timed build called it)
     const uint64_t bases = idx->h_goff.empty() ? 0 : idx->h_goff.back();
     idx->nb_skip = reads_hint != ~0ull && !nb_repaid(reads_hint, bases, idx->nw);
-    pa_status rc = idx->nw == 3   ? build_tiles_nw<3>(idx, st)
-                   : idx->nw == 2 ? build_tiles_nw<2>(idx, st)
-                                  : build_tiles_nw<1>(idx, st);  // (keys of one to three words)
+    const pa_status rc = build_align_view(idx, st);
     idx->nb_skip = 0;
-    if (rc != PA_OK) {  // the index stays usable without its align-side view
-        pa::dev_free(idx->tile_cls); pa::dev_free(idx->tile_pk); pa::dev_free(idx->tile_lw); pa::dev_free(idx->tile_nb);
-        pa::dev_free(idx->tile_nb1);
-        idx->tile_nb1 = nullptr, idx->nb_split = ~0ull, idx->rcnb_pending = 0;
-        pa::dev_free(idx->tile_gblk); pa::dev_free(idx->bloom); pa::dev_free(idx->tile_rcp); pa::dev_free(idx->tile_rcnb);
-        pa::dev_free(idx->mm_bits);
-        idx->mm_bits = nullptr;
-        idx->tile_rcnb = nullptr;
-        idx->tile_cls = nullptr, idx->tile_pk = nullptr, idx->tile_lw = nullptr, idx->tile_nb = nullptr;
-        idx->tile_gblk = nullptr, idx->bloom = nullptr, idx->bloom_lg = 0, idx->tile_n = 0, idx->tile_rcp = nullptr;
-    }
+    if (rc != PA_OK) release_align_view(idx);  // the index stays usable without its align-side view
     return rc;
+}
+
+// The distinct k-mers of the encoded genomes, estimated (k_hll, plan::hll_distinct).
+static pa_status estimate_distinct(pa_index *idx, hipStream_t st, uint64_t *distinct) {
+    const int k = (int)idx->k;
+    Bufs b(st);
+    uint32_t *reg = nullptr;
+    PA_HIP(b.get(&reg, (4ull << kHllBits)));
+    PA_HIP(hipMemsetAsync(reg, 0, (4ull << kHllBits), st));
+    for_each_genome_windows(idx, k, [&](uint32_t, uint64_t start, uint64_t nwin) {
+        const dim3 grid(grid_for((nwin + kRun - 1) / kRun));
+        with_nw(idx->nw, [&](auto w) {
+            hipLaunchKernelGGL(k_hll<w()>, grid, dim3(kBlock), 0, st, idx->codes, start, nwin, k, mask0_of(k, w()), reg);
+        });
+    });
+    std::vector<uint32_t> h(1u << kHllBits);
+    PA_HIP(hipMemcpyAsync(h.data(), reg, (4ull << kHllBits), hipMemcpyDeviceToHost, st));
+    PA_HIP(hipStreamSynchronize(st));
+    *distinct = plan::hll_distinct(h.data(), (uint32_t)h.size());
+    return PA_OK;
+}
+
+// The table's capacity by the plan (pa_index_plan.h): on the genome windows,
+// else -- or when PA_CAP_HLL=1 or the large layout ask for it (tests, A/B) --
+// on the distinct estimate.
+static pa_status table_capacity(pa_index *idx, uint64_t windows, hipStream_t st, uint64_t *out) {
+    const int sb = slot_bytes(idx->nw);
+    size_t free_b = 0, total_b = 0;
+    PA_HIP(pa::dev_mem_info(&free_b, &total_b));
+    uint64_t cap = plan::table_cap_windows(windows, sb, free_b, idx->compact_table && idx->nw == 1,
+                                           env_int("PA_CAP_MULT", plan::kNoCapMult));
+    const bool forced = env_is("PA_CAP_HLL", '1') || idx->force_large || free_b == 0;
+    if (forced) cap = 0;
+    if (cap == 0 && idx->k > 0 && windows > 0) {
+        uint64_t distinct = 0;
+        PA_TRY(estimate_distinct(idx, st, &distinct));
+        idx->distinct_estimate = distinct;
+        if (forced) PA_HIP(pa::dev_mem_info(&free_b, &total_b));
+        const char *first = env("PA_CAP_DISTINCT");  // A/B: this many slots per distinct k-mer first
+        cap = plan::table_cap_distinct(distinct, windows, sb, free_b, forced, first ? std::atof(first) : 0.0);
+        if (cap == 0) {
+            set_error("index build: the k-mer table of ~" + std::to_string(distinct) +
+                      " distinct k-mers does not fit the free device memory" +
+                      (idx->both_strands ? " (a both-strand index needs about twice a forward index's memory)" : ""));
+            return PA_ENOMEM;
+        }
+    }
+    *out = plan::table_cap_lines(cap);
+    return PA_OK;
 }
 
 pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, uint32_t n, int64_t k,
                       hipStream_t st, bool defer_tiles, uint8_t *dev_codes) {
-    PhaseTimer tm(st);
-    PhaseScope ps(&tm);
+    TimedPhases tm(st);
     idx->k = k;
     idx->nw = k > 0 ? key_words(k) : 1;
     idx->n_genomes = n;
@@ -2492,18 +2411,17 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
     idx->total_windows = windows;
     // genome tiling for keys of one or two words (k <= 63) while positions fit 32 bits (tpos);
     // PA_NO_TILE=1 turns it off (A/B measurements)
-    const char *no_tile = std::getenv("PA_NO_TILE");
     uint64_t max_glen = 0;
     for (uint32_t g = 0; g < n; g++) max_glen = std::max<uint64_t>(max_glen, goff[g + 1] - goff[g]);
-    idx->tile_n = (idx->nw <= 3 && k > 0 && total > 0 && max_glen < 0xFFFFFFFFull && !(no_tile && no_tile[0] == '1'))
+    idx->tile_n = (idx->nw <= 3 && k > 0 && total > 0 && max_glen < 0xFFFFFFFFull && !env_is("PA_NO_TILE", '1'))
                       ? total : 0;
     idx->tpos_local = total >= 0xFFFFFFFFull ? 1 : 0;
     // PA_LAYOUT=large (tests): every choice the build makes for a reference too
     // large for the default layout (C5: 8 Gbp) -- table sized on the distinct
     // estimate at 1.43 slots per k-mer, genome-local first occurrences, the 12-B
     // present-only neighbour bits, no Bloom filter -- on a small reference
-    if (const char *e = std::getenv("PA_LAYOUT")) idx->force_large = std::strcmp(e, "large") == 0;
-    if (const char *e = std::getenv("PA_TPOS_LOCAL")) idx->tpos_local |= e[0] == '1';  // tests: the >= 4 Gbp layout
+    if (const char *e = env("PA_LAYOUT")) idx->force_large = std::strcmp(e, "large") == 0;
+    idx->tpos_local |= env_is("PA_TPOS_LOCAL", '1');  // tests: the >= 4 Gbp layout
     idx->tpos_local |= idx->force_large;
     if (dev_codes)
         idx->codes = dev_codes;  // (index_reduce: the 2-bit codes are on the device already)
@@ -2517,41 +2435,25 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
         PA_HIP(pa::dev_malloc(&idx->fwd_len, std::max<uint64_t>(n, 1) * 8));
         PA_HIP(hipMemcpyAsync(idx->fwd_len, idx->h_fwd_len.data(), (uint64_t)n * 8, hipMemcpyHostToDevice, st));
     }
-    if (total > 0 && !dev_codes && both) {
-        // only the forward text is uploaded; k_encode_strands writes the regions
+    if (total > 0 && !dev_codes) {
+        // step 1: the forward text is uploaded and encoded (both strands: k_encode_strands writes the regions)
         uint8_t *ascii = nullptr;
         uint64_t *d_fgoff = nullptr;
         unsigned long long *bad = nullptr, h_bad = ~0ull;
         Bufs b(st);  // (the staging buffers go before the table is allocated)
-        PA_HIP(b.get(&ascii, fwd_total + kExpandPad));
-        PA_HIP(b.get(&d_fgoff, (n + 1) * 8));
+        PA_HIP(b.get(&ascii, both ? fwd_total + kExpandPad : fwd_total));
+        if (both) PA_HIP(b.get(&d_fgoff, (n + 1) * 8));
         PA_HIP(b.get(&bad, 8));
         tm.mark("alloc");
         PA_HIP(hipMemsetAsync(bad, 0xFF, 8, st));
-        PA_HIP(hipMemcpyAsync(d_fgoff, fwd_goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+        if (both) PA_HIP(hipMemcpyAsync(d_fgoff, fwd_goff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
         PA_HIP(hipMemcpyAsync(ascii, genomes + text_off, fwd_total, hipMemcpyHostToDevice, st));
         tm.mark("upload");
-        const unsigned grid = grid_for((total + kExpandRun - 1) / kExpandRun);
-        hipLaunchKernelGGL(k_encode_strands, dim3(grid > 65536 ? 65536 : grid), dim3(kBlock), 0, st, ascii, d_fgoff,
-                           idx->goff, n, idx->codes, bad);
-        PA_HIP(hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, st));
-        PA_HIP(hipStreamSynchronize(st));
-        if (h_bad != ~0ull) {
-            set_error("genome text may only contain A, C, G, T and N (byte " + std::to_string(h_bad) + ")");
-            return PA_EINVAL;
-        }
-    } else if (total > 0 && !dev_codes) {
-        uint8_t *ascii = nullptr;  // ASCII staging buffer, freed before the table is allocated
-        unsigned long long *bad = nullptr, h_bad = ~0ull;
-        Bufs b(st);
-        PA_HIP(b.get(&ascii, total));
-        PA_HIP(b.get(&bad, 8));
-        tm.mark("alloc");
-        PA_HIP(hipMemsetAsync(bad, 0xFF, 8, st));
-        PA_HIP(hipMemcpyAsync(ascii, genomes + goff[0], total, hipMemcpyHostToDevice, st));
-        tm.mark("upload");
-        hipLaunchKernelGGL(k_encode, dim3(grid_for(total) > 65536 ? 65536 : grid_for(total)), dim3(kBlock), 0, st,
-                           ascii, idx->codes, total, bad);
+        if (both)
+            hipLaunchKernelGGL(k_encode_strands, dim3(scan_grid((total + kExpandRun - 1) / kExpandRun)), dim3(kBlock), 0,
+                               st, ascii, d_fgoff, idx->goff, n, idx->codes, bad);
+        else
+            hipLaunchKernelGGL(k_encode, dim3(scan_grid(total)), dim3(kBlock), 0, st, ascii, idx->codes, total, bad);
         PA_HIP(hipMemcpyAsync(&h_bad, bad, 8, hipMemcpyDeviceToHost, st));
         PA_HIP(hipStreamSynchronize(st));
         if (h_bad != ~0ull) {
@@ -2560,98 +2462,10 @@ pa_status index_build(pa_index *idx, const char *genomes, const uint64_t *goff, 
         }
     }
     tm.mark("encode");
-    // Table capacity (whole 64-B lines).  Load 1/4 of the genome windows when
-    // the table fits a third of the free device memory (absent keys -- the
-    // sequencing-error windows -- then end in their home slot 3 times out of
-    // 4), else 1/2 of the windows if table + build scratch fit; a reference
-    // too large for either is sized on its distinct k-mers (HyperLogLog
-    // estimate + 3 %): 4, 2 or 1.43 slots per distinct k-mer, the largest that
-    // fits.  The build needs 8 B of scratch per slot (list offsets; the rest
-    // of its bookkeeping lives in the slots) and at most 4 B per genome window
-    // for the genome lists; the sizing still counts 20 B per slot, which
-    // leaves the align-side view (tiles, neighbour bits) its room.
+    // step 2: the table
     const int sb = slot_bytes(idx->nw);
-    const uint64_t per_slot = (uint64_t)sb + 20;
-    size_t free_b = 0, total_b = 0;
-    PA_HIP(pa::dev_mem_info(&free_b, &total_b));
-    const uint64_t reserve = windows * 4 + (1ull << 30);
-    auto fits = [&](uint64_t c) { return c * per_slot + reserve <= (uint64_t)free_b; };
     uint64_t cap = 0;
-    // (PA_BUILD_COMPACT: 2 per window for one-word keys -- the scans of the
-    // table and its first touches shrink with it; aligns ~2-4 % slower, C4 job
-    // +13 %, C2 +15 %; two- and three-word keys, inserted one window at a
-    // time, built slower at that load: k = 63 0.171 -> 0.196 s)
-    const bool compact = idx->compact_table && idx->nw == 1;
-    if (!compact && (4 * windows + 64) * (uint64_t)sb <= free_b / 3 && fits(4 * windows + 64))
-        cap = 4 * windows + 64;
-    else if (fits(2 * windows + 64))
-        cap = 2 * windows + 64;
-    if (const char *e = std::getenv("PA_CAP_MULT")) cap = (uint64_t)std::max(2, std::atoi(e)) * windows + 64;
-    if (const char *e = std::getenv("PA_CAP_HLL")) {  // tests / A-B: size on the distinct estimate, at 1.43 per k-mer
-        if (e[0] == '1') cap = 0, free_b = (size_t)0;
-    }
-    if (idx->force_large) cap = 0, free_b = (size_t)0;
-    if (cap == 0 && k > 0 && windows > 0) {
-        Bufs b(st);
-        uint32_t *reg = nullptr;
-        PA_HIP(b.get(&reg, (4ull << kHllBits)));
-        PA_HIP(hipMemsetAsync(reg, 0, (4ull << kHllBits), st));
-        const uint64_t mask0 = (2 * k - 64 * (idx->nw - 1)) >= 64 ? ~0ull : ((1ull << (2 * k - 64 * (idx->nw - 1))) - 1);
-        for (uint32_t g = 0; g < n; g++) {
-            const uint64_t len = idx->h_goff[g + 1] - idx->h_goff[g];
-            if ((uint64_t)k > len) continue;
-            const uint64_t nwin = len - k + 1;
-            const dim3 grid(grid_for((nwin + kRun - 1) / kRun));
-            with_nw(idx->nw, [&](auto w) {
-                hipLaunchKernelGGL(k_hll<w()>, grid, dim3(kBlock), 0, st, idx->codes, idx->h_goff[g], nwin, (int)k, mask0,
-                                   reg);
-            });
-        }
-        std::vector<uint32_t> h(1u << kHllBits);
-        PA_HIP(hipMemcpyAsync(h.data(), reg, (4ull << kHllBits), hipMemcpyDeviceToHost, st));
-        PA_HIP(hipStreamSynchronize(st));
-        b.free(reg);
-        const double mm = (double)(1u << kHllBits);
-        double z = 0;
-        uint32_t zeros = 0;
-        for (uint32_t v : h) {
-            z += std::ldexp(1.0, -(int)v);
-            zeros += v == 0;
-        }
-        double est = (0.7213 / (1.0 + 1.079 / mm)) * mm * mm / z;
-        if (est < 2.5 * mm && zeros) est = mm * std::log(mm / zeros);
-        const uint64_t distinct = (uint64_t)(est * 1.03) + 64;
-        idx->distinct_estimate = distinct;
-        const bool forced = free_b == 0;
-        if (forced) PA_HIP(pa::dev_mem_info(&free_b, &total_b));
-        // (2.5 before 2: C5's kept 2.65 G k-mers at load 0.39 instead of 0.48 run 4-7 % faster,
-        // profiles/r05/ab_c5_table.txt -- and build ~1.5 s slower: the larger table leaves the
-        // neighbour words no free range in the slab pool, whose trim then stalls a hipMalloc)
-        // (PA_BUILD_COMPACT does not apply here: C5's job index at 2 per k-mer
-        // built no faster, 4.58 vs 4.47 s, and the serving index built after
-        // it in the same process, placed in its freed slabs, aligned 10 % slower)
-        double mults[4] = {4.0, 2.5, 2.0, 1.43};
-        if (const char *e = std::getenv("PA_CAP_DISTINCT")) {  // A/B: this many slots per distinct k-mer first
-            const double m = std::atof(e);
-            if (m >= 1.2 && m <= 8.0) mults[0] = m, mults[1] = 2.0, mults[2] = 1.43;
-        }
-        for (double mult : mults) {
-            const uint64_t c = (uint64_t)(mult * (double)distinct) + 64;
-            if (forced && mult > 1.5) continue;
-            if (fits(c)) {
-                cap = c;
-                break;
-            }
-        }
-        if (cap == 0) {
-            set_error("index build: the k-mer table of ~" + std::to_string(distinct) +
-                      " distinct k-mers does not fit the free device memory" +
-                      (both ? " (a both-strand index needs about twice a forward index's memory)" : ""));
-            return PA_ENOMEM;
-        }
-    }
-    if (cap == 0) cap = 64;
-    cap = (cap + 3) / 4 * 4;  // whole 64-B lines (the fast kernel probes a line per step)
+    PA_TRY(table_capacity(idx, windows, st, &cap));
     idx->cap = cap;
     idx->home = pad::HomeCfg{cap};
     PA_HIP(pa::dev_malloc(&idx->table, idx->cap * sb));
@@ -2723,8 +2537,7 @@ pa_status index_reduce(pa_index *idx, const uint32_t *sel, uint32_t n, hipStream
     };
     uint8_t *codes = nullptr;
     hipError_t e = pa::dev_malloc(&codes, std::max<uint64_t>(goff[n], 1));
-    const char *inplace = std::getenv("PA_REDUCE_INPLACE");  // tests: force the in-place path
-    if (e == hipSuccess && inplace && inplace[0] == '1') {
+    if (e == hipSuccess && env_is("PA_REDUCE_INPLACE", '1')) {  // tests: force the in-place path
         pa::dev_free(codes);
         codes = nullptr;
         e = hipErrorOutOfMemory;
@@ -2745,7 +2558,7 @@ pa_status index_reduce(pa_index *idx, const uint32_t *sel, uint32_t n, hipStream
         for (const Run &u : runs) overlap |= u.to != u.from && u.to + u.len > u.from;
         // PA_REDUCE_INJECT=bounce|copy (tests): the bounce allocation, or the
         // copy after the first run, fails
-        const char *inj = std::getenv("PA_REDUCE_INJECT");
+        const char *inj = env("PA_REDUCE_INJECT");
         const bool inj_bounce = inj && std::strcmp(inj, "bounce") == 0, inj_copy = inj && std::strcmp(inj, "copy") == 0;
         if (overlap && (e = inj_bounce ? hipErrorOutOfMemory : pa::dev_malloc(&bounce, kBounce)) != hipSuccess) {
             (void)hipGetLastError();
@@ -2872,7 +2685,7 @@ pa_status reads_synthesize(const pa_index *idx, pa_reads *r, uint64_t n, uint32_
             const double t = x < 0 ? 0 : (x > 1 ? 1 : x);
             return (uint32_t)std::min(16777215.0, t * 16777216.0);
         };
-        hipLaunchKernelGGL(k_synth_reads, dim3(grid_for(r->n_bases) > 65536 ? 65536 : grid_for(r->n_bases)),
+        hipLaunchKernelGGL(k_synth_reads, dim3(scan_grid(r->n_bases)),
                            dim3(kBlock), 0, st, idx->codes, idx->goff, d_elig, (uint32_t)elig.size(), n, len, first,
                            seed, th(sub_rate), th(rc_rate), th(foreign_rate), r->seq, r->qual, r->off, idx->fwd_len);
     }

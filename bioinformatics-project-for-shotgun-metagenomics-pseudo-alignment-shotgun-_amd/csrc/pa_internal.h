@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
 #include <map>
 #include <memory>
 #include <string>
@@ -17,6 +18,13 @@ namespace pa {
 
 // Last error, thread-local; set by the PA_* macros below.
 void set_error(const std::string &msg);
+
+// Environment switches (tests and A/B runs), read where and when they are used:
+// tests flip them between two calls of one process, so nothing is kept.
+inline const char *env(const char *name) { return std::getenv(name); }
+inline bool env_is(const char *name, char c) { const char *e = env(name); return e && e[0] == c; }
+inline uint64_t env_u64(const char *name, uint64_t unset) { const char *e = env(name); return e ? std::strtoull(e, nullptr, 10) : unset; }
+inline int env_int(const char *name, int unset) { const char *e = env(name); return e ? std::atoi(e) : unset; }
 
 // The one HIP-error path: the message holds the operation's name (ErrOp, when
 // one is set), HIP's text, file:line and the call; the sticky error is cleared;
@@ -74,6 +82,11 @@ inline hipError_t dev_malloc(T **p, size_t n) {
     return dev_malloc_raw((void **)p, n);
 }
 hipError_t dev_free(void *p);
+template <typename T>
+inline void dev_release(T *&p) {  // freed and forgotten: a second call frees nothing
+    (void)dev_free((void *)p);
+    p = nullptr;
+}
 // Like dev_malloc but never gives the pool's idle slabs back to the driver to
 // make room (whose reclaim stalls): hipErrorOutOfMemory when no free range of
 // the pool and no free device memory can hold n bytes.
@@ -218,7 +231,7 @@ struct pa_index {
     uint64_t *tile_lw = nullptr;       // [4 (tile_n / 64 + 5)] lane-walk blocks: 2-bit words + flag planes (k_tile_walk)
     uint64_t *tile_big = nullptr;      // [tile_n / 64 + 4] plane "set size > tile_big_mg" (pa_align, cached)
     int64_t tile_big_mg = -1;          // the --max-genomes value tile_big was made for (-1: none)
-    void *tile_nb = nullptr;           // [3 tile_n] one-substitution neighbour bits (k_nb_build), optional:
+    void *tile_nb = nullptr;           // [3 tile_n] one-substitution neighbour bits (k_nb_first), optional:
     int nb_spec = 0;                   //   1: 64-bit words, present | specific << 32; 0: 32-bit words, present
     void *tile_nb1 = nullptr;          //   its second piece, words nb_split.. (null: one piece; pa_device.h NbW)
     uint64_t nb_split = ~0ull;
@@ -278,6 +291,33 @@ struct pa_index {
     double prof_ms = 0;
     uint64_t prof_launches = 0;
 };
+
+namespace pa {
+// The one list of an index's align-side view: every buffer made by
+// index_prepare, the neighbour-bit builds and the align pass's cached planes,
+// and the state that describes them.  Afterwards the index is one without a
+// tiling (the exact kernel serves it); a second call frees nothing.
+inline void release_align_view(pa_index *idx) {
+    dev_release(idx->tile_cls);
+    dev_release(idx->tile_pk);
+    dev_release(idx->tile_lw);
+    dev_release(idx->tile_gblk);
+    dev_release(idx->tile_nb);
+    dev_release(idx->tile_nb1);
+    dev_release(idx->tile_rcnb);
+    dev_release(idx->bloom);
+    dev_release(idx->mm_bits);
+    dev_release(idx->tile_rcp);
+    dev_release(idx->tile_big);
+    dev_release(idx->tile_nbbig);
+    dev_release(idx->tile_nbm);
+    idx->tile_n = 0;
+    idx->nb_split = ~0ull;
+    idx->nb_spec = idx->nb_pending = idx->rcnb_pending = idx->rcnb_checks = 0;
+    idx->bloom_lg = idx->mm_lg = 0;
+    idx->tile_big_mg = idx->tile_nbbig_mg = idx->tile_nbm_mg = -1;
+}
+}  // namespace pa
 
 struct pa_reads {
     int device = 0;

@@ -194,8 +194,8 @@ pa_status reduce_sets(const pa_lineage *l, const uint8_t *d_type, const uint64_t
     PA_HIP(hipMemsetAsync(qcount, 0, 8, st));
     PA_HIP(hipMemsetAsync(err, 0, 4, st));
     const TreeDev t{l->parent, l->last, l->node_of, l->gpre, l->n_nodes, l->n_genomes};
-    const char *e = std::getenv("PA_LINEAGE_LDS");  // (0: global atomics for every tree; read per call, as PA_BOOT_LDS)
-    const bool lds = l->n_nodes <= PA_LINEAGE_LDS_NODES && !(e && e[0] == '0');
+    // (PA_LINEAGE_LDS=0: global atomics for every tree; read per call, as PA_BOOT_LDS)
+    const bool lds = l->n_nodes <= PA_LINEAGE_LDS_NODES && !pa::env_is("PA_LINEAGE_LDS", '0');
     const size_t lds_bytes = lds ? (size_t)l->n_nodes * 4 : 0;
     // a block's uint32 histogram cannot wrap: a batch holds fewer than 2^32 sets
     const unsigned grid = grid_for(n, 2048);

@@ -215,8 +215,7 @@ pa_status align_pairs(pa_index *idx, const pa_reads *r1, const pa_reads *r2, con
     PA_HIP(hipMemsetAsync(d_cnt, 0, 16, st));
     PA_HIP(hipMemsetAsync(d_len + n, 0, 4, st));
     // ---- combine
-    const char *e = std::getenv("PA_PAIR_COMBINE");
-    const int combine = !(e && e[0] == '0');
+    const int combine = !pa::env_is("PA_PAIR_COMBINE", '0');
     hipLaunchKernelGGL(k_pair_combine, dim3(std::min(grid_for(n), 2048u)), dim3(kBlock), 0, st, m1, m2, n, combine,
                        d_type, d_qf, d_hr, d_len, d_src, d_queue, d_cnt);
     PA_HIP(hipGetLastError());

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Model of the Bloom blocks k_nb_build touches per wave instruction (random
-sequence, k = 31, minimizer 15-mers of a random order): one window per lane
-and one substituted offset j per step (k_nb_build pass 0) vs the windows'
+"""Model of the Bloom blocks the neighbour-bit build's pass 0 touches per wave
+instruction (random sequence, k = 31, minimizer 15-mers of a random order): one
+window per lane and one substituted offset j per step (the order k_nb_first
+replaced) vs the windows'
 (window, substituted position) pairs in position order, 64 per step
 (k_nb_first).  Distinct blocks ~ memory requests.
 
