@@ -103,6 +103,14 @@ pa_status check_acc(const pa::AccBase *acc, const pa_index *idx, const char *typ
     return PA_OK;
 }
 
+// A selection of pa_reads_select / pa_extract_fastq_file (not NULL).
+pa_status check_extract_spec(const pa_extract_spec *spec) {
+    PA_CHECK(pa::extract_mask_ok(spec->type_mask), PA_EINVAL,
+             "type_mask must hold at least one of the four type bits and no other");
+    PA_CHECK((spec->flags & ~PA_EXTRACT_INVERT) == 0, PA_EINVAL, "unknown flag bits in pa_extract_spec.flags");
+    return PA_OK;
+}
+
 // The index's device current and its align-side view made.
 pa_status prepare_pass(const pa_index *idx, void *stream) {
     PA_HIP(hipSetDevice(idx->device));
@@ -604,6 +612,33 @@ pa_status pa_align_fastq_range(const pa_index *idx, const char *path, uint64_t o
     }
     if (ids) *ids = set;
     return PA_OK;
+}
+
+pa_status pa_reads_select(const pa_index *idx, const pa_reads *reads, const pa_params *params,
+                          const pa_extract_spec *spec, uint8_t *selected, uint64_t *n_selected, void *stream) {
+    PA_CHECK(idx && reads && params && spec && n_selected, PA_EINVAL, "NULL argument");
+    PA_TRY(check_extract_spec(spec));
+    pa::DevParams dp;
+    PA_TRY(begin_align(idx, reads, params, stream, &dp));
+    return pa::reads_select(const_cast<pa_index *>(idx), reads, dp, spec, selected, n_selected, as_stream(stream));
+}
+
+pa_status pa_extract_fastq_file(const pa_index *idx, const char *path, const pa_params *params,
+                                const pa_extract_spec *spec, int32_t out_fd, uint64_t read_index_base,
+                                pa_result *acc, int32_t threads, uint64_t window_bytes, void *stream,
+                                pa_extract_stats *stats) {
+    PA_CHECK(idx && path && params && spec && stats, PA_EINVAL, "NULL argument");
+    *stats = pa_extract_stats{};
+    PA_TRY(check_index(idx));
+    if (acc) PA_TRY(check_result(idx, acc));
+    PA_TRY(check_extract_spec(spec));
+    PA_CHECK(out_fd >= 0, PA_EINVAL, "bad file descriptor");
+    pa::DevParams dp;
+    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    PA_HIP(hipSetDevice(idx->device));
+    return pa::align_fastq_file(const_cast<pa_index *>(idx), path, dp, read_index_base, acc, threads > 0 ? threads : 8,
+                                window_bytes ? window_bytes : (128ull << 20), as_stream(stream), nullptr, 0, ~0ull,
+                                nullptr, spec, out_fd, stats);
 }
 
 pa_status pa_idsets_disjoint(const pa_idset *const *sets, uint32_t n_sets, int32_t device, int32_t *disjoint) {

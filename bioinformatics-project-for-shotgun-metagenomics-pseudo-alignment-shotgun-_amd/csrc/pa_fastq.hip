@@ -431,7 +431,7 @@ struct WindowOut {
 // its bytes (a second one).
 pa_status parse_align_window(ParseBufs &B, const uint8_t *D, uint64_t lo, uint64_t hi, bool last, pa_index *idx,
                              const DevParams &prm, uint64_t base, pa_result *acc, hipStream_t st, WindowOut &out,
-                             double *t_meta, double *t_rec) {
+                             double *t_meta, double *t_rec, Extract *ex = nullptr) {
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
         return std::chrono::duration<double, std::milli>(b - a).count();
@@ -441,6 +441,7 @@ pa_status parse_align_window(ParseBufs &B, const uint8_t *D, uint64_t lo, uint64
     const uint64_t t0 = lo & ~15ull;
     const uint64_t ntiles = (hi - t0 + kTile - 1) / kTile;
     const unsigned sgrid = (unsigned)((ntiles + kScanBlock - 1) / kScanBlock);
+    if (ex && ex->timing) PA_HIP(hipEventRecord(ex->ev[5], st));
     PA_HIP(hipMemsetAsync(B.meta, 0, offsetof(Meta, max_len), st));
     hipLaunchKernelGGL(k_nl_count, dim3((unsigned)ntiles), dim3(256), 0, st, D, t0, lo, hi, B.tile_cnt);
     hipLaunchKernelGGL(k_scan_sums, dim3(sgrid), dim3(256), 0, st, B.tile_cnt, ntiles, B.bsum);
@@ -470,6 +471,8 @@ pa_status parse_align_window(ParseBufs &B, const uint8_t *D, uint64_t lo, uint64
                        B.meta, B.tile_off, B.nl, B.rec_off, B.seq, B.qual, B.meta);
     PA_HIP(hipGetLastError());
     PA_HIP(hipMemcpyAsync(B.h_meta, B.meta, sizeof(Meta), hipMemcpyDeviceToHost, st));
+    unsigned long long n_bases = 0;  // (the length scan's total; only the extraction asks for it)
+    if (ex) PA_HIP(hipMemcpyAsync(&n_bases, B.tot, 8, hipMemcpyDeviceToHost, st));
     tw = now();
     PA_HIP(hipStreamSynchronize(st));
     *t_rec += ms(tw, now());
@@ -480,14 +483,16 @@ pa_status parse_align_window(ParseBufs &B, const uint8_t *D, uint64_t lo, uint64
     pa_reads r{};
     r.device = idx->device;
     r.n = R;
-    r.n_bases = 0;  // (not read by the align path)
+    r.n_bases = n_bases;  // (not read by the align path; the assign pass gets the real count)
     r.max_len = (uint32_t)B.h_meta->max_len;
     r.seq = B.seq;
     r.qual = B.qual;
     r.off = (uint64_t *)B.rec_off;
     r.q_min = 255 - (int32_t)B.h_meta->q_low;  // (over the file so far: <= this window's smallest byte)
     r.len_min = 1;                              // (the grammar: a non-empty sequence)
-    PA_TRY(align(idx, &r, prm, base, acc, st));
+    if (acc) PA_TRY(align(idx, &r, prm, base, acc, st));
+    // the selected records of the window, classified, gathered and written (pa_extract.hip)
+    if (ex) PA_TRY(extract_window(*ex, idx, &r, prm, D, t0, lo, hi, B.nl, st));
     out.records = R;
     return PA_OK;
 }
@@ -820,8 +825,9 @@ pa_status align_fastq_prefetched(pa_index *idx, pa_fastq_prefetch *pf, const Dev
 }
 pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm, uint64_t base, pa_result *acc,
                            int threads, uint64_t window, hipStream_t st, uint64_t *n_reads, uint64_t offset,
-                           uint64_t length, std::vector<uint64_t> *ids_out) {
-    ErrOp op("pa_align_fastq_file");
+                           uint64_t length, std::vector<uint64_t> *ids_out, const pa_extract_spec *extract, int out_fd,
+                           pa_extract_stats *extract_stats) {
+    ErrOp op(extract ? "pa_extract_fastq_file" : "pa_align_fastq_file");
     // PA_STREAM_TIMING=1: where the time goes (stderr)
     const bool timing = pa::env_is("PA_STREAM_TIMING", '1');
     auto now = [] { return std::chrono::steady_clock::now(); };
@@ -862,6 +868,7 @@ pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm
 
     uint8_t *H[2] = {nullptr, nullptr}, *D[2] = {nullptr, nullptr};
     ParseBufs B;
+    Extract ex;
     hipStream_t cs = nullptr;
     hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_carry[2] = {nullptr, nullptr};
     std::thread reader;
@@ -877,6 +884,7 @@ pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm
             if (ev_carry[i]) hipEventDestroy(ev_carry[i]);
         }
         B.release();
+        extract_close(ex);
         if (cs) hipStreamDestroy(cs);
         if (src.gz) pa::gz_close(src.gz);
         if (src.fd >= 0) close(src.fd);
@@ -902,6 +910,7 @@ pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm
         PA_HIP(hipEventCreateWithFlags(&ev_carry[i], hipEventDisableTiming));
     }
     PA_HIP(B.alloc(kCarryMax + W, est_rec, st));
+    if (extract) PA_TRY(extract_open(ex, idx, extract, out_fd, kCarryMax + W, extract_stats, st));
     PA_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
     t_alloc = ms(t_start, now());
     // the index's align-side view and the align queues, while window 0 is read
@@ -940,7 +949,7 @@ pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm
         if (hi == lo) break;  // (an empty last window: nothing after the previous records)
         WindowOut w;
         rc = parse_align_window(B, D[cur], lo, hi, last, idx, prm, base + records, acc, st, w, &t_wait_meta,
-                                &t_wait_rec);
+                                &t_wait_rec, extract ? &ex : nullptr);
         if (rc != PA_OK) break;
         // (a record longer than the carry limit is left to the host parser too)
         if (w.fail || (!last && hi - w.end > kCarryMax)) {

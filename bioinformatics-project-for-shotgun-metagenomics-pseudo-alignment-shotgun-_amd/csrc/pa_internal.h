@@ -597,10 +597,35 @@ pa_status ensure_workspace(pa_index *idx, size_t bytes);
 pa_status reserve_queues(pa_index *idx, uint64_t n);  // align queues for batches of up to n reads
 pa_status ensure_qmask(pa_index *idx, uint64_t n);    // quality-filter masks for batches of up to n reads
 // offset / length: a byte range of a plain file, cut on record boundaries
-// (pa_align_fastq_range); ids_out: the range's id hashes
+// (pa_align_fastq_range); ids_out: the range's id hashes; extract: the selected records
+// written to out_fd (pa_extract_fastq_file: acc may then be null)
 pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm, uint64_t base, pa_result *acc,
                            int threads, uint64_t window, hipStream_t st, uint64_t *n_reads, uint64_t offset = 0,
-                           uint64_t length = ~0ull, std::vector<uint64_t> *ids_out = nullptr);
+                           uint64_t length = ~0ull, std::vector<uint64_t> *ids_out = nullptr,
+                           const pa_extract_spec *extract = nullptr, int out_fd = -1,
+                           pa_extract_stats *extract_stats = nullptr);
+// read extraction (pa_extract.hip): the state of one
+// pa_extract_fastq_file call -- the selection on the device, the output buffer
+// of a window (device and pinned, span + 16 bytes each) and the statistics.
+struct Extract {
+    uint32_t type_mask = 0, invert = 0;
+    uint8_t *keep = nullptr;               // device [n_genomes] genome_keep, or null
+    unsigned long long *by_type = nullptr; // device [4] selected records per type, over the file
+    uint8_t *d_out = nullptr, *h_out = nullptr;
+    uint64_t cap = 0;
+    int fd = -1;
+    pa_extract_stats *stats = nullptr;
+    bool timing = false;                   // PA_STREAM_TIMING=1: the per-window split on stderr
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // ev[5]: the window's start
+};
+bool extract_mask_ok(uint32_t type_mask);
+pa_status extract_open(Extract &x, const pa_index *idx, const pa_extract_spec *spec, int fd, uint64_t span,
+                       pa_extract_stats *stats, hipStream_t st);
+void extract_close(Extract &x);
+pa_status extract_window(Extract &x, pa_index *idx, const pa_reads *r, const DevParams &prm, const uint8_t *D,
+                         uint64_t t0, uint64_t lo, uint64_t hi, const uint32_t *nl, hipStream_t st);
+pa_status reads_select(pa_index *idx, const pa_reads *r, const DevParams &prm, const pa_extract_spec *spec,
+                       uint8_t *selected, uint64_t *n_selected, hipStream_t st);
 pa_status idsets_disjoint(const std::vector<const std::vector<uint64_t> *> &sets, int device, bool *disjoint);
 pa_status fastq_prefetch_start(const char *path, int device, int threads, uint64_t window, pa_fastq_prefetch **out);
 void fastq_prefetch_free(pa_fastq_prefetch *pf);

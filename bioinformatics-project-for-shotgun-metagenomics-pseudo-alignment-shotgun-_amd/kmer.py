@@ -649,6 +649,25 @@ class _FileBatch(_Batch):
             self.ids, self.seq, self.qual, self.off = _columnar(FASTAQFile(self.path).container)
 
 
+EXTRACT_MAPPING_WORDS = {"filtered": 0, "unmapped": 1, "unique": 2, "ambiguous": 3}  # (word -> PA_* type value)
+
+
+def extract_type_mask(mapping) -> int:
+    """The pa_extract_spec type_mask of a selection given as --assignments'
+    words: a comma-separated string (--extract-mapping) or a sequence of words.
+    ValueError for an empty list, an empty word or an unknown one."""
+    words = mapping.split(",") if isinstance(mapping, str) else list(mapping)
+    if not words:
+        raise ValueError("The extract mapping list is empty (choose from unique, ambiguous, unmapped, filtered)")
+    mask = 0
+    for w in words:
+        w = w.strip() if isinstance(w, str) else w
+        if w not in EXTRACT_MAPPING_WORDS:
+            raise ValueError(f"Unknown extract mapping {w!r} (choose from unique, ambiguous, unmapped, filtered)")
+        mask |= 1 << EXTRACT_MAPPING_WORDS[w]
+    return mask
+
+
 def _dropped_mask(qual: np.ndarray, off: np.ndarray, mrq) -> np.ndarray:
     """Read.mean_quality() < min_read_quality per read (src/kmer.py:394-399, 587),
     raw ASCII: an exact integer test for an int threshold, the reference's own
@@ -928,11 +947,97 @@ class PseudoAlignment:
             self.align_reads_from_container(FASTAQFile(reads_file).container, m, p, min_read_quality,
                                             min_kmer_quality, max_genomes)
             return
-        if min_read_quality is not None:
+        self._adopt_streamed(result, reads_file, prm, n, min_read_quality, min_kmer_quality, max_genomes)
+
+    def extract_reads_from_file(self, reads_file: str, out_file: str, mapping: Sequence[str] = ("unique", "ambiguous"),
+                                genomes: Optional[Sequence[str]] = None, invert: bool = False, m: int = 1, p: int = 1,
+                                min_read_quality: Optional[int] = None, min_kmer_quality: Optional[int] = None,
+                                max_genomes: Optional[int] = None, *, host_parsed: bool = False) -> Dict[str, Any]:
+        """align_reads_from_file, with the selected reads written to ``out_file``
+        as FASTQ records in file order.  ``mapping``: the
+        read types to select, of "unique", "ambiguous", "unmapped" and
+        "filtered"; ``genomes``: identifiers that restrict the mapped reads to
+        those whose genomes_mapped_to holds one of them (None: no
+        restriction); ``invert``: everything else instead.  Returns the
+        statistics (records, selected, bytes, selected_by_type).  The records
+        are gathered on the device from the device-parsed file where
+        align_reads_from_file would stream it; otherwise, and for a file
+        outside that subset of the grammar, the exact parser's records are
+        selected by N.reads_select and written by the host (``host_parsed``:
+        at once, for a job that needs the host-parsed records anyway)."""
+        from data_file import FASTAQFile
+        type_mask = extract_type_mask(mapping)
+        ref = self.kmer_reference
+        keep = None
+        if genomes is not None:
+            names = [g.identifier for g in ref.genomes]
+            unknown = [x for x in genomes if x not in set(names)]
+            if unknown:
+                raise ValueError(f"unknown genome identifier: {unknown[0]}")
+            wanted = set(genomes)
+            keep = np.fromiter((name in wanted for name in names), dtype=np.uint8, count=len(names))
+        spec = N.ExtractSpec.make(type_mask, keep, invert)
+        fresh = (not self._batches and not self._host and self._result is None and self not in _COVERAGE
+                 and self not in _PILEUP and self not in _ABUNDANCE and self not in _LINEAGE)
+        err = _check_align_args(ref, m, p, min_read_quality, min_kmer_quality, max_genomes)
+        with open(out_file, "wb") as fh:
+            if fresh and err is None and not host_parsed and os.environ.get("PA_STREAM", "1") != "0":
+                FASTAQFile.check_extension(reads_file)
+                result = N.Result(ref.index)
+                prm = N.Params.make(m, p, min_read_quality, min_kmer_quality, max_genomes)
+                n, stats = N.extract_fastq_file(ref.index, reads_file, prm, spec, fh.fileno(), self._next_index, result)
+                if n is not None:
+                    self._adopt_streamed(result, reads_file, prm, n, min_read_quality, min_kmer_quality, max_genomes)
+                    return stats
+                result.close()
+                fh.truncate(0)  # (a late window refused: what the earlier ones wrote goes)
+                fh.seek(0)
+            # the exact path: a parse error leaves the (truncated) file empty
+            container = FASTAQFile(reads_file).container
+            self.align_reads_from_container(container, m, p, min_read_quality, min_kmer_quality, max_genomes)
+            ids, seq, qual, off = _columnar(container)
+            n = len(ids)
+            batch = self._batches[-1] if n else None
+            if n == 0:
+                sel = np.zeros(0, dtype=bool)
+                types = np.zeros(0, dtype=np.uint8)
+            elif batch.all_dropped:  # (no device pass was made: every read is PA_DROPPED)
+                types = np.zeros(n, dtype=np.uint8)
+                sel = np.full(n, bool(type_mask & 1) != bool(invert))
+            else:
+                reads = N.Reads.upload(seq, qual, off, device=ref.index.device)
+                try:
+                    sel = N.reads_select(ref.index, reads, batch.params, spec)
+                    types = None
+                    if sel.any():  # (the statistics' types: the batch's own per-read results)
+                        types, _, _, _, _ = N.align_reads(ref.index, reads, batch.params)
+                finally:
+                    reads.close()
+            stats = {"records": n, "selected": int(sel.sum()), "bytes": 0,
+                     "selected_by_type": {name: 0 for name in N.EXTRACT_TYPE_NAMES}}
+            off = np.asarray(off, dtype=np.int64)
+            chunks: List[bytes] = []
+            held = 0
+            for i in np.flatnonzero(sel):
+                a, b = int(off[i]), int(off[i + 1])
+                rec = b"@" + ids[i].encode("utf-8") + b"\n" + seq[a:b].tobytes() + b"\n+\n" + qual[a:b].tobytes() + b"\n"
+                chunks.append(rec)
+                held += len(rec)
+                stats["bytes"] += len(rec)
+                stats["selected_by_type"][N.EXTRACT_TYPE_NAMES[int(types[i])]] += 1
+                if held >= (8 << 20):
+                    fh.write(b"".join(chunks))
+                    chunks, held = [], 0
+            fh.write(b"".join(chunks))
+        return stats
+
+    def _adopt_streamed(self, result, reads_file, prm, n, mrq, mkq, mg) -> None:
+        """The bookkeeping of a file the device-parsed stream aligned into ``result``."""
+        if mrq is not None:
             self.filter_read_quality_flag = True
-        if min_kmer_quality is not None:
+        if mkq is not None:
             self.filter_kmer_quality_flag = True
-        if max_genomes is not None:
+        if mg is not None:
             self.filter_max_genomes_flag = True
         self._result = result
         stats, _, _, _ = result.fetch()
@@ -940,7 +1045,7 @@ class PseudoAlignment:
         self.filtered_quality_reads += int(stats[3])
         self.filtered_quality_kmers += int(stats[4])
         self.filtered_hr_kmers += int(stats[5])
-        self._batches.append(_FileBatch(self._next_index, reads_file, prm, min_read_quality, n))
+        self._batches.append(_FileBatch(self._next_index, reads_file, prm, mrq, n))
         self._next_index += n
         self._streamed_records = n  # (diagnostics: the device-parsed path was taken)
 

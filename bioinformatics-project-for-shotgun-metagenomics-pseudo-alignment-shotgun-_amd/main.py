@@ -11,6 +11,7 @@
                     [--abundance FILE [--abundance-iterations N] [--abundance-tolerance X]
                      [--abundance-bootstraps B [--abundance-seed S] [--abundance-confidence X]]]
                     [--lineages FILE [--lineage-report FILE]]
+                    [--extract FILE [--extract-mapping LIST] [--extract-genomes a,b] [--extract-invert]]
 
 Same tasks (reference | dumpref | align | dumpalign), flags, flag-combination
 checks, default coercions and error exits as src/main.py:61-402:
@@ -112,6 +113,19 @@ def _has_lineage_flag(argv: List[str]) -> bool:
     return False
 
 
+_EXTRACT_FLAGS = ("--extract", "--extract-mapping", "--extract-genomes", "--extract-invert")
+
+
+def _has_extract_flag(argv: List[str]) -> bool:
+    """An --extract* flag on the command line, in any spelling argparse accepts
+    (as _has_coverage_flag)."""
+    for a in argv:
+        name = a.split("=", 1)[0]
+        if len(name) > 2 and name.startswith("--") and any(f.startswith(name) for f in _EXTRACT_FLAGS):
+            return True
+    return False
+
+
 def _has_reads2_flag(argv: List[str]) -> bool:
     """--reads2 on the command line (`--reads2 X`, `--reads2=X`)."""
     return any(a.split("=", 1)[0] == "--reads2" for a in argv)
@@ -153,6 +167,8 @@ def _early_reads_path(argv: List[str]) -> Optional[str]:
     if _has_abundance_flag(argv):  # (and an abundance job: the candidate pass needs the read columns)
         return None
     if _has_lineage_flag(argv):  # (and a lineage job, as an abundance job)
+        return None
+    if _has_extract_flag(argv):  # (an extract job streams the file in windows itself, records gathered per window)
         return None
     if _has_reads2_flag(argv):  # (and a paired job: both files are parsed on the host)
         return None
@@ -206,7 +222,8 @@ if __name__ == "__main__":  # the HIP runtime starts on a native thread while th
 
 from constants import DEFAULT_AMBIGUOUS_THRESHOLD, DEFAULT_SIMILARITY_THRESHOLD, DEFAULT_UNIQUE_THRESHOLD
 from data_file import FASTAFile, FASTAQFile, InvalidExtensionError, NoRecordsInDataFile
-from kmer import AddingExistingRead, KmerReference, NotValidatingUniqueMapping, PseudoAlignment
+from kmer import (AddingExistingRead, KmerReference, NotValidatingUniqueMapping, PseudoAlignment,
+                  extract_type_mask)
 
 _TIMING = os.environ.get("PA_CLI_TIMING") == "1"  # stage times on stderr (diagnostic)
 
@@ -288,6 +305,15 @@ def parse_arguments(args: Optional[List[str]] = None) -> argparse.Namespace:
                         help="the genomes' lineages, one line per genome: identifier<TAB>name;name;... (root first)")
     parser.add_argument("--lineage-report", default=None, metavar="FILE",
                         help="write one line per node of the lineage tree (reads in the clade, on the node) to FILE")
+    # not in the reference: the selected reads written back out as FASTQ, dumpalign with --reads
+    parser.add_argument("--extract", default=None, metavar="FILE",
+                        help="write the selected reads' FASTQ records to FILE, in file order")
+    parser.add_argument("--extract-mapping", default=None, metavar="LIST",
+                        help="read types to select, a comma list of unique, ambiguous, unmapped, filtered "
+                             "(default: unique,ambiguous)")
+    parser.add_argument("--extract-genomes", default=None,
+                        help="comma-separated genome identifiers: select only mapped reads that name one of them")
+    parser.add_argument("--extract-invert", action="store_true", help="select every read the selection leaves out")
     return parser.parse_args(args)
 
 
@@ -364,7 +390,7 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
                                     prefetch=None, per_read: bool = False,
                                     coverage: bool = False, assignments: bool = False,
                                     pileup: bool = False, min_base_quality=None,
-                                    abundance: bool = False, lineages=None) -> PseudoAlignment:
+                                    abundance: bool = False, lineages=None, extract=None) -> PseudoAlignment:
     # the FASTQ file goes straight to the device (parsed there, aligned in
     # windows); a file outside that subset of the grammar is parsed the exact
     # way (FASTAQFile), which also raises the reference's errors.  per_read
@@ -386,8 +412,17 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
             alignment._lineage_tree()
         except ValueError as err:
             sys.exit(f"Error: {err} in lineage file.")
+    # extract: (out_file, mapping, genomes, invert) -- the selected records gathered on the device from the
+    # device-parsed stream; with a per-read job above (or --assignments) the host-parsed records are selected
+    if extract is not None:
+        out_file, mapping, genomes, invert = extract
+        stats = alignment.extract_reads_from_file(reads_file, out_file, mapping, genomes, invert, m, p,
+                                                  min_read_quality, min_kmer_quality, max_genomes,
+                                                  host_parsed=per_read or assignments)
+        if _TIMING:
+            print(f"[pa_cli] extract: {stats}", file=sys.stderr, flush=True)
     # assignments: the host parse too -- every read's line needs its id and the read columns
-    if per_read or assignments:
+    elif per_read or assignments:
         alignment.align_reads_from_container(FASTAQFile(reads_file).container, m, p, min_read_quality,
                                              min_kmer_quality, max_genomes)
     else:
@@ -424,6 +459,15 @@ def _load_lineages(args: argparse.Namespace):
         except ValueError as err:
             sys.exit(f"Error: {err}")
     return args._lineages
+
+
+def _extract_job(args: argparse.Namespace):
+    """(out_file, mapping, genomes, invert) of --extract; None without the flag."""
+    if args.extract is None:
+        return None
+    genomes = None if args.extract_genomes is None else [x for x in args.extract_genomes.split(",") if x]
+    return (args.extract, "unique,ambiguous" if args.extract_mapping is None else args.extract_mapping, genomes,
+            args.extract_invert)
 
 
 def _print_json(obj) -> None:
@@ -517,6 +561,24 @@ def _check_task(args: argparse.Namespace) -> None:
         validate_file_readable(args.lineages, "Lineages")
         if args.lineage_report is not None:
             validate_file_writable(args.lineage_report, "Lineage report output")
+    if args.extract is None and (args.extract_mapping is not None or args.extract_genomes is not None
+                                 or args.extract_invert):
+        sys.exit("Error: --extract-mapping, --extract-genomes and --extract-invert need --extract.")
+    if args.extract is not None:
+        try:
+            extract_type_mask("unique,ambiguous" if args.extract_mapping is None else args.extract_mapping)
+        except ValueError as err:
+            sys.exit(f"Error: {err}.")
+        if args.task != "dumpalign" or not args.reads:
+            sys.exit("Error: --extract is only allowed for task 'dumpalign' with --reads.")
+        if args.reads2 is not None:
+            sys.exit("Error: --extract cannot be combined with --reads2 (pairs are not extracted).")
+        if args.alignfile:
+            sys.exit("Error: --extract cannot be combined with -a.")
+        if os.path.exists(args.extract) and os.path.samefile(args.extract, args.reads) or (
+                os.path.abspath(args.extract) == os.path.abspath(args.reads)):
+            sys.exit("Error: --extract FILE is the --reads file.")
+        validate_file_writable(args.extract, "Extract output")
     if args.task == "reference":
         if extra:
             sys.exit("Error: For task 'reference', only -g, -k, -r, --filter-similar, and --similarity-threshold "
@@ -644,7 +706,7 @@ def _run(args: argparse.Namespace) -> None:
                 return
             host_parsed = (args.coverage or args.assignments is not None or args.variants is not None
                            or args.abundance is not None or args.lineages is not None)
-            pf = None if host_parsed else _prefetch_reads(args.reads)
+            pf = None if host_parsed or args.extract is not None else _prefetch_reads(args.reads)
             ref = _load_reference(args.referencefile)
             _check_strands(args, ref)
             _print_alignment(create_alignment_from_reference(ref, args.reads, *filt, prefetch=pf,
@@ -653,7 +715,8 @@ def _run(args: argparse.Namespace) -> None:
                                                              pileup=args.variants is not None,
                                                              min_base_quality=args.variant_min_base_quality,
                                                              abundance=args.abundance is not None,
-                                                             lineages=_load_lineages(args)), args)
+                                                             lineages=_load_lineages(args),
+                                                             extract=_extract_job(args)), args)
         elif args.genomefile and args.kmer_size and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
             validate_file_readable(args.genomefile, "Genome FASTA")
@@ -669,11 +732,12 @@ def _run(args: argparse.Namespace) -> None:
             # abundance job, as coverage)
             host_parsed = (args.coverage or args.assignments is not None or args.variants is not None
                            or args.abundance is not None or args.lineages is not None)
-            sharded = None if host_parsed else _dumpalign_sharded(args, filt)
+            # (an extract job too: its output is written by one device, window after window)
+            sharded = None if host_parsed or args.extract is not None else _dumpalign_sharded(args, filt)
             if sharded is not None:
                 _print_json(sharded.get_summary())
                 return
-            pf = None if host_parsed else _prefetch_reads(args.reads)
+            pf = None if host_parsed or args.extract is not None else _prefetch_reads(args.reads)
             ref = create_reference(args.genomefile, args.kmer_size, args.filter_similar, args.similarity_threshold,
                                    reads_file=args.reads, both_strands=args.both_strands)
             _print_alignment(create_alignment_from_reference(ref, args.reads, *filt, prefetch=pf,
@@ -682,7 +746,8 @@ def _run(args: argparse.Namespace) -> None:
                                                              pileup=args.variants is not None,
                                                              min_base_quality=args.variant_min_base_quality,
                                                              abundance=args.abundance is not None,
-                                                             lineages=_load_lineages(args)), args)
+                                                             lineages=_load_lineages(args),
+                                                             extract=_extract_job(args)), args)
         elif args.alignfile:
             validate_file_readable(args.alignfile, "Alignment output")
             try:

@@ -35,6 +35,8 @@ PA_READS_UNKNOWN = 2 ** 64 - 1
 PA_NB_READS_PER_KBASE = 2500  # (include/pa.h: the neighbour bits' break-even, reads per 1000 genome bases)
 PA_NB_READS_PER_KBASE_2W, PA_NB_READS_PER_KBASE_3W = 10000, 18000  # (two- / three-word keys)
 NO_NODE = 0xFFFFFFFF  # PA_NO_NODE: a read no node of the lineage tree holds
+PA_EXTRACT_INVERT = 1
+EXTRACT_TYPE_NAMES = ("filtered", "unmapped", "unique", "ambiguous")  # (--assignments' words, by PA_* type value)
 LINEAGE_LDS_NODES = 4096  # PA_LINEAGE_LDS_NODES (include/pa.h: the largest tree counted through the LDS histogram)
 
 # every symbol declared in include/pa.h
@@ -48,7 +50,7 @@ EXPORTS = (
     "pa_result_create", "pa_result_reset", "pa_result_fetch", "pa_result_device_view", "pa_result_copy_out",
     "pa_result_copy_in", "pa_result_load", "pa_result_free",
     "pa_align", "pa_align_detail", "pa_align_reads", "pa_align_pairs", "pa_align_batch", "pa_align_fastq_file", "pa_align_fastq_range",
-    "pa_idsets_disjoint", "pa_idset_free",
+    "pa_idsets_disjoint", "pa_idset_free", "pa_reads_select", "pa_extract_fastq_file",
     "pa_fastq_prefetch_start", "pa_align_fastq_prefetched", "pa_fastq_prefetch_free",
     "pa_comm_unique_id", "pa_comm_init", "pa_comm_free", "pa_comm_count", "pa_counters_reduce",
     "pa_index_prepare_coverage", "pa_coverage_create", "pa_coverage_reset", "pa_coverage_add", "pa_coverage_summary",
@@ -109,6 +111,27 @@ class AbundanceInfo(ctypes.Structure):
 class LineageInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("reads_unique", "reads_ambiguous", "reads_unmapped", "reads_dropped")] \
         + [("n_nodes", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class ExtractSpec(ctypes.Structure):
+    """pa_extract_spec; ``make`` keeps the genome_keep array alive with the structure."""
+    _fields_ = [("type_mask", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("genome_keep", ctypes.c_void_p)]
+
+    @classmethod
+    def make(cls, type_mask: int, genome_keep=None, invert: bool = False) -> "ExtractSpec":
+        keep = None if genome_keep is None else np.ascontiguousarray(genome_keep, dtype=np.uint8)
+        spec = cls(int(type_mask), PA_EXTRACT_INVERT if invert else 0, None if keep is None else keep.ctypes.data)
+        spec._keep = keep
+        return spec
+
+
+class ExtractStats(ctypes.Structure):
+    _fields_ = [("records", ctypes.c_uint64), ("selected", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
+                ("selected_by_type", ctypes.c_uint64 * 4)]
+
+    def as_dict(self) -> dict:
+        return {"records": int(self.records), "selected": int(self.selected), "bytes": int(self.bytes),
+                "selected_by_type": {n: int(self.selected_by_type[i]) for i, n in enumerate(EXTRACT_TYPE_NAMES)}}
 
 
 # pa_variant, one record of Pileup.variants (40 bytes, no implicit padding)
@@ -183,6 +206,10 @@ def lib():
                                       ctypes.POINTER(U64)]),
         "pa_align_fastq_range": (I32, [P, ctypes.c_char_p, U64, U64, ctypes.POINTER(Params), U64, P, I32, U64, P,
                                        ctypes.POINTER(U64), PP]),
+        "pa_reads_select": (I32, [P, P, ctypes.POINTER(Params), ctypes.POINTER(ExtractSpec), P, ctypes.POINTER(U64),
+                                  P]),
+        "pa_extract_fastq_file": (I32, [P, ctypes.c_char_p, ctypes.POINTER(Params), ctypes.POINTER(ExtractSpec), I32,
+                                        U64, P, I32, U64, P, ctypes.POINTER(ExtractStats)]),
         "pa_idsets_disjoint": (I32, [ctypes.POINTER(P), U32, I32, ctypes.POINTER(I32)]),
         "pa_idset_free": (None, [P]),
         "pa_fastq_prefetch_start": (I32, [ctypes.c_char_p, I32, I32, U64, PP]),
@@ -848,6 +875,37 @@ def align_fastq_file(index: Index, path: str, params: Params, read_index_base: i
         return None
     _check(st)
     return int(n.value)
+
+
+def reads_select(index: Index, reads: Reads, params: Params, spec: ExtractSpec, stream=None) -> np.ndarray:
+    """pa_reads_select: sel(r) of every read of an uploaded batch (bool array)."""
+    flags = np.zeros(reads.n, dtype=np.uint8)
+    count = U64(0)
+    _check(lib().pa_reads_select(index.handle, reads.handle, ctypes.byref(params), ctypes.byref(spec), _ptr(flags),
+                                 ctypes.byref(count), _stream(stream)))
+    return flags.astype(bool)
+
+
+def extract_fastq_file(index: Index, path: str, params: Params, spec: ExtractSpec, out_fd: int,
+                       read_index_base: int = 0, result: Optional[Result] = None, threads: Optional[int] = None,
+                       window_bytes: int = 0, stream=None) -> Tuple[Optional[int], dict]:
+    """pa_extract_fastq_file: the selected records of the device-parsed file
+    written to ``out_fd``.  Returns (records, statistics); records is None when
+    the file is outside the device-parsed subset of the grammar -- the
+    statistics then say how many bytes were already written (truncate the
+    output, reset ``result`` and take the exact path)."""
+    stats = ExtractStats()
+    if window_bytes <= 0:
+        env = os.environ.get("PA_STREAM_WINDOW")
+        window_bytes = int(env) if env and env.isdigit() else 0
+    st = lib().pa_extract_fastq_file(index.handle, os.fsencode(path), ctypes.byref(params), ctypes.byref(spec),
+                                     int(out_fd), int(read_index_base), None if result is None else result.handle,
+                                     int(threads or ingest_threads()), int(window_bytes), _stream(stream),
+                                     ctypes.byref(stats))
+    if st == PA_ENOTCANON:
+        return None, stats.as_dict()
+    _check(st)
+    return int(stats.records), stats.as_dict()
 
 
 class IdSet:

@@ -54,6 +54,9 @@
  *   pa_idsets_disjoint       the dumpalign job read-sharded over N GPUs     src/main.py:289-310
  *   pa_fastq_prefetch_start  the same with the file moved to the device in the
  *   pa_align_fastq_prefetched  background (overlaps the index build)       src/main.py:286-310
+ *   pa_extract_fastq_file    the same stream with the selected records written back out as FASTQ
+ *   pa_reads_select          (--extract: host depletion, the reads of one genome, the unmapped reads);
+ *                            no reference counterpart: the definition is DESIGN.md section 20
  *   pa_counters_reduce       the multi-GPU sum/min of PseudoAlignment counters
  *                            (read shards of one job); the
  *                            reference is single-process, so this has no
@@ -680,6 +683,49 @@ pa_status pa_align_fastq_range(const pa_index *idx, const char *path, uint64_t o
  * which decides and raises the reference's error).  Checked on `device`. */
 pa_status pa_idsets_disjoint(const pa_idset *const *sets, uint32_t n_sets, int32_t device, int32_t *disjoint);
 void pa_idset_free(pa_idset *ids);
+
+/* Read extraction.  Reads are classified exactly as
+ * pa_align_detail classifies them with the same params.  A selection is
+ * (type_mask, genome_keep, flags):
+ *   type_mask    bits 1u << PA_DROPPED .. 1u << PA_AMBIGUOUSLY_MAPPED; zero or any other bit: PA_EINVAL
+ *   genome_keep  NULL, or n_genomes host bytes; restricts MAPPED reads only: a unique or ambiguous
+ *                read passes iff its genomes_mapped_to list holds a genome g with genome_keep[g] != 0
+ *                (an ambiguous read with an empty list never passes a non-NULL genome_keep); dropped
+ *                and unmapped reads are not affected by it
+ *   sel(r) = (type_mask has type(r)) && (r is dropped or unmapped, or genome_keep == NULL, or r's list
+ *            meets genome_keep), negated when flags & PA_EXTRACT_INVERT. */
+#define PA_EXTRACT_INVERT 1u
+typedef struct {
+    uint32_t type_mask, flags;
+    const uint8_t *genome_keep; /* n_genomes bytes or NULL */
+} pa_extract_spec;
+typedef struct {
+    uint64_t records, selected, bytes, selected_by_type[4];
+} pa_extract_stats;
+
+/* sel(r) for an uploaded batch: selected[n] host bytes (0 / 1; nullable) and
+ * *n_selected.  The kernel-level handle of the selection and the worker of a
+ * host-parsed extraction. */
+pa_status pa_reads_select(const pa_index *idx, const pa_reads *reads, const pa_params *params,
+                          const pa_extract_spec *spec, uint8_t *selected, uint64_t *n_selected, void *stream);
+
+/* pa_align_fastq_file's stream (plain and ".gz"), with the selected records
+ * written to out_fd in file order, each as its four lines ending in a line
+ * feed ("@" + id, sequence, "+", qualities): for a file inside the
+ * device-parsed subset a copy of the record's own bytes, a last record without
+ * a final line feed given one.  Per window the device classifies the reads
+ * (the assign pass), selects, scans the lengths and gathers the bytes; one
+ * copy to pinned memory and one write follow, in window order.  acc
+ * (nullable): the counter pass runs on every window as in pa_align_fastq_file.
+ * stats: records seen, records selected, bytes written, selected records per
+ * type.  PA_ENOTCANON as pa_align_fastq_file gives it, possibly at a late
+ * window: the bytes already written stay written and stats->bytes counts them
+ * -- truncate the file, reset acc and take the exact path.  PA_EIO: a failed
+ * or short write.  PA_EINVAL: a NULL argument or a bad mask.  One device. */
+pa_status pa_extract_fastq_file(const pa_index *idx, const char *path, const pa_params *params,
+                                const pa_extract_spec *spec, int32_t out_fd, uint64_t read_index_base,
+                                pa_result *acc /* nullable */, int32_t threads, uint64_t window_bytes,
+                                void *stream, pa_extract_stats *stats);
 
 /* The same as one device-resident step: pa_fastq_prefetch_start begins moving
  * the (plain, not gzip) FASTQ file into device memory on a background thread
