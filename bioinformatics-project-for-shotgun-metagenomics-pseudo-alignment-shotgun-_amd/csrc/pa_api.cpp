@@ -1069,6 +1069,68 @@ void pa_lineage_free(pa_lineage *l) {
     pa::lineage_free(l);
 }
 
+// ---- containment (csrc/pa_contain.hip) ------------------------------------------------------
+
+pa_status pa_containment_create(const pa_index *idx, pa_containment **out) {
+    PA_CHECK(out != nullptr, PA_EINVAL, "NULL argument");
+    *out = nullptr;
+    PA_TRY(check_index(idx));
+    PA_HIP(hipSetDevice(idx->device));
+    return pa::containment_create(idx, out);
+}
+
+pa_status pa_containment_reset(pa_containment *c, void *stream) {
+    PA_CHECK(c != nullptr, PA_EINVAL, "NULL argument");
+    PA_HIP(hipSetDevice(c->device));
+    pa::ErrOp op("pa_containment_reset");
+    return pa::containment_reset(c, as_stream(stream));
+}
+
+// (no prepare_pass: the mark kernel reads the table and the classes, so a deferred index stays deferred)
+pa_status pa_containment_add(const pa_index *idx, const pa_reads *reads, const pa_params *params,
+                             pa_containment *acc, void *stream) {
+    PA_CHECK(acc != nullptr, PA_EINVAL, "NULL argument");
+    PA_TRY(check_batch(idx, reads));
+    PA_TRY(check_acc(acc, idx, "pa_containment"));
+    pa::DevParams dp;
+    PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    PA_HIP(hipSetDevice(idx->device));
+    pa::ErrOp op("pa_containment_add");
+    return pa::containment_add(idx, reads, dp, acc, as_stream(stream));
+}
+
+// An accumulator whose index was reduced or freed since cannot be scanned: the
+// table its bits number is gone.  (The index a live accumulator names is kept
+// alive by its owner, as for every accumulator.)
+pa_status pa_containment_counts(const pa_containment *c, uint64_t *kmers, uint64_t *kmers_seen, uint64_t *specific,
+                                uint64_t *specific_seen, uint64_t *hits_specific, pa_containment_info *info,
+                                void *stream) {
+    PA_CHECK(c != nullptr, PA_EINVAL, "NULL argument");
+    PA_TRY(check_index(c->idx));
+    PA_TRY(check_acc(c, c->idx, "pa_containment"));
+    PA_HIP(hipSetDevice(c->device));
+    pa::ErrOp op("pa_containment_counts");
+    return pa::containment_counts(c, kmers, kmers_seen, specific, specific_seen, hits_specific, info,
+                                  as_stream(stream));
+}
+
+pa_status pa_containment_nodes(const pa_containment *c, const pa_lineage *l, uint64_t *direct_kmers,
+                               uint64_t *direct_seen, uint64_t *clade_kmers, uint64_t *clade_seen, void *stream) {
+    PA_CHECK(c != nullptr && l != nullptr, PA_EINVAL, "NULL argument");
+    PA_TRY(check_index(c->idx));
+    PA_TRY(check_acc(c, c->idx, "pa_containment"));
+    PA_TRY(check_acc(l, c->idx, "pa_lineage"));
+    PA_HIP(hipSetDevice(c->device));
+    pa::ErrOp op("pa_containment_nodes");
+    return pa::containment_nodes(c, l, direct_kmers, direct_seen, clade_kmers, clade_seen, as_stream(stream));
+}
+
+void pa_containment_free(pa_containment *c) {
+    if (!c) return;
+    hipSetDevice(c->device);
+    pa::containment_free(c);
+}
+
 pa_status pa_profile_enable(pa_index *idx, int32_t enable) {
     PA_CHECK(idx != nullptr, PA_EINVAL, "NULL argument");
     idx->profile = enable != 0;

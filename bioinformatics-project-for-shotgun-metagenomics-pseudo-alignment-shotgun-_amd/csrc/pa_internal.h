@@ -416,6 +416,15 @@ struct pa_lineage : pa::AccBase {
     unsigned long long *counts = nullptr;  // device [4 + G] as pa_abundance's (candidates_device fills it)
 };
 
+// Containment accumulator of one index (pa_contain.hip): one bit per table
+// slot, set when a retained window of a read found that k-mer.
+struct pa_containment : pa::AccBase {
+    uint32_t *bits = nullptr;              // device [cap / 32, rounded up] bit `slot`
+    uint64_t bits_bytes = 0;
+    unsigned long long *hits = nullptr;    // device [G] retained windows whose set is {g}
+    unsigned long long *counters = nullptr;  // device [8]: pa_containment_info's seven, the atomic ORs issued
+};
+
 struct pa_result {
     int device = 0;
     uint32_t n_genomes = 0;
@@ -582,6 +591,17 @@ pa_status lineage_counts(const pa_lineage *l, uint64_t *direct, uint64_t *clade,
                          hipStream_t st);
 pa_status lineage_lca(const pa_lineage *l, const uint64_t *set_off, const uint32_t *sets, uint64_t n_sets,
                       uint32_t *node_out, hipStream_t st);
+// containment (pa_contain.hip): needs the table and the classes only, never the align-side view
+pa_status containment_create(const pa_index *idx, pa_containment **out);
+pa_status containment_reset(pa_containment *c, hipStream_t st);
+void containment_free(pa_containment *c);
+pa_status containment_add(const pa_index *idx, const pa_reads *r, const DevParams &p, pa_containment *acc,
+                          hipStream_t st);
+pa_status containment_counts(const pa_containment *c, uint64_t *kmers, uint64_t *kmers_seen, uint64_t *specific,
+                             uint64_t *specific_seen, uint64_t *hits_specific, pa_containment_info *info,
+                             hipStream_t st);
+pa_status containment_nodes(const pa_containment *c, const pa_lineage *l, uint64_t *direct_kmers,
+                            uint64_t *direct_seen, uint64_t *clade_kmers, uint64_t *clade_seen, hipStream_t st);
 // pairs (pa_pair.hip; the pair-exact kernel is k_align_exact's sibling in pa_align.hip)
 pa_status pair_exact_pass(pa_index *idx, const pa_reads *m1, const pa_reads *m2, const DevParams &p,
                           const uint32_t *d_queue, const unsigned long long *d_count, uint64_t n_queued,

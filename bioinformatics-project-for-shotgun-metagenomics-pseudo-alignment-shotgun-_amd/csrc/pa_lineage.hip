@@ -25,6 +25,7 @@
 #include "pa_device.h"
 #include "pa_internal.h"
 #include "pa_tree.h"
+#include "pa_tree_dev.h"
 
 namespace {
 
@@ -35,19 +36,8 @@ constexpr uint32_t kNoNode = PA_NO_NODE;
 // covers the same 16 genomes in a quarter of one load instruction.
 constexpr uint32_t kLaneSet = 16;
 
-struct TreeDev {
-    const uint32_t *parent, *last, *node_of, *gpre;  // [n_nodes] x 3 by preorder number; [G]
-    uint32_t n_nodes, G;
-};
-
-// The climb from the smaller preorder number until the subtree's interval holds
-// the larger; the caller's node.  mn <= mx < n_nodes; the root's interval holds
-// every number, so the loop ends there at the latest.
-__device__ __forceinline__ uint32_t climb(const TreeDev &t, uint32_t mn, uint32_t mx) {
-    uint32_t v = mn;
-    while (t.last[v] < mx && v != 0) v = t.parent[v];
-    return t.node_of[v];
-}
+using pad::climb;  // (pa_tree_dev.h: the k-mers' reduction of pa_contain.hip climbs the same tables)
+using pad::TreeDev;
 
 template <bool LDS>
 __device__ __forceinline__ void count_node(uint32_t *hist, unsigned long long *direct, uint32_t node) {

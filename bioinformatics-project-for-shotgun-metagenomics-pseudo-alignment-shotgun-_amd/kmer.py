@@ -718,6 +718,46 @@ _ABUNDANCE: "weakref.WeakKeyDictionary[PseudoAlignment, Optional[N.Abundance]]" 
 # with the first batch (or the first report), from the index's genomes.
 _LINEAGE: "weakref.WeakKeyDictionary[PseudoAlignment, list]" = weakref.WeakKeyDictionary()
 
+# Containment accumulators of the alignments made with containment=True, kept
+# like _COVERAGE and for the same reason: [accumulator or None, reads of batches
+# dropped whole on the host].
+_CONTAINMENT: "weakref.WeakKeyDictionary[PseudoAlignment, list]" = weakref.WeakKeyDictionary()
+
+CONTAINMENT_HEADER = ("#genome\tlength\tkmers\tkmers_seen\tcontainment\tidentity\tspecific_kmers\tspecific_seen"
+                      "\tspecific_containment\tspecific_hits\tduplication\n")
+CONTAINMENT_INFO = ("reads", "reads_dropped", "windows", "windows_retained", "windows_filtered_quality",
+                    "windows_filtered_hr", "windows_absent")
+
+
+def containment_ratios(k, kmers, kmers_seen, specific, specific_seen, hits_specific):
+    """(containment, specific_containment, duplication, identity) of one genome or
+    node: kmers_seen / kmers, specific_seen / specific, hits_specific /
+    specific_seen and containment ** (1 / k), each 0 when its denominator is 0."""
+    c = int(kmers_seen) / int(kmers) if int(kmers) else 0.0
+    sc = int(specific_seen) / int(specific) if int(specific) else 0.0
+    d = int(hits_specific) / int(specific_seen) if int(specific_seen) else 0.0
+    return c, sc, d, (c ** (1.0 / k) if k else 0.0)
+
+
+def containment_text(rows, info) -> str:
+    """The --containment file: CONTAINMENT_HEADER, one tab-separated line per row
+    of get_containment's "genomes" (floats as format(x, ".9g")) and a last
+    comment line with the reads and the windows' counters."""
+    def f(x) -> str:
+        return format(float(x), ".9g")
+    lines = [CONTAINMENT_HEADER]
+    for r in rows:
+        lines.append("\t".join((str(r["genome"]), str(int(r["length"])), str(int(r["kmers"])),
+                                str(int(r["kmers_seen"])), f(r["containment"]), f(r["identity"]),
+                                str(int(r["specific_kmers"])), str(int(r["specific_seen"])),
+                                f(r["specific_containment"]), str(int(r["specific_hits"])),
+                                f(r["duplication"]))) + "\n")
+    lines.append(f"#reads\t{int(info['reads'])}\tdropped\t{int(info['reads_dropped'])}"
+                 f"\twindows\t{int(info['windows'])}\tretained\t{int(info['windows_retained'])}"
+                 f"\tfiltered_quality\t{int(info['windows_filtered_quality'])}"
+                 f"\tfiltered_hr\t{int(info['windows_filtered_hr'])}\tabsent\t{int(info['windows_absent'])}\n")
+    return "".join(lines)
+
 ABUNDANCE_HEADER = "#genome\tlength\tunique_reads\tcompatible_reads\testimated_reads\tread_fraction\tabundance\n"
 
 
@@ -827,11 +867,19 @@ class PseudoAlignment:
     batches gets a node of the genomes' taxonomy tree -- its genome's node, or
     the lowest common ancestor of its compatibility set -- and
     ``get_lineage_report`` / ``write_lineage_report`` report the reads per node
-    and clade; ``write_assignments`` gains a ``taxon`` column."""
+    and clade; ``write_assignments`` gains a ``taxon`` column.
+
+    ``containment=True`` (not in the reference either): every retained window of
+    those batches marks its k-mer of the index, and ``get_containment`` /
+    ``write_containment`` report, per genome, how many of its distinct k-mers
+    the reads hold; with ``lineages`` the lineage report gains the same per
+    clade."""
 
     def __init__(self, kmer_reference: KmerReference, coverage: bool = False, pileup: bool = False,
                  min_base_quality: Optional[int] = None, abundance: bool = False,
-                 lineages: Optional[Lineages] = None) -> None:
+                 lineages: Optional[Lineages] = None, containment: bool = False) -> None:
+        if containment:
+            _CONTAINMENT[self] = [None, 0]  # (the accumulator is made with the first batch)
         if lineages is not None:
             if not isinstance(lineages, Lineages):
                 raise ValueError("lineages must be a Lineages")
@@ -927,7 +975,8 @@ class PseudoAlignment:
         from data_file import FASTAQFile
         # (a coverage job takes the host-parsed path: the placements need the read columns)
         fresh = (not self._batches and not self._host and self._result is None and self not in _COVERAGE
-                 and self not in _PILEUP and self not in _ABUNDANCE and self not in _LINEAGE)
+                 and self not in _PILEUP and self not in _ABUNDANCE and self not in _LINEAGE
+                 and self not in _CONTAINMENT)
         err = _check_align_args(self.kmer_reference, m, p, min_read_quality, min_kmer_quality, max_genomes)
         n = None
         if fresh and err is None and os.environ.get("PA_STREAM", "1") != "0":
@@ -978,7 +1027,8 @@ class PseudoAlignment:
             keep = np.fromiter((name in wanted for name in names), dtype=np.uint8, count=len(names))
         spec = N.ExtractSpec.make(type_mask, keep, invert)
         fresh = (not self._batches and not self._host and self._result is None and self not in _COVERAGE
-                 and self not in _PILEUP and self not in _ABUNDANCE and self not in _LINEAGE)
+                 and self not in _PILEUP and self not in _ABUNDANCE and self not in _LINEAGE
+                 and self not in _CONTAINMENT)
         err = _check_align_args(ref, m, p, min_read_quality, min_kmer_quality, max_genomes)
         with open(out_file, "wb") as fh:
             if fresh and err is None and not host_parsed and os.environ.get("PA_STREAM", "1") != "0":
@@ -1081,6 +1131,8 @@ class PseudoAlignment:
             if self in _LINEAGE:
                 _LINEAGE[self][3] += n
                 read_node = np.full(n, N.NO_NODE, dtype=np.uint32)
+            if self in _CONTAINMENT:
+                _CONTAINMENT[self][1] += n
         else:
             if self._result is None:
                 self._result = N.Result(ref.index)
@@ -1099,6 +1151,8 @@ class PseudoAlignment:
                 self._abundance().add(reads, prm)
             if self in _LINEAGE:
                 read_node = self._lineage().add(reads, prm)
+            if self in _CONTAINMENT:
+                self._containment().add(reads, prm)
             reads.close()
             delta = stats - self._gpu_stats
             self._gpu_stats = stats
@@ -1127,6 +1181,8 @@ class PseudoAlignment:
             raise ValueError("pairs are not supported with coverage, pileup or abundance: those accumulators take reads")
         if self in _LINEAGE:
             raise ValueError("pairs are not supported with lineages: that accumulator takes reads")
+        if self in _CONTAINMENT:
+            raise ValueError("pairs are not supported with containment: that accumulator takes reads")
         ids1, seq1, qual1, off1 = _columnar(reads1)
         ids2, seq2, qual2, off2 = _columnar(reads2)
         if len(ids1) != len(ids2):
@@ -1478,6 +1534,12 @@ class PseudoAlignment:
         tree = self._lineage_tree()
         direct, clade, info = self._lineage().counts()
         rows = lineage_report_rows(tree, direct, clade)
+        if self in _CONTAINMENT:  # (section 21: the clades' k-mers, after every other column)
+            _, _, ck, cs = self._containment().nodes(self._lineage())
+            for r in rows:
+                v = r["node"]
+                r["kmers_clade"], r["kmers_seen_clade"] = int(ck[v]), int(cs[v])
+                r["kmer_containment"] = int(cs[v]) / int(ck[v]) if int(ck[v]) else 0.0
         dropped = info["reads_dropped"] + _LINEAGE[self][3]
         out: Dict[str, Any] = {"rows": rows, "classified": int(clade[0]), "unmapped": info["reads_unmapped"],
                                "dropped": dropped, "nodes": tree.n_nodes}
@@ -1505,7 +1567,57 @@ class PseudoAlignment:
         if "iterations" in rep:
             boot = (rep["bootstraps"], rep["seed"], rep["confidence"]) if "bootstraps" in rep else None
             ab = (rep["iterations"], rep["last_delta"], rep["classes"], boot)
-        fh.write(lineage_report_text(rep["rows"], rep["reads"], rep["unmapped"], rep["dropped"], ab))
+        fh.write(lineage_report_text(rep["rows"], rep["reads"], rep["unmapped"], rep["dropped"], ab,
+                                     containment=self in _CONTAINMENT))
+
+    def _containment(self) -> "N.Containment":
+        slot = _CONTAINMENT[self]
+        if slot[0] is None:
+            slot[0] = N.Containment(self.kmer_reference.index)
+        return slot[0]
+
+    def get_containment(self, genomes: Optional[Sequence[str]] = None) -> Dict[str, Any]:
+        """The distinct k-mers of every genome the reads hold (DESIGN.md section
+        21): ``{"genomes": [{"genome", "length", "kmers", "kmers_seen",
+        "containment", "identity", "specific_kmers", "specific_seen",
+        "specific_containment", "specific_hits", "duplication"}, ...], "info":
+        {CONTAINMENT_INFO}}`` for the genomes named in ``genomes`` (None: all),
+        in FASTA order.  ValueError for an alignment made without
+        ``containment=True`` (or loaded from a file) and for an unknown
+        identifier."""
+        if self not in _CONTAINMENT:
+            raise ValueError("this alignment was made without containment=True")
+        ref = self.kmer_reference
+        names = [g.identifier for g in ref.genomes]
+        wanted = None
+        if genomes is not None:
+            known = set(names)
+            unknown = [x for x in genomes if x not in known]
+            if unknown:
+                raise ValueError(f"unknown genome identifier: {unknown[0]}")
+            wanted = set(genomes)
+        c, info = self._containment().counts()
+        info["reads"] += _CONTAINMENT[self][1]
+        info["reads_dropped"] += _CONTAINMENT[self][1]
+        k = int(ref.kmer_len)
+        lengths = self._containment().lengths
+        rows = []
+        for g, name in enumerate(names):
+            if wanted is not None and name not in wanted:
+                continue
+            cont, scont, dup, ident = containment_ratios(k, c["kmers"][g], c["kmers_seen"][g], c["specific"][g],
+                                                         c["specific_seen"][g], c["hits_specific"][g])
+            rows.append({"genome": name, "length": lengths[g], "kmers": int(c["kmers"][g]),
+                         "kmers_seen": int(c["kmers_seen"][g]), "containment": cont, "identity": ident,
+                         "specific_kmers": int(c["specific"][g]), "specific_seen": int(c["specific_seen"][g]),
+                         "specific_containment": scont, "specific_hits": int(c["hits_specific"][g]),
+                         "duplication": dup})
+        return {"genomes": rows, "info": info}
+
+    def write_containment(self, fh, genomes: Optional[Sequence[str]] = None) -> None:
+        """get_containment as text (containment_text)."""
+        rep = self.get_containment(genomes)
+        fh.write(containment_text(rep["genomes"], rep["info"]))
 
     def get_reads_by_mapping_type(self, mapping_type: ReadMappingType) -> List[str]:
         return [rid for rid, d in self.reads.items() if d["mapping_type"] == mapping_type]

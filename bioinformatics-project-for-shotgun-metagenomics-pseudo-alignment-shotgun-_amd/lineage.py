@@ -11,6 +11,7 @@ from typing import Dict, List, Mapping, Optional, Sequence, Tuple
 ROOT_NAME = "root"
 LINEAGE_HEADER_COLUMNS = ("#taxon", "depth", "genomes", "reads_clade", "reads_direct", "clade_share")
 LINEAGE_ABUNDANCE_COLUMNS = ("read_fraction", "abundance")
+LINEAGE_KMER_COLUMNS = ("kmers_clade", "kmers_seen_clade", "kmer_containment")
 ASSIGNMENTS_TAXON_HEADER = "#read\tmapping\tgenomes\ttaxon\n"
 
 
@@ -164,7 +165,8 @@ def lineage_report_rows(tree: LineageTree, direct: Sequence[int], clade: Sequenc
              "clade_share": int(clade[v]) / classified if classified else 0.0} for v in tree.order]
 
 
-def lineage_report_text(rows: Sequence[dict], reads: int, unmapped: int, dropped: int, abundance=None) -> str:
+def lineage_report_text(rows: Sequence[dict], reads: int, unmapped: int, dropped: int, abundance=None,
+                        containment: bool = False) -> str:
     """The --lineage-report file: the header, one tab-separated line per row
     (lineage_report_rows; floats as format(x, ".9g")) and a last comment line
     with the reads, the classified, unmapped and dropped ones and the nodes.
@@ -172,7 +174,8 @@ def lineage_report_text(rows: Sequence[dict], reads: int, unmapped: int, dropped
     hold "read_fraction" and "abundance": those columns are added and the EM's
     settings appended to the last line as abundance_text appends them;
     bootstrap = None or (bootstraps, seed, confidence) when the rows also hold
-    the four bootstrap columns."""
+    the four bootstrap columns.  ``containment``: the rows also hold
+    LINEAGE_KMER_COLUMNS, written after every other column."""
     from kmer import ABUNDANCE_BOOTSTRAP_COLUMNS
     cols = list(LINEAGE_HEADER_COLUMNS)
     extra: List[str] = []
@@ -184,7 +187,8 @@ def lineage_report_text(rows: Sequence[dict], reads: int, unmapped: int, dropped
         if bootstrap is not None:
             extra += list(ABUNDANCE_BOOTSTRAP_COLUMNS)
             last += f"\tbootstraps\t{int(bootstrap[0])}\tseed\t{int(bootstrap[1])}\tconfidence\t{_f(bootstrap[2])}"
-    lines = ["\t".join(cols + extra) + "\n"]
+    kmers = list(LINEAGE_KMER_COLUMNS) if containment else []
+    lines = ["\t".join(cols + extra + kmers) + "\n"]
     classified = 0
     for r in rows:
         if r["depth"] == 0:
@@ -192,6 +196,8 @@ def lineage_report_text(rows: Sequence[dict], reads: int, unmapped: int, dropped
         out = [str(r["taxon"]), str(int(r["depth"])), str(int(r["genomes"])), str(int(r["reads_clade"])),
                str(int(r["reads_direct"])), _f(r["clade_share"])]
         out += [_f(r[c]) for c in extra]
+        if containment:
+            out += [str(int(r["kmers_clade"])), str(int(r["kmers_seen_clade"])), _f(r["kmer_containment"])]
         lines.append("\t".join(out) + "\n")
     lines.append(f"#reads\t{int(reads)}\tclassified\t{classified}\tunmapped\t{int(unmapped)}\tdropped\t{int(dropped)}"
                  f"\tnodes\t{len(rows)}{last}\n")
@@ -199,4 +205,4 @@ def lineage_report_text(rows: Sequence[dict], reads: int, unmapped: int, dropped
 
 
 __all__ = ["Lineages", "LineageTree", "parse_lineage_line", "lineage_report_rows", "lineage_report_text",
-           "ROOT_NAME", "LINEAGE_HEADER_COLUMNS", "LINEAGE_ABUNDANCE_COLUMNS", "ASSIGNMENTS_TAXON_HEADER"]
+           "ROOT_NAME", "LINEAGE_HEADER_COLUMNS", "LINEAGE_ABUNDANCE_COLUMNS", "LINEAGE_KMER_COLUMNS", "ASSIGNMENTS_TAXON_HEADER"]

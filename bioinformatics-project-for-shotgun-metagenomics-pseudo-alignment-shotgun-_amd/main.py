@@ -11,6 +11,7 @@
                     [--abundance FILE [--abundance-iterations N] [--abundance-tolerance X]
                      [--abundance-bootstraps B [--abundance-seed S] [--abundance-confidence X]]]
                     [--lineages FILE [--lineage-report FILE]]
+                    [--containment FILE]
                     [--extract FILE [--extract-mapping LIST] [--extract-genomes a,b] [--extract-invert]]
 
 Same tasks (reference | dumpref | align | dumpalign), flags, flag-combination
@@ -113,6 +114,16 @@ def _has_lineage_flag(argv: List[str]) -> bool:
     return False
 
 
+def _has_containment_flag(argv: List[str]) -> bool:
+    """--containment on the command line, in any spelling the parser accepts
+    (`--con` and longer: `--c` and `--co` are --coverage's)."""
+    for a in argv:
+        name = a.split("=", 1)[0]
+        if name.startswith("--con") and "--containment".startswith(name):
+            return True
+    return False
+
+
 _EXTRACT_FLAGS = ("--extract", "--extract-mapping", "--extract-genomes", "--extract-invert")
 
 
@@ -167,6 +178,8 @@ def _early_reads_path(argv: List[str]) -> Optional[str]:
     if _has_abundance_flag(argv):  # (and an abundance job: the candidate pass needs the read columns)
         return None
     if _has_lineage_flag(argv):  # (and a lineage job, as an abundance job)
+        return None
+    if _has_containment_flag(argv):  # (and a containment job: its pass takes the read columns)
         return None
     if _has_extract_flag(argv):  # (an extract job streams the file in windows itself, records gathered per window)
         return None
@@ -249,7 +262,15 @@ def validate_file_writable(filepath: str, description: str) -> None:
 
 
 def parse_arguments(args: Optional[List[str]] = None) -> argparse.Namespace:
-    parser = argparse.ArgumentParser(prog="Biosequence project")
+    class _Parser(argparse.ArgumentParser):
+        # --containment answers to `--con...` only: `--c` and `--co` stay --coverage's abbreviations
+        def _get_option_tuples(self, option_string):
+            found = super()._get_option_tuples(option_string)
+            if len(found) > 1 and not option_string.split("=", 1)[0].startswith("--con"):
+                found = [t for t in found if "--containment" not in t[0].option_strings]
+            return found
+
+    parser = _Parser(prog="Biosequence project")
     parser.add_argument("-t", "--task", required=True, help="Task to execute")
     parser.add_argument("-g", "--genomefile", help="Genome FASTA file (multiple records)")
     parser.add_argument("-k", "--kmer-size", type=int, help="Length of k-mers")
@@ -306,6 +327,9 @@ def parse_arguments(args: Optional[List[str]] = None) -> argparse.Namespace:
     parser.add_argument("--lineage-report", default=None, metavar="FILE",
                         help="write one line per node of the lineage tree (reads in the clade, on the node) to FILE")
     # not in the reference: the selected reads written back out as FASTQ, dumpalign with --reads
+    parser.add_argument("--containment", default=None, metavar="FILE",
+                        help="write one line per genome (its distinct k-mers, those the reads hold, the containment "
+                             "and identity from them) to FILE")
     parser.add_argument("--extract", default=None, metavar="FILE",
                         help="write the selected reads' FASTQ records to FILE, in file order")
     parser.add_argument("--extract-mapping", default=None, metavar="LIST",
@@ -390,7 +414,8 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
                                     prefetch=None, per_read: bool = False,
                                     coverage: bool = False, assignments: bool = False,
                                     pileup: bool = False, min_base_quality=None,
-                                    abundance: bool = False, lineages=None, extract=None) -> PseudoAlignment:
+                                    abundance: bool = False, lineages=None, extract=None,
+                                    containment: bool = False) -> PseudoAlignment:
     # the FASTQ file goes straight to the device (parsed there, aligned in
     # windows); a file outside that subset of the grammar is parsed the exact
     # way (FASTAQFile), which also raises the reference's errors.  per_read
@@ -404,9 +429,11 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
     # pileup: likewise (the base counts need the read columns); abundance: likewise (the candidate pass does)
     # lineages: likewise (its pass is the candidate pass); the tree is made over the index's genomes, now,
     # so that a genome without a lineage ends the job before a read is aligned
+    # containment: likewise (the mark pass takes the read columns)
     alignment = (PseudoAlignment(kmer_reference, coverage=coverage, pileup=pileup, min_base_quality=min_base_quality,
-                                 abundance=abundance, lineages=lineages)
-                 if coverage or pileup or abundance or lineages is not None else PseudoAlignment(kmer_reference))
+                                 abundance=abundance, lineages=lineages, containment=containment)
+                 if coverage or pileup or abundance or lineages is not None or containment
+                 else PseudoAlignment(kmer_reference))
     if lineages is not None:
         try:
             alignment._lineage_tree()
@@ -561,6 +588,14 @@ def _check_task(args: argparse.Namespace) -> None:
         validate_file_readable(args.lineages, "Lineages")
         if args.lineage_report is not None:
             validate_file_writable(args.lineage_report, "Lineage report output")
+    if args.containment is not None:
+        if args.task != "dumpalign" or not args.reads:
+            sys.exit("Error: --containment is only allowed for task 'dumpalign' with --reads.")
+        if args.reads2 is not None:
+            sys.exit("Error: --reads2 cannot be combined with --containment (the containment pass takes single reads).")
+        if args.alignfile:
+            sys.exit("Error: --containment cannot be combined with -a.")
+        validate_file_writable(args.containment, "Containment output")
     if args.extract is None and (args.extract_mapping is not None or args.extract_genomes is not None
                                  or args.extract_invert):
         sys.exit("Error: --extract-mapping, --extract-genomes and --extract-invert need --extract.")
@@ -656,6 +691,9 @@ def _print_alignment(alignment: PseudoAlignment, args: argparse.Namespace) -> No
     if args.lineage_report is not None:  # (with --abundance: its estimates rolled up the tree, under the same settings)
         with open(args.lineage_report, "w") as fh:
             alignment.write_lineage_report(fh, *em)
+    if args.containment is not None:
+        with open(args.containment, "w") as fh:
+            alignment.write_containment(fh)
 
 
 def _run(args: argparse.Namespace) -> None:
@@ -705,7 +743,8 @@ def _run(args: argparse.Namespace) -> None:
                 _print_alignment(create_alignment_from_pairs(ref, args.reads, args.reads2, *filt), args)
                 return
             host_parsed = (args.coverage or args.assignments is not None or args.variants is not None
-                           or args.abundance is not None or args.lineages is not None)
+                           or args.abundance is not None or args.lineages is not None
+                           or args.containment is not None)
             pf = None if host_parsed or args.extract is not None else _prefetch_reads(args.reads)
             ref = _load_reference(args.referencefile)
             _check_strands(args, ref)
@@ -716,7 +755,8 @@ def _run(args: argparse.Namespace) -> None:
                                                              min_base_quality=args.variant_min_base_quality,
                                                              abundance=args.abundance is not None,
                                                              lineages=_load_lineages(args),
-                                                             extract=_extract_job(args)), args)
+                                                             extract=_extract_job(args),
+                                                             containment=args.containment is not None), args)
         elif args.genomefile and args.kmer_size and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
             validate_file_readable(args.genomefile, "Genome FASTA")
@@ -731,7 +771,8 @@ def _run(args: argparse.Namespace) -> None:
             # an assignments job too: its lines come from one host-parsed batch; a pileup job and an
             # abundance job, as coverage)
             host_parsed = (args.coverage or args.assignments is not None or args.variants is not None
-                           or args.abundance is not None or args.lineages is not None)
+                           or args.abundance is not None or args.lineages is not None
+                           or args.containment is not None)
             # (an extract job too: its output is written by one device, window after window)
             sharded = None if host_parsed or args.extract is not None else _dumpalign_sharded(args, filt)
             if sharded is not None:
@@ -747,7 +788,8 @@ def _run(args: argparse.Namespace) -> None:
                                                              min_base_quality=args.variant_min_base_quality,
                                                              abundance=args.abundance is not None,
                                                              lineages=_load_lineages(args),
-                                                             extract=_extract_job(args)), args)
+                                                             extract=_extract_job(args),
+                                                             containment=args.containment is not None), args)
         elif args.alignfile:
             validate_file_readable(args.alignfile, "Alignment output")
             try:

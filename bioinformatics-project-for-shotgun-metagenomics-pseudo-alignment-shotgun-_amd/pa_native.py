@@ -60,6 +60,8 @@ EXPORTS = (
     "pa_abundance_create", "pa_abundance_reset", "pa_abundance_add", "pa_abundance_info_get", "pa_abundance_classes",
     "pa_abundance_estimate", "pa_abundance_bootstrap", "pa_abundance_free", "pa_align_candidates",
     "pa_lineage_create", "pa_lineage_reset", "pa_lineage_add", "pa_lineage_counts", "pa_lineage_lca", "pa_lineage_free",
+    "pa_containment_create", "pa_containment_reset", "pa_containment_add", "pa_containment_counts",
+    "pa_containment_nodes", "pa_containment_free",
     "pa_profile_enable", "pa_profile_read", "pa_profile_read_kernels", "pa_mem_trim",
     "pa_parse_text", "pa_parse_file", "pa_seqset_sizes", "pa_seqset_export", "pa_seqset_free", "pa_gz_inflate_file",
 )
@@ -111,6 +113,11 @@ class AbundanceInfo(ctypes.Structure):
 class LineageInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("reads_unique", "reads_ambiguous", "reads_unmapped", "reads_dropped")] \
         + [("n_nodes", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class ContainmentInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("reads", "reads_dropped", "windows", "windows_retained",
+                                               "windows_filtered_quality", "windows_filtered_hr", "windows_absent")]
 
 
 class ExtractSpec(ctypes.Structure):
@@ -254,6 +261,12 @@ def lib():
         "pa_lineage_counts": (I32, [P, P, P, ctypes.POINTER(LineageInfo), P]),
         "pa_lineage_lca": (I32, [P, P, P, U64, P, P]),
         "pa_lineage_free": (None, [P]),
+        "pa_containment_create": (I32, [P, PP]),
+        "pa_containment_reset": (I32, [P, P]),
+        "pa_containment_add": (I32, [P, P, ctypes.POINTER(Params), P, P]),
+        "pa_containment_counts": (I32, [P, P, P, P, P, P, ctypes.POINTER(ContainmentInfo), P]),
+        "pa_containment_nodes": (I32, [P, P, P, P, P, P, P]),
+        "pa_containment_free": (None, [P]),
         "pa_profile_enable": (I32, [P, I32]),
         "pa_profile_read": (I32, [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), ctypes.POINTER(U64)]),
         "pa_profile_read_kernels": (I32, [P, P, P]),
@@ -1469,6 +1482,57 @@ class Lineage:
     def close(self):
         if getattr(self, "_h", None):
             lib().pa_lineage_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class Containment:
+    """The distinct reference k-mers the reads hold (pa_containment, DESIGN.md
+    section 21): one bit per k-mer of the index, set by ``add`` for every
+    retained window of a batch (``params``' m and p are ignored); ``counts``
+    reads them per genome, ``nodes`` per node and clade of a Lineage's tree."""
+
+    def __init__(self, index: Index):
+        h = P()
+        _check(lib().pa_containment_create(index.handle, ctypes.byref(h)))
+        self._h = h
+        self._index = index  # (kept alive: the accumulator's bits number its table's slots)
+        self.n_genomes = index.n_genomes
+        self.lengths = [int(x) for x in index.genome_lengths]  # forward bases per genome
+
+    @property
+    def handle(self):
+        return self._h
+
+    def add(self, reads: Reads, params: Params, stream=None) -> None:
+        _check(lib().pa_containment_add(self._index.handle, reads.handle, ctypes.byref(params), self._h,
+                                        _stream(stream)))
+
+    def reset(self, stream=None) -> None:
+        _check(lib().pa_containment_reset(self._h, _stream(stream)))
+
+    def counts(self, stream=None):
+        """({"kmers", "kmers_seen", "specific", "specific_seen", "hits_specific"}: uint64
+        arrays [n_genomes], info) since the last reset; info holds the seven
+        counters of pa_containment_info."""
+        names = ("kmers", "kmers_seen", "specific", "specific_seen", "hits_specific")
+        out = {n: np.zeros(self.n_genomes, dtype=np.uint64) for n in names}
+        s = ContainmentInfo()
+        _check(lib().pa_containment_counts(self._h, *[_ptr(out[n]) if self.n_genomes else None for n in names],
+                                           ctypes.byref(s), _stream(stream)))
+        return out, {n: int(getattr(s, n)) for n, _ in ContainmentInfo._fields_}
+
+    def nodes(self, lineage: Lineage, stream=None):
+        """(direct_kmers, direct_seen, clade_kmers, clade_seen): uint64 arrays
+        [lineage.n_nodes] in the caller's node numbers."""
+        out = [np.zeros(lineage.n_nodes, dtype=np.uint64) for _ in range(4)]
+        _check(lib().pa_containment_nodes(self._h, lineage.handle, *[_ptr(a) for a in out], _stream(stream)))
+        return tuple(out)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().pa_containment_free(self._h)
             self._h = None
 
     __del__ = close

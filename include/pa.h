@@ -46,6 +46,10 @@
  *   pa_lineage_*             every read's node in a taxonomy tree (the lowest common ancestor of its
  *                            compatibility set) and the reads per node and clade (--lineages); no
  *                            reference counterpart: the definition is DESIGN.md section 17
+ *   pa_containment_*         the distinct reference k-mers the reads hold, per genome and per node of
+ *                            a lineage tree (--containment); no reference counterpart: the definition
+ *                            is DESIGN.md section 21 (the windows are extract_kmer_references',
+ *                            src/kmer.py:410-429)
  *   pa_align_batch           one-shot host-buffer form of pa_align
  *   pa_align_fastq_file      FASTAQFile + align_reads_from_container as one
  *                            device-parsed stream                          src/data_file.py:134-158,
@@ -641,6 +645,62 @@ pa_status pa_lineage_counts(const pa_lineage *l, uint64_t *direct, uint64_t *cla
 pa_status pa_lineage_lca(const pa_lineage *l, const uint64_t *set_off, const uint32_t *sets, uint64_t n_sets,
                          uint32_t *node_out, void *stream);
 void pa_lineage_free(pa_lineage *l);
+
+/* ---- containment: the distinct reference k-mers the reads hold ----
+ *
+ * With the pa_params of pa_align (m and p are ignored):
+ *   1. A read dropped by --min-read-quality (quality sum < mrq * len, strict) adds
+ *      to reads and reads_dropped and to nothing else.
+ *   2. Every window j (0 .. len - k) of a kept read, in this order (that of
+ *      pa_align's exact kernel, which decides the counters):
+ *        a. with --min-kmer-quality: quality sum < mkq * k -> windows_filtered_quality;
+ *        b. a base other than ACGT, or a k-mer the index does not hold -> windows_absent;
+ *        c. with --max-genomes: set size > mg -> windows_filtered_hr;
+ *        d. else the window is retained: windows_retained, seen(w) = 1, and
+ *           hits_specific[g] += 1 when its set is {g}.  Repeats within a read and
+ *           across reads count every time.
+ *      A read shorter than k has no windows.  windows = the sum of the four.
+ *   3. Per genome g, S(w) the genome set of k-mer w: kmers[g] = the distinct k-mers
+ *      with g in S(w), specific[g] = those with S(w) = {g} (pa_index_extsim_stats'
+ *      total and uniq under the identity grouping); kmers_seen[g] and
+ *      specific_seen[g] = the same restricted to seen(w) = 1.  On a both-strand
+ *      index everything is that of the forward index of the regions T(g).
+ *   4. Per node v of a pa_lineage's tree: node(w) = the lowest common ancestor of
+ *      genome_node[g] over g in S(w); direct_kmers[v] / direct_seen[v] count the
+ *      k-mers with node(w) == v, clade_*[v] are the sums over v's subtree, so
+ *      clade_kmers[0] = n_kmers.
+ * 64-bit integers made by integer OR and integer add: the same reads give the
+ * same numbers in whatever batches they come.
+ *
+ * The accumulator holds one bit per table slot (capacity / 8 bytes), 8 bytes per
+ * genome and eight counters; its bytes are not part of pa_index_info; it runs on
+ * one device.  pa_containment_add needs the table and the classes only: an
+ * index built with PA_BUILD_DEFER_TILES stays deferred.  hits_specific goes
+ * through a histogram in LDS for up to PA_LINEAGE_LDS_NODES genomes, through
+ * 64-bit global atomics above (PA_CONTAIN_LDS=0 in the environment, read per
+ * call: global atomics always; the same counts).
+ *
+ * PA_EINVAL: an accumulator used with another index, or with its own after a
+ * pa_index_reduce; a lineage made for another index.  PA_ENOMEM leaves the
+ * index usable. */
+typedef struct pa_containment pa_containment;
+typedef struct {
+    uint64_t reads, reads_dropped, windows, windows_retained, windows_filtered_quality, windows_filtered_hr,
+        windows_absent;
+} pa_containment_info;
+pa_status pa_containment_create(const pa_index *idx, pa_containment **out);
+pa_status pa_containment_reset(pa_containment *c, void *stream);
+/* Returns when done; after an error `acc` may hold a part of the batch: reset it. */
+pa_status pa_containment_add(const pa_index *idx, const pa_reads *reads, const pa_params *params,
+                             pa_containment *acc, void *stream);
+/* kmers .. hits_specific: n_genomes entries each; any output may be NULL. */
+pa_status pa_containment_counts(const pa_containment *c, uint64_t *kmers, uint64_t *kmers_seen, uint64_t *specific,
+                                uint64_t *specific_seen, uint64_t *hits_specific, pa_containment_info *info,
+                                void *stream);
+/* direct_* / clade_*: the lineage's n_nodes entries each; any output may be NULL. */
+pa_status pa_containment_nodes(const pa_containment *c, const pa_lineage *l, uint64_t *direct_kmers,
+                               uint64_t *direct_seen, uint64_t *clade_kmers, uint64_t *clade_seen, void *stream);
+void pa_containment_free(pa_containment *c);
 
 /* upload + pa_align + fetch for host buffers (stats and per-genome arrays accumulate: +=, min) */
 pa_status pa_align_batch(const pa_index *idx, const uint8_t *seq, const uint8_t *qual, const uint64_t *read_off,

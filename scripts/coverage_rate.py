@@ -7,6 +7,7 @@ genomes, k = 31, synthesized 150-bp reads, 0.5 % substitutions).
     python scripts/coverage_rate.py --mode assign   [--reads N] [--runs R] [--read-err E --rc-rate X --foreign-rate Y]
     python scripts/coverage_rate.py --mode bootstrap [--reads N] [--runs R] [--replicates B]
     python scripts/coverage_rate.py --mode lineage  [--reads N] [--runs R]
+    python scripts/coverage_rate.py --mode containment [--reads N] [--runs R]
 
 --mode detail times one pa_align_detail call with its lists (the pass a
 coverage add rides on); run it with PA_LIBRARY=<the parent commit's libpa.so>
@@ -60,6 +61,13 @@ genome families, with and without the node array and under PA_LINEAGE_LDS=0
 (global atomics instead of the LDS histogram).  With PA_LIBRARY naming the
 parent's library (and PA_LIBRARY_PARTIAL=1), which has no pa_lineage_*, the
 line holds the two yardsticks only.
+
+--mode containment times pa_containment_add next to
+pa_align_reads and pa_align_detail with its lists on the same batch: the first
+add on clear bits, then the median of the later ones, the same under
+PA_CONTAIN_LDS=0, and the reduction (pa_containment_counts, and
+pa_containment_nodes under --mode lineage's tree).  One add runs with
+PA_CONTAIN_STATS=1: the library prints the atomic ORs issued so far to stderr.
 
 --mode pairs times pa_align_pairs on a both-strand C2
 index: --reads pairs (default 1 000 000) made on the host -- fragments of 300 ..
@@ -221,7 +229,7 @@ def run_pairs(args, genomes, out):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=("detail", "coverage", "assign", "pileup", "abundance", "bootstrap", "pairs",
-                                       "lineage"),
+                                       "lineage", "containment"),
                     required=True)
     ap.add_argument("--replicates", type=int, default=100, help="bootstrap replicates of --mode bootstrap")
     ap.add_argument("--reads", type=int, default=None, help="reads (default 10 000 000); pairs with --mode pairs (1 000 000)")
@@ -395,6 +403,41 @@ def main():
                    reads_on_root=int(direct[0]), classified=int(clade[0]),
                    no_node=int((nodes == N.NO_NODE).sum()))
         lin.close()
+    elif args.mode == "containment":
+        med, ts, entries = time_assign(index, reads, prm, args.runs)
+        out.update(align_reads_s=med, align_reads_runs_s=ts, list_entries=entries)
+        dmed, dts, _ = time_detail(index, reads, prm, args.runs)
+        out.update(align_detail_s=dmed, align_detail_runs_s=dts)
+        con = N.Containment(index)
+        os.environ["PA_CONTAIN_STATS"] = "1"  # (stderr: the atomic ORs issued since the reset, after each add)
+        t0 = time.perf_counter()
+        con.add(reads, prm)
+        out["containment_first_add_s"] = time.perf_counter() - t0  # (every k-mer's bit still clear)
+        con.add(reads, prm)
+        del os.environ["PA_CONTAIN_STATS"]
+        med, ts = timed(lambda: con.add(reads, prm), args.runs)
+        out.update(containment_add_s=med, containment_add_runs_s=ts, containment_reads_per_s=args.reads / med,
+                   ratio_containment_add_over_align_detail=med / dmed,
+                   ratio_containment_add_over_align_reads=med / out["align_reads_s"])
+        os.environ["PA_CONTAIN_LDS"] = "0"
+        med, ts = timed(lambda: con.add(reads, prm), args.runs)
+        out.update(containment_add_global_atomics_s=med)
+        del os.environ["PA_CONTAIN_LDS"]
+        holder = {}
+        med, ts = timed(lambda: holder.update(c=con.counts()), args.runs)
+        out.update(counts_s=med, counts_runs_s=ts)
+        species = (args.genomes + 4) // 5  # (--mode lineage's tree)
+        parent = [0] + [0] * species + [1 + g // 5 for g in range(args.genomes)]
+        lin = N.Lineage(index, parent, [1 + species + g for g in range(args.genomes)])
+        med, ts = timed(lambda: holder.update(n=con.nodes(lin)), args.runs)
+        out.update(nodes_s=med)
+        arrays, info = holder["c"]
+        out.update(info=info, kmers=int(arrays["kmers"].sum()), kmers_seen=int(arrays["kmers_seen"].sum()),
+                   specific=int(arrays["specific"].sum()), specific_seen=int(arrays["specific_seen"].sum()),
+                   n_kmers=int(index.info().n_kmers), clade_kmers_root=int(holder["n"][2][0]),
+                   clade_seen_root=int(holder["n"][3][0]), table_slots=int(index.info().table_slots))
+        lin.close()
+        con.close()
     else:
         med, ts, entries = time_detail(index, reads, prm, args.runs)
         out.update(align_detail_branch_s=med, align_detail_branch_runs_s=ts, list_entries=entries)
