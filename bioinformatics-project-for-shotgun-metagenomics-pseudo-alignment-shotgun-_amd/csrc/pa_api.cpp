@@ -111,6 +111,28 @@ pa_status check_extract_spec(const pa_extract_spec *spec) {
     return PA_OK;
 }
 
+// The trim of a pa_*_fastq_*_ex call (opts nullable): the spec checked, as the
+// streams take it; the windows' statistics summed here and added to the
+// caller's only when the call succeeds (a refused late window leaves them alone).
+struct StreamTrimCall {
+    pa::TrimSpec spec{};
+    pa_trim_stats got{};
+    pa::StreamTrim trim;
+    pa_trim_stats *dst = nullptr;
+    pa_status open(const pa_fastq_opts *opts) {
+        if (!opts || !opts->trim) return PA_OK;
+        PA_TRY(pa::trim_spec_check(opts->trim, &spec));
+        trim.spec = &spec;
+        trim.stats = &got;
+        dst = opts->trim_stats;
+        return PA_OK;
+    }
+    pa_status finish(pa_status rc) {
+        if (rc == PA_OK && dst) pa::trim_stats_add(dst, got);
+        return rc;
+    }
+};
+
 // The index's device current and its align-side view made.
 pa_status prepare_pass(const pa_index *idx, void *stream) {
     PA_HIP(hipSetDevice(idx->device));
@@ -461,6 +483,22 @@ pa_status pa_reads_download(const pa_reads *reads, uint64_t first, uint64_t coun
     return PA_OK;
 }
 
+pa_status pa_reads_trim(const pa_reads *in, const pa_trim_spec *spec, pa_reads **out, uint32_t *start,
+                        uint32_t *end, pa_trim_stats *stats, void *stream) {
+    PA_CHECK(in && spec && out, PA_EINVAL, "NULL argument");
+    *out = nullptr;
+    pa::TrimSpec t;
+    PA_TRY(pa::trim_spec_check(spec, &t));
+    PA_HIP(hipSetDevice(in->device));
+    std::unique_ptr<pa_reads, void (*)(pa_reads *)> r(new (std::nothrow) pa_reads(), pa_reads_free);
+    PA_CHECK(r != nullptr, PA_ENOMEM, "out of host memory");
+    pa_trim_stats got{};  // (the caller's sums move only when the call succeeds)
+    PA_TRY(pa::reads_trim(in, t, r.get(), start, end, &got, as_stream(stream)));
+    if (stats) pa::trim_stats_add(stats, got);
+    *out = r.release();
+    return PA_OK;
+}
+
 void pa_reads_free(pa_reads *reads) {
     if (!reads) return;
     hipSetDevice(reads->device);
@@ -575,15 +613,25 @@ pa_status pa_align(const pa_index *idx, const pa_reads *reads, const pa_params *
 pa_status pa_align_fastq_file(const pa_index *idx, const char *path, const pa_params *params,
                               uint64_t read_index_base, pa_result *acc, int32_t threads, uint64_t window_bytes,
                               void *stream, uint64_t *n_reads) {
+    return pa_align_fastq_file_ex(idx, path, params, read_index_base, acc, threads, window_bytes, stream, n_reads,
+                                  nullptr);
+}
+
+pa_status pa_align_fastq_file_ex(const pa_index *idx, const char *path, const pa_params *params,
+                                 uint64_t read_index_base, pa_result *acc, int32_t threads, uint64_t window_bytes,
+                                 void *stream, uint64_t *n_reads, const pa_fastq_opts *opts) {
     PA_CHECK(path && acc, PA_EINVAL, "NULL argument");
     PA_TRY(check_index(idx));
     PA_TRY(check_result(idx, acc));
     pa::DevParams dp;
     PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    StreamTrimCall tc;
+    PA_TRY(tc.open(opts));
     PA_HIP(hipSetDevice(idx->device));
     if (n_reads) *n_reads = 0;
-    return pa::align_fastq_file(const_cast<pa_index *>(idx), path, dp, read_index_base, acc, threads > 0 ? threads : 8,
-                                window_bytes ? window_bytes : (128ull << 20), as_stream(stream), n_reads);
+    return tc.finish(pa::align_fastq_file(const_cast<pa_index *>(idx), path, dp, read_index_base, acc,
+                                          threads > 0 ? threads : 8, window_bytes ? window_bytes : (128ull << 20),
+                                          as_stream(stream), n_reads, 0, ~0ull, nullptr, nullptr, -1, nullptr, tc.trim));
 }
 
 pa_status pa_align_fastq_range(const pa_index *idx, const char *path, uint64_t offset, uint64_t length,
@@ -627,6 +675,14 @@ pa_status pa_extract_fastq_file(const pa_index *idx, const char *path, const pa_
                                 const pa_extract_spec *spec, int32_t out_fd, uint64_t read_index_base,
                                 pa_result *acc, int32_t threads, uint64_t window_bytes, void *stream,
                                 pa_extract_stats *stats) {
+    return pa_extract_fastq_file_ex(idx, path, params, spec, out_fd, read_index_base, acc, threads, window_bytes,
+                                    stream, stats, nullptr);
+}
+
+pa_status pa_extract_fastq_file_ex(const pa_index *idx, const char *path, const pa_params *params,
+                                   const pa_extract_spec *spec, int32_t out_fd, uint64_t read_index_base,
+                                   pa_result *acc, int32_t threads, uint64_t window_bytes, void *stream,
+                                   pa_extract_stats *stats, const pa_fastq_opts *opts) {
     PA_CHECK(idx && path && params && spec && stats, PA_EINVAL, "NULL argument");
     *stats = pa_extract_stats{};
     PA_TRY(check_index(idx));
@@ -635,10 +691,12 @@ pa_status pa_extract_fastq_file(const pa_index *idx, const char *path, const pa_
     PA_CHECK(out_fd >= 0, PA_EINVAL, "bad file descriptor");
     pa::DevParams dp;
     PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    StreamTrimCall tc;
+    PA_TRY(tc.open(opts));
     PA_HIP(hipSetDevice(idx->device));
-    return pa::align_fastq_file(const_cast<pa_index *>(idx), path, dp, read_index_base, acc, threads > 0 ? threads : 8,
-                                window_bytes ? window_bytes : (128ull << 20), as_stream(stream), nullptr, 0, ~0ull,
-                                nullptr, spec, out_fd, stats);
+    return tc.finish(pa::align_fastq_file(const_cast<pa_index *>(idx), path, dp, read_index_base, acc,
+                                          threads > 0 ? threads : 8, window_bytes ? window_bytes : (128ull << 20),
+                                          as_stream(stream), nullptr, 0, ~0ull, nullptr, spec, out_fd, stats, tc.trim));
 }
 
 pa_status pa_idsets_disjoint(const pa_idset *const *sets, uint32_t n_sets, int32_t device, int32_t *disjoint) {
@@ -687,15 +745,23 @@ void pa_fastq_prefetch_free(pa_fastq_prefetch *pf) { pa::fastq_prefetch_free(pf)
 
 pa_status pa_align_fastq_prefetched(const pa_index *idx, pa_fastq_prefetch *pf, const pa_params *params,
                                     uint64_t read_index_base, pa_result *acc, void *stream, uint64_t *n_reads) {
+    return pa_align_fastq_prefetched_ex(idx, pf, params, read_index_base, acc, stream, n_reads, nullptr);
+}
+
+pa_status pa_align_fastq_prefetched_ex(const pa_index *idx, pa_fastq_prefetch *pf, const pa_params *params,
+                                       uint64_t read_index_base, pa_result *acc, void *stream, uint64_t *n_reads,
+                                       const pa_fastq_opts *opts) {
     PA_CHECK(pf && acc, PA_EINVAL, "NULL argument");
     PA_TRY(check_index(idx));
     PA_TRY(check_result(idx, acc));
     pa::DevParams dp;
     PA_TRY(to_dev_params(params, idx->n_genomes, &dp));
+    StreamTrimCall tc;
+    PA_TRY(tc.open(opts));
     PA_HIP(hipSetDevice(idx->device));
     if (n_reads) *n_reads = 0;
-    return pa::align_fastq_prefetched(const_cast<pa_index *>(idx), pf, dp, read_index_base, acc, as_stream(stream),
-                                      n_reads);
+    return tc.finish(pa::align_fastq_prefetched(const_cast<pa_index *>(idx), pf, dp, read_index_base, acc,
+                                                as_stream(stream), n_reads, tc.trim));
 }
 
 pa_status pa_align_detail(const pa_index *idx, const pa_reads *reads, const pa_params *params, uint8_t *read_type,

@@ -383,6 +383,11 @@ struct ParseBufs {
     unsigned long long *tile_off = nullptr, *bsum = nullptr, *rec_off = nullptr, *ids = nullptr, *tot = nullptr;
     Meta *meta = nullptr, *h_meta = nullptr;
     uint64_t ids_cap = 0, max_rec = 0;
+    // the trimmed window (pa_trim.hip): a second pair of columns, only when a trim is set
+    uint8_t *t_seq = nullptr, *t_qual = nullptr;
+    uint64_t *t_off = nullptr;
+    uint32_t *t_start = nullptr, *t_end = nullptr, *t_len = nullptr;
+    unsigned long long *t_cnt = nullptr;
 
     hipError_t alloc(uint64_t span, uint64_t est_rec, hipStream_t st) {
         const uint64_t max_tiles = span / kTile + 2;
@@ -410,9 +415,25 @@ struct ParseBufs {
         if (e == hipSuccess) e = hipMemsetAsync(meta, 0, sizeof(Meta), st);
         return e;
     }
+    hipError_t alloc_trim(uint64_t span) {
+        hipError_t e = hipSuccess;
+        auto m = [&](void **p, uint64_t b) {
+            if (e == hipSuccess) e = pa::dev_malloc(p, b);
+        };
+        m((void **)&t_seq, span + kReadPad);
+        m((void **)&t_qual, span + kReadPad);
+        m((void **)&t_off, (max_rec + 1) * 8);
+        m((void **)&t_start, max_rec * 4);
+        m((void **)&t_end, max_rec * 4);
+        m((void **)&t_len, (max_rec + 1) * 4);
+        m((void **)&t_cnt, pa::kTrimCounters * 8);
+        return e;
+    }
     void release() {
         pa::dev_free(seq); pa::dev_free(qual); pa::dev_free(tile_cnt); pa::dev_free(nl); pa::dev_free(len); pa::dev_free(tile_off);
         pa::dev_free(bsum); pa::dev_free(rec_off); pa::dev_free(ids); pa::dev_free(tot); pa::dev_free(meta);
+        pa::dev_free(t_seq); pa::dev_free(t_qual); pa::dev_free(t_off); pa::dev_free(t_start); pa::dev_free(t_end);
+        pa::dev_free(t_len); pa::dev_free(t_cnt);
         hipHostFree(h_meta);
         *this = ParseBufs{};
     }
@@ -431,7 +452,7 @@ struct WindowOut {
 // its bytes (a second one).
 pa_status parse_align_window(ParseBufs &B, const uint8_t *D, uint64_t lo, uint64_t hi, bool last, pa_index *idx,
                              const DevParams &prm, uint64_t base, pa_result *acc, hipStream_t st, WindowOut &out,
-                             double *t_meta, double *t_rec, Extract *ex = nullptr) {
+                             double *t_meta, double *t_rec, Extract *ex = nullptr, StreamTrim trim = StreamTrim{}) {
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
         return std::chrono::duration<double, std::milli>(b - a).count();
@@ -472,7 +493,7 @@ pa_status parse_align_window(ParseBufs &B, const uint8_t *D, uint64_t lo, uint64
     PA_HIP(hipGetLastError());
     PA_HIP(hipMemcpyAsync(B.h_meta, B.meta, sizeof(Meta), hipMemcpyDeviceToHost, st));
     unsigned long long n_bases = 0;  // (the length scan's total; only the extraction asks for it)
-    if (ex) PA_HIP(hipMemcpyAsync(&n_bases, B.tot, 8, hipMemcpyDeviceToHost, st));
+    if (ex || trim.spec) PA_HIP(hipMemcpyAsync(&n_bases, B.tot, 8, hipMemcpyDeviceToHost, st));
     tw = now();
     PA_HIP(hipStreamSynchronize(st));
     *t_rec += ms(tw, now());
@@ -490,6 +511,18 @@ pa_status parse_align_window(ParseBufs &B, const uint8_t *D, uint64_t lo, uint64
     r.off = (uint64_t *)B.rec_off;
     r.q_min = 255 - (int32_t)B.h_meta->q_low;  // (over the file so far: <= this window's smallest byte)
     r.len_min = 1;                              // (the grammar: a non-empty sequence)
+    if (trim.spec) {  // the window's reads trimmed into the second pair of columns: all below see those
+        Bufs b(st);
+        TrimOut to;
+        PA_TRY(trim_device(&r, n_bases, *trim.spec, B.t_start, B.t_end, B.t_len, B.t_seq, B.t_qual, B.t_off, B.t_cnt, b,
+                           trim.stats, &to, st));
+        r.seq = B.t_seq;
+        r.qual = B.t_qual;
+        r.off = B.t_off;
+        r.n_bases = to.n_bases;
+        r.max_len = to.max_len;
+        r.len_min = to.len_min;  // (q_min stays a lower bound)
+    }
     if (acc) PA_TRY(align(idx, &r, prm, base, acc, st));
     // the selected records of the window, classified, gathered and written (pa_extract.hip)
     if (ex) PA_TRY(extract_window(*ex, idx, &r, prm, D, t0, lo, hi, B.nl, st));
@@ -755,7 +788,7 @@ void fastq_prefetch_free(pa_fastq_prefetch *pf) {
 // window's bytes are on the device: no carries (the text is contiguous), the
 // index's align-side view made while the copies run.
 pa_status align_fastq_prefetched(pa_index *idx, pa_fastq_prefetch *pf, const DevParams &prm, uint64_t base,
-                                 pa_result *acc, hipStream_t st, uint64_t *n_reads) {
+                                 pa_result *acc, hipStream_t st, uint64_t *n_reads, StreamTrim trim) {
     const bool timing = pa::env_is("PA_STREAM_TIMING", '1');
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
@@ -782,7 +815,8 @@ pa_status align_fastq_prefetched(pa_index *idx, pa_fastq_prefetch *pf, const Dev
     {  // (the parse buffers exist once a byte is on the device, or the thread is done)
         const pa_status rc = wait_for(1);
         if (rc == PA_EUNSUPPORTED)  // not prefetched (too large): the windowed stream
-            return align_fastq_file(idx, pf->path.c_str(), prm, base, acc, pf->threads, pf->window, st, n_reads);
+            return align_fastq_file(idx, pf->path.c_str(), prm, base, acc, pf->threads, pf->window, st, n_reads, 0,
+                                    ~0ull, nullptr, nullptr, -1, nullptr, trim);
         PA_TRY(rc);
     }
     {  // the align-side view, for the reads this file holds (a file of few reads skips the neighbour bits)
@@ -793,6 +827,7 @@ pa_status align_fastq_prefetched(pa_index *idx, pa_fastq_prefetch *pf, const Dev
     PA_TRY(reserve_queues(idx, pf->bufs.max_rec));
     // the parse stream must see the prefetch thread's allocations and memsets
     PA_HIP(hipStreamSynchronize(pf->st));
+    if (trim.spec && !pf->bufs.t_seq) PA_HIP(pf->bufs.alloc_trim(pf->window + 16));  // (freed with the prefetch)
     uint64_t lo = 0, records = 0;
     bool fail = pf->size == 0;
     while (!fail) {
@@ -801,7 +836,7 @@ pa_status align_fastq_prefetched(pa_index *idx, pa_fastq_prefetch *pf, const Dev
         const bool last = hi == pf->size;
         WindowOut w;
         PA_TRY(parse_align_window(pf->bufs, pf->text, lo, hi, last, idx, prm, base + records, acc, st, w, &t_meta,
-                                  &t_rec));
+                                  &t_rec, nullptr, trim));
         if (w.fail) {
             fail = true;
             break;
@@ -826,7 +861,7 @@ pa_status align_fastq_prefetched(pa_index *idx, pa_fastq_prefetch *pf, const Dev
 pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm, uint64_t base, pa_result *acc,
                            int threads, uint64_t window, hipStream_t st, uint64_t *n_reads, uint64_t offset,
                            uint64_t length, std::vector<uint64_t> *ids_out, const pa_extract_spec *extract, int out_fd,
-                           pa_extract_stats *extract_stats) {
+                           pa_extract_stats *extract_stats, StreamTrim trim) {
     ErrOp op(extract ? "pa_extract_fastq_file" : "pa_align_fastq_file");
     // PA_STREAM_TIMING=1: where the time goes (stderr)
     const bool timing = pa::env_is("PA_STREAM_TIMING", '1');
@@ -910,6 +945,7 @@ pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm
         PA_HIP(hipEventCreateWithFlags(&ev_carry[i], hipEventDisableTiming));
     }
     PA_HIP(B.alloc(kCarryMax + W, est_rec, st));
+    if (trim.spec) PA_HIP(B.alloc_trim(kCarryMax + W));
     if (extract) PA_TRY(extract_open(ex, idx, extract, out_fd, kCarryMax + W, extract_stats, st));
     PA_HIP(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
     t_alloc = ms(t_start, now());
@@ -949,7 +985,7 @@ pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm
         if (hi == lo) break;  // (an empty last window: nothing after the previous records)
         WindowOut w;
         rc = parse_align_window(B, D[cur], lo, hi, last, idx, prm, base + records, acc, st, w, &t_wait_meta,
-                                &t_wait_rec, extract ? &ex : nullptr);
+                                &t_wait_rec, extract ? &ex : nullptr, trim);
         if (rc != PA_OK) break;
         // (a record longer than the carry limit is left to the host parser too)
         if (w.fail || (!last && hi - w.end > kCarryMax)) {

@@ -611,6 +611,40 @@ pa_status align_pairs(pa_index *idx, const pa_reads *m1, const pa_reads *m2, con
                       pa_result *acc, uint8_t *type, uint32_t *qf, uint32_t *hr, uint64_t *list_off, uint32_t *lists,
                       uint64_t list_cap, uint64_t *list_total, uint64_t *exact_pairs, hipStream_t st);
 pa_status reads_measure(pa_reads *r, hipStream_t st);  // q_min / len_min of a batch (at its creation)
+// read trimming (pa_trim.hip)
+struct TrimSpec {  // a checked pa_trim_spec as the kernel takes it
+    uint32_t flags, q3, q5, alen, min_ov, permille;
+    uint64_t a0, a1;  // the adapter's two code bit planes, base j at bit j
+};
+struct TrimOut {  // what the trimmed batch's pa_reads needs
+    uint64_t n_bases = 0;
+    uint32_t max_len = 0;
+    int64_t len_min = 0;
+};
+// The one place pa_trim_stats are summed: dst += src.
+inline void trim_stats_add(pa_trim_stats *dst, const pa_trim_stats &src) {
+    dst->reads += src.reads;
+    dst->bases_in += src.bases_in;
+    dst->bases_out += src.bases_out;
+    dst->reads_trimmed += src.reads_trimmed;
+    dst->reads_quality += src.reads_quality;
+    dst->bases_quality += src.bases_quality;
+    dst->reads_adapter += src.reads_adapter;
+    dst->bases_adapter += src.bases_adapter;
+    dst->reads_empty += src.reads_empty;
+}
+constexpr int kTrimCounters = 11;  // pa_trim_stats' nine, the longest and the shortest new read
+pa_status trim_spec_check(const pa_trim_spec *spec, TrimSpec *out);
+pa_status trim_device(const pa_reads *in, uint64_t in_bases, const TrimSpec &t, uint32_t *d_start, uint32_t *d_end,
+                      uint32_t *d_len, uint8_t *o_seq, uint8_t *o_qual, uint64_t *o_off, unsigned long long *d_cnt,
+                      Bufs &b, pa_trim_stats *stats, TrimOut *out, hipStream_t st);
+pa_status reads_trim(const pa_reads *in, const TrimSpec &t, pa_reads *out, uint32_t *start, uint32_t *end,
+                     pa_trim_stats *stats, hipStream_t st);
+// a trim of the device-parsed streams (null spec: none)
+struct StreamTrim {
+    const TrimSpec *spec = nullptr;
+    pa_trim_stats *stats = nullptr;
+};
 // the filters an align of batch r applies: quality thresholds no read can fail dropped
 pa_status effective_params(const pa_reads *r, const DevParams &p, DevParams &out, hipStream_t st);
 pa_status ensure_workspace(pa_index *idx, size_t bytes);
@@ -623,7 +657,7 @@ pa_status align_fastq_file(pa_index *idx, const char *path, const DevParams &prm
                            int threads, uint64_t window, hipStream_t st, uint64_t *n_reads, uint64_t offset = 0,
                            uint64_t length = ~0ull, std::vector<uint64_t> *ids_out = nullptr,
                            const pa_extract_spec *extract = nullptr, int out_fd = -1,
-                           pa_extract_stats *extract_stats = nullptr);
+                           pa_extract_stats *extract_stats = nullptr, StreamTrim trim = StreamTrim{});
 // read extraction (pa_extract.hip): the state of one
 // pa_extract_fastq_file call -- the selection on the device, the output buffer
 // of a window (device and pinned, span + 16 bytes each) and the statistics.
@@ -650,7 +684,7 @@ pa_status idsets_disjoint(const std::vector<const std::vector<uint64_t> *> &sets
 pa_status fastq_prefetch_start(const char *path, int device, int threads, uint64_t window, pa_fastq_prefetch **out);
 void fastq_prefetch_free(pa_fastq_prefetch *pf);
 pa_status align_fastq_prefetched(pa_index *idx, pa_fastq_prefetch *pf, const DevParams &prm, uint64_t base,
-                                 pa_result *acc, hipStream_t st, uint64_t *n_reads);
+                                 pa_result *acc, hipStream_t st, uint64_t *n_reads, StreamTrim trim = StreamTrim{});
 pa_status index_dumpref(const pa_index *idx, const uint8_t *keep, const uint32_t *desc_of, uint32_t n_desc,
                         const char *const *desc_json, int fd, int threads, uint64_t *desc_unique, uint64_t *desc_multi,
                         uint64_t *desc_order, uint32_t *desc_last_genome, uint64_t *n_kmers_out, hipStream_t st);

@@ -637,16 +637,19 @@ class _FileBatch(_Batch):
     qualities) are parsed from the file only when per-read results or ids are
     asked for."""
 
-    __slots__ = ("path", "n")
+    __slots__ = ("path", "n", "trim", "device")
 
-    def __init__(self, base, path, params, mrq, n):
+    def __init__(self, base, path, params, mrq, n, trim=None, device=None):
         super().__init__(base, None, None, None, None, params, mrq)
-        self.path, self.n = path, n
+        self.path, self.n, self.trim, self.device = path, n, trim, device
 
     def load(self) -> None:
         if self.ids is None:
             from data_file import FASTAQFile
-            self.ids, self.seq, self.qual, self.off = _columnar(FASTAQFile(self.path).container)
+            ids, seq, qual, off = _columnar(FASTAQFile(self.path).container)
+            if self.trim is not None:  # (the stream aligned the trimmed reads; its statistics are counted already)
+                seq, qual, off = _trim_on_device(seq, qual, off, self.trim, None, self.device)
+            self.ids, self.seq, self.qual, self.off = ids, seq, qual, off
 
 
 EXTRACT_MAPPING_WORDS = {"filtered": 0, "unmapped": 1, "unique": 2, "ambiguous": 3}  # (word -> PA_* type value)
@@ -666,6 +669,39 @@ def extract_type_mask(mapping) -> int:
             raise ValueError(f"Unknown extract mapping {w!r} (choose from unique, ambiguous, unmapped, filtered)")
         mask |= 1 << EXTRACT_MAPPING_WORDS[w]
     return mask
+
+
+def _trim_on_device(seq, qual, off, spec: "N.TrimSpec", stats: Optional["N.TrimStats"], device, keep: bool = False):
+    """The columns of a batch trimmed by pa_reads_trim:
+    uploaded, trimmed on the device, downloaded.  ``stats`` accumulates.
+    ``keep``: the trimmed device batch is returned as a fourth value instead
+    of being freed (the caller aligns it and closes it)."""
+    reads = N.Reads.upload(seq, qual, off, device=device)
+    try:
+        out, _, _, _ = reads.trim(spec, stats=stats)
+    finally:
+        reads.close()
+    try:
+        cols = out.download()
+    except BaseException:
+        out.close()
+        raise
+    if keep:
+        return cols + (out,)
+    out.close()
+    return cols
+
+
+def _native_trim(spec) -> Optional["N.TrimSpec"]:
+    """A trim argument (a trim.Spec, an N.TrimSpec or None) as the N.TrimSpec
+    to apply, or None when it trims nothing."""
+    if spec is None:
+        return None
+    if not isinstance(spec, N.TrimSpec):
+        if not hasattr(spec, "native"):
+            raise ValueError("trim must be a trim.Spec or a pa_native.TrimSpec")
+        spec = spec.native()
+    return spec if spec.active else None
 
 
 def _dropped_mask(qual: np.ndarray, off: np.ndarray, mrq) -> np.ndarray:
@@ -722,6 +758,11 @@ _LINEAGE: "weakref.WeakKeyDictionary[PseudoAlignment, list]" = weakref.WeakKeyDi
 # like _COVERAGE and for the same reason: [accumulator or None, reads of batches
 # dropped whole on the host].
 _CONTAINMENT: "weakref.WeakKeyDictionary[PseudoAlignment, list]" = weakref.WeakKeyDictionary()
+
+# Trim state of the alignments made with trim=..., kept like _COVERAGE (an .aln
+# file holds per-read results only): [mate 1's N.TrimSpec or None, mate 2's,
+# mate 1's N.TrimStats, mate 2's].
+_TRIM: "weakref.WeakKeyDictionary[PseudoAlignment, list]" = weakref.WeakKeyDictionary()
 
 CONTAINMENT_HEADER = ("#genome\tlength\tkmers\tkmers_seen\tcontainment\tidentity\tspecific_kmers\tspecific_seen"
                       "\tspecific_containment\tspecific_hits\tduplication\n")
@@ -873,11 +914,22 @@ class PseudoAlignment:
     those batches marks its k-mer of the index, and ``get_containment`` /
     ``write_containment`` report, per genome, how many of its distinct k-mers
     the reads hold; with ``lineages`` the lineage report gains the same per
-    clade."""
+    clade.
+
+    ``trim=spec`` (not in the reference either; a ``trim.Spec``): every read is
+    trimmed on the device before anything else sees it -- quality ends, then a
+    3' adapter -- and ``reads``, the counters and every accumulator are those of
+    the trimmed reads; ``trim2`` is the spec of the second mates of a paired job
+    (default: ``trim``); ``get_trim_stats`` reports what was cut (DESIGN.md
+    section 22)."""
 
     def __init__(self, kmer_reference: KmerReference, coverage: bool = False, pileup: bool = False,
                  min_base_quality: Optional[int] = None, abundance: bool = False,
-                 lineages: Optional[Lineages] = None, containment: bool = False) -> None:
+                 lineages: Optional[Lineages] = None, containment: bool = False, trim=None, trim2=None) -> None:
+        t1 = _native_trim(trim)
+        t2 = t1 if trim2 is None else _native_trim(trim2)
+        if t1 is not None or t2 is not None:
+            _TRIM[self] = [t1, t2, N.TrimStats(), N.TrimStats()]
         if containment:
             _CONTAINMENT[self] = [None, 0]  # (the accumulator is made with the first batch)
         if lineages is not None:
@@ -937,6 +989,34 @@ class PseudoAlignment:
             if not unique_batch:
                 seen.add(rid)
 
+    def _trim_stats_of(self, mate: int) -> Optional["N.TrimStats"]:
+        t = _TRIM.get(self)
+        return None if t is None else t[1 + mate]
+
+    def _trim_spec(self, mate: int = 1) -> Optional["N.TrimSpec"]:
+        t = _TRIM.get(self)
+        return None if t is None else t[mate - 1]
+
+    def _trimmed(self, seq, qual, off, mate: int = 1):
+        """The columns as the rest of the alignment sees them: trimmed on the
+        device when mate ``mate`` has a trim spec, else as given."""
+        spec = self._trim_spec(mate)
+        if spec is None:
+            return seq, qual, off
+        return _trim_on_device(seq, qual, off, spec, _TRIM[self][1 + mate], self.kmer_reference.index.device)
+
+    def get_trim_stats(self, mate: Optional[int] = None) -> Optional[Dict[str, int]]:
+        """What the trim cut off so far (pa_trim_stats as a dict): of mate 1's
+        or mate 2's reads, or of both summed (``mate`` None).  None for an
+        alignment made without ``trim``."""
+        t = _TRIM.get(self)
+        if t is None:
+            return None
+        if mate is not None:
+            return t[1 + mate].as_dict()
+        a, b = t[2].as_dict(), t[3].as_dict()
+        return {k: a[k] + b[k] for k in a}
+
     def add_read(self, read: Read) -> None:
         self._add_ids([read.identifier], None, False)
         if self._ids is not None:
@@ -985,9 +1065,11 @@ class PseudoAlignment:
             result = N.Result(ref.index)
             prm = N.Params.make(m, p, min_read_quality, min_kmer_quality, max_genomes)
             if prefetch is not None and prefetch.device == ref.index.device:
-                n = N.align_fastq_prefetched(ref.index, prefetch, prm, self._next_index, result)
+                n = N.align_fastq_prefetched(ref.index, prefetch, prm, self._next_index, result,
+                                             trim=self._trim_spec(), trim_stats=self._trim_stats_of(1))
             else:
-                n = N.align_fastq_file(ref.index, reads_file, prm, self._next_index, result)
+                n = N.align_fastq_file(ref.index, reads_file, prm, self._next_index, result,
+                                       trim=self._trim_spec(), trim_stats=self._trim_stats_of(1))
             if n is None:
                 result.close()
         if prefetch is not None:
@@ -1035,7 +1117,8 @@ class PseudoAlignment:
                 FASTAQFile.check_extension(reads_file)
                 result = N.Result(ref.index)
                 prm = N.Params.make(m, p, min_read_quality, min_kmer_quality, max_genomes)
-                n, stats = N.extract_fastq_file(ref.index, reads_file, prm, spec, fh.fileno(), self._next_index, result)
+                n, stats = N.extract_fastq_file(ref.index, reads_file, prm, spec, fh.fileno(), self._next_index, result,
+                                                trim=self._trim_spec(), trim_stats=self._trim_stats_of(1))
                 if n is not None:
                     self._adopt_streamed(result, reads_file, prm, n, min_read_quality, min_kmer_quality, max_genomes)
                     return stats
@@ -1055,7 +1138,9 @@ class PseudoAlignment:
                 types = np.zeros(n, dtype=np.uint8)
                 sel = np.full(n, bool(type_mask & 1) != bool(invert))
             else:
-                reads = N.Reads.upload(seq, qual, off, device=ref.index.device)
+                # (the selection is decided on the reads as aligned -- trimmed, when a trim is set;
+                # the records written below are the file's own)
+                reads = N.Reads.upload(batch.seq, batch.qual, batch.off, device=ref.index.device)
                 try:
                     sel = N.reads_select(ref.index, reads, batch.params, spec)
                     types = None
@@ -1095,7 +1180,8 @@ class PseudoAlignment:
         self.filtered_quality_reads += int(stats[3])
         self.filtered_quality_kmers += int(stats[4])
         self.filtered_hr_kmers += int(stats[5])
-        self._batches.append(_FileBatch(self._next_index, reads_file, prm, mrq, n))
+        self._batches.append(_FileBatch(self._next_index, reads_file, prm, mrq, n, self._trim_spec(),
+                                        self.kmer_reference.index.device))
         self._next_index += n
         self._streamed_records = n  # (diagnostics: the device-parsed path was taken)
 
@@ -1103,6 +1189,20 @@ class PseudoAlignment:
         n = len(ids)
         if n == 0:
             return
+        trimmed = None  # (the trimmed batch on the device: aligned below as it is, not uploaded again)
+        if self._trim_spec() is not None:
+            seq, qual, off, trimmed = _trim_on_device(seq, qual, off, self._trim_spec(), self._trim_stats_of(1),
+                                                      self.kmer_reference.index.device, keep=True)
+        try:  # (all below sees the trimmed reads)
+            self._align_trimmed_columns(ids, seq, qual, off, m, p, mrq, mkq, mg, unique_batch, trimmed)
+        finally:
+            if trimmed is not None:
+                trimmed.close()
+
+    def _align_trimmed_columns(self, ids, seq, qual, off, m, p, mrq, mkq, mg, unique_batch, on_device) -> None:
+        """_align_columns after its trim (the columns as given when none is set).
+        ``on_device``: the same columns as a device batch already, or None."""
+        n = len(ids)
         if mrq is not None:
             self.filter_read_quality_flag = True
         if mkq is not None:
@@ -1140,7 +1240,7 @@ class PseudoAlignment:
             # the align-side view this batch repays (the neighbour bits only
             # past their break-even in reads per genome base; pa_index_prepare_ex)
             ref.index.prepare(expected_reads=n)
-            reads = N.Reads.upload(seq, qual, off, device=ref.index.device)
+            reads = on_device if on_device is not None else N.Reads.upload(seq, qual, off, device=ref.index.device)
             N.align(ref.index, reads, prm, self._next_index, self._result)
             stats, _, _, _ = self._result.fetch()
             if self in _COVERAGE:
@@ -1192,6 +1292,8 @@ class PseudoAlignment:
         if n == 0:
             return
         ids = [pair_identifier(a, b) for a, b in zip(ids1, ids2)]
+        seq1, qual1, off1 = self._trimmed(seq1, qual1, off1, 1)  # (each mate by its own spec)
+        seq2, qual2, off2 = self._trimmed(seq2, qual2, off2, 2)
         mrq, mkq, mg = min_read_quality, min_kmer_quality, max_genomes
         if mrq is not None:
             self.filter_read_quality_flag = True

@@ -13,6 +13,8 @@
                     [--lineages FILE [--lineage-report FILE]]
                     [--containment FILE]
                     [--extract FILE [--extract-mapping LIST] [--extract-genomes a,b] [--extract-invert]]
+                    [--trim-quality Q] [--trim-quality5 Q] [--trim-adapter SEQ] [--trim-adapter2 SEQ]
+                    [--trim-min-overlap N] [--trim-error-rate X] [--trim-report FILE]
 
 Same tasks (reference | dumpref | align | dumpalign), flags, flag-combination
 checks, default coercions and error exits as src/main.py:61-402:
@@ -237,6 +239,7 @@ from constants import DEFAULT_AMBIGUOUS_THRESHOLD, DEFAULT_SIMILARITY_THRESHOLD,
 from data_file import FASTAFile, FASTAQFile, InvalidExtensionError, NoRecordsInDataFile
 from kmer import (AddingExistingRead, KmerReference, NotValidatingUniqueMapping, PseudoAlignment,
                   extract_type_mask)
+import trim as trimming
 
 _TIMING = os.environ.get("PA_CLI_TIMING") == "1"  # stage times on stderr (diagnostic)
 
@@ -338,6 +341,20 @@ def parse_arguments(args: Optional[List[str]] = None) -> argparse.Namespace:
     parser.add_argument("--extract-genomes", default=None,
                         help="comma-separated genome identifiers: select only mapped reads that name one of them")
     parser.add_argument("--extract-invert", action="store_true", help="select every read the selection leaves out")
+    # not in the reference: the reads trimmed on the device before anything else sees them, align / dumpalign with --reads
+    parser.add_argument("--trim-quality", type=int, default=None, metavar="Q",
+                        help="cut the 3' end where the qualities fall below Q (a raw quality byte, as --min-read-quality)")
+    parser.add_argument("--trim-quality5", type=int, default=None, metavar="Q", help="the same for the 5' end")
+    parser.add_argument("--trim-adapter", default=None, metavar="SEQ",
+                        help="cut a 3' adapter (1 .. 64 letters of ACGT) and everything after it")
+    parser.add_argument("--trim-adapter2", default=None, metavar="SEQ",
+                        help="the adapter of the second mates (--reads2; default: --trim-adapter's)")
+    parser.add_argument("--trim-min-overlap", type=int, default=None, metavar="N",
+                        help="bases of the adapter a read's end must hold (default: 3)")
+    parser.add_argument("--trim-error-rate", type=float, default=None, metavar="X",
+                        help="mismatches allowed per compared base, 0 .. 0.5 (default: 0.1)")
+    parser.add_argument("--trim-report", default=None, metavar="FILE",
+                        help="write the trim statistics (reads and bases in, out and cut) to FILE")
     return parser.parse_args(args)
 
 
@@ -415,7 +432,7 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
                                     coverage: bool = False, assignments: bool = False,
                                     pileup: bool = False, min_base_quality=None,
                                     abundance: bool = False, lineages=None, extract=None,
-                                    containment: bool = False) -> PseudoAlignment:
+                                    containment: bool = False, trim=None) -> PseudoAlignment:
     # the FASTQ file goes straight to the device (parsed there, aligned in
     # windows); a file outside that subset of the grammar is parsed the exact
     # way (FASTAQFile), which also raises the reference's errors.  per_read
@@ -430,9 +447,10 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
     # lineages: likewise (its pass is the candidate pass); the tree is made over the index's genomes, now,
     # so that a genome without a lineage ends the job before a read is aligned
     # containment: likewise (the mark pass takes the read columns)
+    # trim: every path below trims first -- the stream per window, the host-parsed ones per batch
     alignment = (PseudoAlignment(kmer_reference, coverage=coverage, pileup=pileup, min_base_quality=min_base_quality,
-                                 abundance=abundance, lineages=lineages, containment=containment)
-                 if coverage or pileup or abundance or lineages is not None or containment
+                                 abundance=abundance, lineages=lineages, containment=containment, trim=trim)
+                 if coverage or pileup or abundance or lineages is not None or containment or trim is not None
                  else PseudoAlignment(kmer_reference))
     if lineages is not None:
         try:
@@ -460,12 +478,13 @@ def create_alignment_from_reference(kmer_reference: KmerReference, reads_file: s
 
 
 def create_alignment_from_pairs(kmer_reference: KmerReference, reads_file: str, reads2_file: str, m: int, p: int,
-                                min_read_quality, min_kmer_quality, max_genomes) -> PseudoAlignment:
+                                min_read_quality, min_kmer_quality, max_genomes, trim=(None, None)) -> PseudoAlignment:
     # a paired job: both files parsed on the host, one device, one entry per pair
     FASTAQFile.check_extension(reads_file)
     FASTAQFile.check_extension(reads2_file)
     _stage("reference built")
-    alignment = PseudoAlignment(kmer_reference)
+    alignment = (PseudoAlignment(kmer_reference) if trim == (None, None)
+                 else PseudoAlignment(kmer_reference, trim=trim[0], trim2=trim[1] or trimming.Spec()))
     try:
         alignment.align_pairs_from_containers(FASTAQFile(reads_file).container, FASTAQFile(reads2_file).container,
                                               m, p, min_read_quality, min_kmer_quality, max_genomes)
@@ -495,6 +514,39 @@ def _extract_job(args: argparse.Namespace):
     genomes = None if args.extract_genomes is None else [x for x in args.extract_genomes.split(",") if x]
     return (args.extract, "unique,ambiguous" if args.extract_mapping is None else args.extract_mapping, genomes,
             args.extract_invert)
+
+
+_TRIM_WHAT = "--trim-quality, --trim-quality5, --trim-adapter or --trim-adapter2"
+
+
+def _trim_specs(args: argparse.Namespace):
+    """(mate 1's trim.Spec, mate 2's) of the --trim-* flags, each None when it
+    trims nothing; ValueError for an adapter or a number out of range."""
+    if (args.trim_quality is None and args.trim_quality5 is None and args.trim_adapter is None
+            and args.trim_adapter2 is None):
+        return None, None
+    overlap = trimming.DEFAULT_MIN_OVERLAP if args.trim_min_overlap is None else args.trim_min_overlap
+    permille = trimming.DEFAULT_ERROR_PERMILLE
+    if args.trim_error_rate is not None:
+        if not 0 <= args.trim_error_rate <= 0.5:  # (false for NaN too)
+            raise ValueError("the trim error rate must be between 0 and 0.5")
+        permille = int(round(1000 * args.trim_error_rate))
+    specs = []
+    for adapter in (args.trim_adapter, args.trim_adapter if args.trim_adapter2 is None else args.trim_adapter2):
+        spec = trimming.Spec(args.trim_quality, args.trim_quality5, adapter, overlap, permille)
+        specs.append(spec if spec.active else None)
+    return specs[0], specs[1]
+
+
+def _write_trim_report(alignment: PseudoAlignment, args: argparse.Namespace) -> None:
+    """--trim-report: one line of values, a second one for the second mates of a paired job."""
+    if args.trim_report is None:
+        return
+    stats = [alignment.get_trim_stats(1) or trimming.new_stats()]
+    if args.reads2 is not None:
+        stats.append(alignment.get_trim_stats(2) or trimming.new_stats())
+    with open(args.trim_report, "w") as fh:
+        fh.write(trimming.report_text(stats))
 
 
 def _print_json(obj) -> None:
@@ -614,6 +666,23 @@ def _check_task(args: argparse.Namespace) -> None:
                 os.path.abspath(args.extract) == os.path.abspath(args.reads)):
             sys.exit("Error: --extract FILE is the --reads file.")
         validate_file_writable(args.extract, "Extract output")
+    trim_flag = (args.trim_quality is not None or args.trim_quality5 is not None or args.trim_adapter is not None
+                 or args.trim_adapter2 is not None)
+    if not trim_flag and (args.trim_min_overlap is not None or args.trim_error_rate is not None):
+        sys.exit(f"Error: --trim-min-overlap and --trim-error-rate need {_TRIM_WHAT}.")
+    if not trim_flag and args.trim_report is not None:
+        sys.exit(f"Error: --trim-report needs {_TRIM_WHAT}.")
+    if trim_flag:
+        if args.task not in ("align", "dumpalign") or not args.reads:
+            sys.exit("Error: the --trim-* flags are only allowed for tasks 'align' and 'dumpalign' with --reads.")
+        if args.trim_adapter2 is not None and args.reads2 is None:
+            sys.exit("Error: --trim-adapter2 needs --reads2 (the second mates' file).")
+        try:
+            _trim_specs(args)
+        except ValueError as err:
+            sys.exit(f"Error: {err}.")
+        if args.trim_report is not None:
+            validate_file_writable(args.trim_report, "Trim report output")
     if args.task == "reference":
         if extra:
             sys.exit("Error: For task 'reference', only -g, -k, -r, --filter-similar, and --similarity-threshold "
@@ -694,11 +763,13 @@ def _print_alignment(alignment: PseudoAlignment, args: argparse.Namespace) -> No
     if args.containment is not None:
         with open(args.containment, "w") as fh:
             alignment.write_containment(fh)
+    _write_trim_report(alignment, args)
 
 
 def _run(args: argparse.Namespace) -> None:
     filt = (args.unique_threshold, args.ambiguous_threhold, args.min_read_quality, args.min_kmer_quality,
             args.max_genomes)
+    trim = _trim_specs(args)
     if args.task == "reference":
         validate_file_readable(args.genomefile, "Genome FASTA")
         validate_file_writable(args.referencefile, "Reference database output")
@@ -730,9 +801,13 @@ def _run(args: argparse.Namespace) -> None:
             ref.save(args.referencefile)
         if args.reads2 is not None:
             validate_file_readable(args.reads2, "FASTQ second-mate reads")
-            create_alignment_from_pairs(ref, args.reads, args.reads2, *filt).save(args.alignfile)
+            alignment = create_alignment_from_pairs(ref, args.reads, args.reads2, *filt, trim=trim)
+            alignment.save(args.alignfile)
+            _write_trim_report(alignment, args)
             return
-        create_alignment_from_reference(ref, args.reads, *filt, per_read=True).save(args.alignfile)
+        alignment = create_alignment_from_reference(ref, args.reads, *filt, per_read=True, trim=trim[0])
+        alignment.save(args.alignfile)
+        _write_trim_report(alignment, args)
     elif args.task == "dumpalign":
         if args.referencefile and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
@@ -740,7 +815,7 @@ def _run(args: argparse.Namespace) -> None:
                 validate_file_readable(args.reads2, "FASTQ second-mate reads")
                 ref = _load_reference(args.referencefile)
                 _check_strands(args, ref)
-                _print_alignment(create_alignment_from_pairs(ref, args.reads, args.reads2, *filt), args)
+                _print_alignment(create_alignment_from_pairs(ref, args.reads, args.reads2, *filt, trim=trim), args)
                 return
             host_parsed = (args.coverage or args.assignments is not None or args.variants is not None
                            or args.abundance is not None or args.lineages is not None
@@ -756,7 +831,8 @@ def _run(args: argparse.Namespace) -> None:
                                                              abundance=args.abundance is not None,
                                                              lineages=_load_lineages(args),
                                                              extract=_extract_job(args),
-                                                             containment=args.containment is not None), args)
+                                                             containment=args.containment is not None,
+                                                             trim=trim[0]), args)
         elif args.genomefile and args.kmer_size and args.reads:
             validate_file_readable(args.reads, "FASTQ reads")
             validate_file_readable(args.genomefile, "Genome FASTA")
@@ -765,7 +841,7 @@ def _run(args: argparse.Namespace) -> None:
                 ref = create_reference(args.genomefile, args.kmer_size, args.filter_similar,
                                        args.similarity_threshold, reads_file=args.reads,
                                        both_strands=args.both_strands)
-                _print_alignment(create_alignment_from_pairs(ref, args.reads, args.reads2, *filt), args)
+                _print_alignment(create_alignment_from_pairs(ref, args.reads, args.reads2, *filt, trim=trim), args)
                 return
             # (a coverage job runs on one device: the depth arrays of read shards are not reduced;
             # an assignments job too: its lines come from one host-parsed batch; a pileup job and an
@@ -774,7 +850,9 @@ def _run(args: argparse.Namespace) -> None:
                            or args.abundance is not None or args.lineages is not None
                            or args.containment is not None)
             # (an extract job too: its output is written by one device, window after window)
-            sharded = None if host_parsed or args.extract is not None else _dumpalign_sharded(args, filt)
+            # (and a job with trim flags: the byte-range shards have no trimming form)
+            sharded = (None if host_parsed or args.extract is not None or trim != (None, None)
+                       else _dumpalign_sharded(args, filt))
             if sharded is not None:
                 _print_json(sharded.get_summary())
                 return
@@ -789,7 +867,8 @@ def _run(args: argparse.Namespace) -> None:
                                                              abundance=args.abundance is not None,
                                                              lineages=_load_lineages(args),
                                                              extract=_extract_job(args),
-                                                             containment=args.containment is not None), args)
+                                                             containment=args.containment is not None,
+                                                             trim=trim[0]), args)
         elif args.alignfile:
             validate_file_readable(args.alignfile, "Alignment output")
             try:

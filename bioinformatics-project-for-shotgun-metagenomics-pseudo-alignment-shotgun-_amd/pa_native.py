@@ -46,12 +46,13 @@ EXPORTS = (
     "pa_index_positions",
     "pa_index_extsim_stats", "pa_index_dumpref",
     "pa_reads_upload", "pa_reads_synthesize", "pa_reads_synthesize_mix", "pa_reads_info", "pa_params_effective",
-    "pa_reads_download", "pa_reads_free",
+    "pa_reads_download", "pa_reads_free", "pa_reads_trim",
     "pa_result_create", "pa_result_reset", "pa_result_fetch", "pa_result_device_view", "pa_result_copy_out",
     "pa_result_copy_in", "pa_result_load", "pa_result_free",
     "pa_align", "pa_align_detail", "pa_align_reads", "pa_align_pairs", "pa_align_batch", "pa_align_fastq_file", "pa_align_fastq_range",
     "pa_idsets_disjoint", "pa_idset_free", "pa_reads_select", "pa_extract_fastq_file",
     "pa_fastq_prefetch_start", "pa_align_fastq_prefetched", "pa_fastq_prefetch_free",
+    "pa_align_fastq_file_ex", "pa_align_fastq_prefetched_ex", "pa_extract_fastq_file_ex",
     "pa_comm_unique_id", "pa_comm_init", "pa_comm_free", "pa_comm_count", "pa_counters_reduce",
     "pa_index_prepare_coverage", "pa_coverage_create", "pa_coverage_reset", "pa_coverage_add", "pa_coverage_summary",
     "pa_coverage_depth", "pa_coverage_free", "pa_align_placements",
@@ -141,6 +142,57 @@ class ExtractStats(ctypes.Structure):
                 "selected_by_type": {n: int(self.selected_by_type[i]) for i, n in enumerate(EXTRACT_TYPE_NAMES)}}
 
 
+PA_TRIM_MAX_ADAPTER = 64
+PA_TRIM_QUALITY3, PA_TRIM_QUALITY5, PA_TRIM_ADAPTER = 1, 2, 4
+TRIM_STAT_NAMES = ("reads", "bases_in", "bases_out", "reads_trimmed", "reads_quality", "bases_quality",
+                   "reads_adapter", "bases_adapter", "reads_empty")
+
+
+class TrimSpec(ctypes.Structure):
+    """pa_trim_spec: quality cutoffs are raw quality
+    bytes; ``make`` sets the flag of every part that is given.  The library
+    checks the values (ValueError)."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("flags", "quality3", "quality5", "adapter_len", "min_overlap",
+                                               "max_error_permille")] + [("adapter", ctypes.c_char * PA_TRIM_MAX_ADAPTER)]
+
+    @classmethod
+    def make(cls, quality3: Optional[int] = None, quality5: Optional[int] = None, adapter: Optional[str] = None,
+             min_overlap: int = 3, max_error_permille: int = 100) -> "TrimSpec":
+        def u32(v, what):
+            v = int(v)
+            if not 0 <= v < 2 ** 32:
+                raise ValueError(f"pa_trim_spec: {what} out of range")
+            return v
+        a = b"" if adapter is None else (adapter if isinstance(adapter, bytes) else str(adapter).encode("latin-1"))
+        flags = ((PA_TRIM_QUALITY3 if quality3 is not None else 0) | (PA_TRIM_QUALITY5 if quality5 is not None else 0)
+                 | (PA_TRIM_ADAPTER if adapter is not None else 0))
+        if len(a) > PA_TRIM_MAX_ADAPTER:
+            raise ValueError("pa_trim_spec: adapter_len must be 1 .. PA_TRIM_MAX_ADAPTER")
+        spec = cls(flags, u32(quality3 or 0, "quality3"), u32(quality5 or 0, "quality5"), len(a),
+                   u32(min_overlap, "min_overlap"), u32(max_error_permille, "max_error_permille"))
+        ctypes.memmove(ctypes.addressof(spec) + cls.adapter.offset, a, len(a))  # (no terminator: 64 bytes fit)
+        return spec
+
+    @property
+    def active(self) -> bool:
+        return self.flags != 0
+
+
+class TrimStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in TRIM_STAT_NAMES]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n in TRIM_STAT_NAMES}
+
+    def add(self, other: "TrimStats") -> None:
+        for n in TRIM_STAT_NAMES:
+            setattr(self, n, int(getattr(self, n)) + int(getattr(other, n)))
+
+
+class FastqOpts(ctypes.Structure):
+    _fields_ = [("trim", ctypes.POINTER(TrimSpec)), ("trim_stats", ctypes.POINTER(TrimStats))]
+
+
 # pa_variant, one record of Pileup.variants (40 bytes, no implicit padding)
 VARIANT_DTYPE = np.dtype([("genome", "<u4"), ("ref", "u1"), ("alt", "u1"), ("pad", "u1", (2,)), ("position", "<u8"),
                           ("depth", "<u4"), ("alt_count", "<u4"), ("acgt", "<u4", (4,))])
@@ -198,6 +250,7 @@ def lib():
         "pa_params_effective": (I32, [P, ctypes.POINTER(Params), ctypes.POINTER(Params), ctypes.POINTER(I32), P]),
         "pa_reads_download": (I32, [P, U64, U64, P, P, P, P]),
         "pa_reads_free": (None, [P]),
+        "pa_reads_trim": (I32, [P, ctypes.POINTER(TrimSpec), PP, P, P, ctypes.POINTER(TrimStats), P]),
         "pa_result_create": (I32, [P, PP]),
         "pa_result_reset": (I32, [P, P]),
         "pa_result_fetch": (I32, [P, ctypes.POINTER(Stats), P, P, P, P]),
@@ -222,6 +275,13 @@ def lib():
         "pa_fastq_prefetch_start": (I32, [ctypes.c_char_p, I32, I32, U64, PP]),
         "pa_align_fastq_prefetched": (I32, [P, P, ctypes.POINTER(Params), U64, P, P, ctypes.POINTER(U64)]),
         "pa_fastq_prefetch_free": (None, [P]),
+        "pa_align_fastq_file_ex": (I32, [P, ctypes.c_char_p, ctypes.POINTER(Params), U64, P, I32, U64, P,
+                                         ctypes.POINTER(U64), ctypes.POINTER(FastqOpts)]),
+        "pa_align_fastq_prefetched_ex": (I32, [P, P, ctypes.POINTER(Params), U64, P, P, ctypes.POINTER(U64),
+                                               ctypes.POINTER(FastqOpts)]),
+        "pa_extract_fastq_file_ex": (I32, [P, ctypes.c_char_p, ctypes.POINTER(Params), ctypes.POINTER(ExtractSpec),
+                                           I32, U64, P, I32, U64, P, ctypes.POINTER(ExtractStats),
+                                           ctypes.POINTER(FastqOpts)]),
         "pa_comm_unique_id": (I32, [P]),
         "pa_comm_init": (I32, [I32, I32, I32, P, PP]),
         "pa_comm_free": (I32, [P]),
@@ -745,6 +805,20 @@ class Reads:
         _check(lib().pa_reads_download(self._h, first, count, _ptr(seq), _ptr(qual), _ptr(off), None))
         return seq[:nb], qual[:nb], off
 
+    def trim(self, spec: "TrimSpec", stream=None, stats: Optional["TrimStats"] = None):
+        """pa_reads_trim: (the trimmed batch, start, end, this call's statistics
+        as a dict); start / end in the original reads' coordinates.  ``stats``
+        accumulates when given."""
+        h = P()
+        start = np.zeros(self.n, dtype=np.uint32)
+        end = np.zeros(self.n, dtype=np.uint32)
+        mine = TrimStats()
+        _check(lib().pa_reads_trim(self._h, ctypes.byref(spec), ctypes.byref(h), _ptr(start), _ptr(end),
+                                   ctypes.byref(mine), _stream(stream)))
+        if stats is not None:
+            stats.add(mine)
+        return Reads(h, self.device), start, end, mine.as_dict()
+
     @property
     def handle(self):
         return self._h
@@ -871,22 +945,37 @@ def align(index: Index, reads: Reads, params: Params, read_index_base: int, resu
                           _stream(stream)))
 
 
+def _fastq_opts(trim: Optional["TrimSpec"]):
+    """(pa_fastq_opts of a trimming stream call, the call's own statistics)."""
+    mine = TrimStats()
+    return FastqOpts(ctypes.pointer(trim), ctypes.pointer(mine)), mine
+
+
 def align_fastq_file(index: Index, path: str, params: Params, read_index_base: int, result: Result,
-                     threads: Optional[int] = None, window_bytes: int = 0, stream=None) -> Optional[int]:
+                     threads: Optional[int] = None, window_bytes: int = 0, stream=None,
+                     trim: Optional["TrimSpec"] = None, trim_stats: Optional["TrimStats"] = None) -> Optional[int]:
     """pa_align_fastq_file: the FASTQ file parsed on the device and aligned in
     windows; returns the number of records, or None when the file is outside
     the device-parsed subset of the grammar (``result`` then holds a partial
-    sum: reset it and take the exact path)."""
+    sum: reset it and take the exact path).  ``trim``: pa_align_fastq_file_ex,
+    every window's reads trimmed first; ``trim_stats`` accumulates when the
+    file was read to its end."""
     n = U64(0)
     if window_bytes <= 0:
         env = os.environ.get("PA_STREAM_WINDOW")
         window_bytes = int(env) if env and env.isdigit() else 0
-    st = lib().pa_align_fastq_file(index.handle, os.fsencode(path), ctypes.byref(params), int(read_index_base),
-                                   result.handle, int(threads or ingest_threads()), int(window_bytes),
-                                   _stream(stream), ctypes.byref(n))
+    args = (index.handle, os.fsencode(path), ctypes.byref(params), int(read_index_base), result.handle,
+            int(threads or ingest_threads()), int(window_bytes), _stream(stream), ctypes.byref(n))
+    if trim is None:
+        st = lib().pa_align_fastq_file(*args)
+    else:
+        opts, mine = _fastq_opts(trim)
+        st = lib().pa_align_fastq_file_ex(*args, ctypes.byref(opts))
     if st == PA_ENOTCANON:
         return None
     _check(st)
+    if trim is not None and trim_stats is not None:
+        trim_stats.add(mine)
     return int(n.value)
 
 
@@ -901,23 +990,32 @@ def reads_select(index: Index, reads: Reads, params: Params, spec: ExtractSpec, 
 
 def extract_fastq_file(index: Index, path: str, params: Params, spec: ExtractSpec, out_fd: int,
                        read_index_base: int = 0, result: Optional[Result] = None, threads: Optional[int] = None,
-                       window_bytes: int = 0, stream=None) -> Tuple[Optional[int], dict]:
+                       window_bytes: int = 0, stream=None, trim: Optional["TrimSpec"] = None,
+                       trim_stats: Optional["TrimStats"] = None) -> Tuple[Optional[int], dict]:
     """pa_extract_fastq_file: the selected records of the device-parsed file
     written to ``out_fd``.  Returns (records, statistics); records is None when
     the file is outside the device-parsed subset of the grammar -- the
     statistics then say how many bytes were already written (truncate the
-    output, reset ``result`` and take the exact path)."""
+    output, reset ``result`` and take the exact path).  ``trim``:
+    pa_extract_fastq_file_ex, the selection decided on the trimmed reads, the
+    bytes written still the file's own."""
     stats = ExtractStats()
     if window_bytes <= 0:
         env = os.environ.get("PA_STREAM_WINDOW")
         window_bytes = int(env) if env and env.isdigit() else 0
-    st = lib().pa_extract_fastq_file(index.handle, os.fsencode(path), ctypes.byref(params), ctypes.byref(spec),
-                                     int(out_fd), int(read_index_base), None if result is None else result.handle,
-                                     int(threads or ingest_threads()), int(window_bytes), _stream(stream),
-                                     ctypes.byref(stats))
+    args = (index.handle, os.fsencode(path), ctypes.byref(params), ctypes.byref(spec), int(out_fd),
+            int(read_index_base), None if result is None else result.handle, int(threads or ingest_threads()),
+            int(window_bytes), _stream(stream), ctypes.byref(stats))
+    if trim is None:
+        st = lib().pa_extract_fastq_file(*args)
+    else:
+        opts, mine = _fastq_opts(trim)
+        st = lib().pa_extract_fastq_file_ex(*args, ctypes.byref(opts))
     if st == PA_ENOTCANON:
         return None, stats.as_dict()
     _check(st)
+    if trim is not None and trim_stats is not None:
+        trim_stats.add(mine)
     return int(stats.records), stats.as_dict()
 
 
@@ -1033,15 +1131,24 @@ class FastqPrefetch:
 
 
 def align_fastq_prefetched(index: Index, prefetch: FastqPrefetch, params: Params, read_index_base: int,
-                           result: Result, stream=None) -> Optional[int]:
+                           result: Result, stream=None, trim: Optional["TrimSpec"] = None,
+                           trim_stats: Optional["TrimStats"] = None) -> Optional[int]:
     """pa_align_fastq_prefetched: like align_fastq_file on a prefetched file;
-    None when the file is outside the device-parsed subset of the grammar."""
+    None when the file is outside the device-parsed subset of the grammar.
+    ``trim``: pa_align_fastq_prefetched_ex."""
     n = U64(0)
-    st = lib().pa_align_fastq_prefetched(index.handle, prefetch.handle, ctypes.byref(params), int(read_index_base),
-                                         result.handle, _stream(stream), ctypes.byref(n))
+    args = (index.handle, prefetch.handle, ctypes.byref(params), int(read_index_base), result.handle,
+            _stream(stream), ctypes.byref(n))
+    if trim is None:
+        st = lib().pa_align_fastq_prefetched(*args)
+    else:
+        opts, mine = _fastq_opts(trim)
+        st = lib().pa_align_fastq_prefetched_ex(*args, ctypes.byref(opts))
     if st == PA_ENOTCANON:
         return None
     _check(st)
+    if trim is not None and trim_stats is not None:
+        trim_stats.add(mine)
     return int(n.value)
 
 

@@ -61,6 +61,9 @@
  *   pa_extract_fastq_file    the same stream with the selected records written back out as FASTQ
  *   pa_reads_select          (--extract: host depletion, the reads of one genome, the unmapped reads);
  *                            no reference counterpart: the definition is DESIGN.md section 20
+ *   pa_reads_trim            quality ends and a 3' adapter cut off every read on the device
+ *   pa_*_fastq_*_ex          (--trim-*), for a batch and per window of the three streams above;
+ *                            no reference counterpart: the definition is DESIGN.md section 22
  *   pa_counters_reduce       the multi-GPU sum/min of PseudoAlignment counters
  *                            (read shards of one job); the
  *                            reference is single-process, so this has no
@@ -310,6 +313,44 @@ pa_status pa_params_effective(const pa_reads *reads, const pa_params *in, pa_par
 pa_status pa_reads_download(const pa_reads *reads, uint64_t first, uint64_t count, uint8_t *seq, uint8_t *qual,
                             uint64_t *read_off, void *stream);
 void pa_reads_free(pa_reads *reads);
+
+/* Read trimming: quality ends, then a 3' adapter; integers only.
+ * A read S, Q of length L becomes S[start:end], Q[start:end] (same index, nothing reordered
+ * or removed; a read trimmed to nothing is an ordinary read of length 0):
+ *   quality (BWA's running sum, both scans over the ORIGINAL read)
+ *     cut = L; s = best = 0                          with PA_TRIM_QUALITY3
+ *     for i = L-1 down to 0: s += quality3 - Q[i]; if s < 0: break; if s > best: best = s, cut = i
+ *     start = 0; s = best = 0                        with PA_TRIM_QUALITY5
+ *     for i = 0 .. L-1:      s += quality5 - Q[i]; if s < 0: break; if s > best: best = s, start = i + 1
+ *     start >= cut: the read is empty, start = end = 0
+ *   adapter A (3', Hamming distance, no indels) over R = S[start:cut] of length L'
+ *     p = 0 .. L'-1 is a hit when ov = min(L' - p, |A|) >= min_overlap and
+ *     1000 * mm <= max_error_permille * ov, mm = #{j < ov: R[p+j] != A[j]} (a read byte other
+ *     than ACGT always mismatches); the smallest hit p wins: end = start + p; no hit: end = cut
+ * Quality cutoffs are raw quality bytes, as pa_params.min_read_quality. */
+#define PA_TRIM_MAX_ADAPTER 64
+#define PA_TRIM_QUALITY3 1u
+#define PA_TRIM_QUALITY5 2u
+#define PA_TRIM_ADAPTER 4u
+typedef struct {
+    uint32_t flags, quality3, quality5, adapter_len, min_overlap, max_error_permille;
+    char adapter[PA_TRIM_MAX_ADAPTER];
+} pa_trim_spec;
+/* Sums over reads (they do not depend on batching): reads_trimmed: length changed;
+ * bases_quality: L - (cut - start), L for a read emptied by quality; bases_adapter: cut - end;
+ * reads_empty: reads of length 0 afterwards. */
+typedef struct {
+    uint64_t reads, bases_in, bases_out, reads_trimmed, reads_quality, bases_quality, reads_adapter,
+        bases_adapter, reads_empty;
+} pa_trim_stats;
+/* out: a new batch on in's device.  start / end: host [n] each, nullable, in the
+ * original read's coordinates.  stats: nullable, ACCUMULATES.  flags == 0: an
+ * identical copy.  PA_EINVAL: a NULL argument; an unknown flag; with
+ * PA_TRIM_ADAPTER an adapter byte outside ACGT, adapter_len 0 or >
+ * PA_TRIM_MAX_ADAPTER; min_overlap 0; max_error_permille > 500; a quality
+ * cutoff > 255 (the last three whatever the flags). */
+pa_status pa_reads_trim(const pa_reads *in, const pa_trim_spec *spec, pa_reads **out, uint32_t *start,
+                        uint32_t *end, pa_trim_stats *stats, void *stream);
 
 /* ---- results (PseudoAlignment counters) ------------------------------------- */
 
@@ -802,6 +843,29 @@ pa_status pa_fastq_prefetch_start(const char *path, int32_t device, int32_t thre
 pa_status pa_align_fastq_prefetched(const pa_index *idx, pa_fastq_prefetch *prefetch, const pa_params *params,
                                     uint64_t read_index_base, pa_result *acc, void *stream, uint64_t *n_reads);
 void pa_fastq_prefetch_free(pa_fastq_prefetch *prefetch);
+
+/* The three streams above with every window's reads trimmed on the device
+ * (pa_reads_trim's pass) before anything else sees them: the counters, and the
+ * selection of an extraction, are those of the trimmed reads.  An extraction
+ * still writes the ORIGINAL records, the file's own bytes.  opts NULL, or
+ * opts->trim NULL: the plain call.  trim_stats (nullable) ACCUMULATES, the
+ * whole file's sums added when the call returns PA_OK and nothing otherwise
+ * (PA_ENOTCANON at a late window leaves them as they were).  PA_EINVAL: a spec pa_reads_trim refuses.  One device: pa_align_fastq_range
+ * has no trimming form. */
+typedef struct {
+    const pa_trim_spec *trim;
+    pa_trim_stats *trim_stats;
+} pa_fastq_opts;
+pa_status pa_align_fastq_file_ex(const pa_index *idx, const char *path, const pa_params *params,
+                                 uint64_t read_index_base, pa_result *acc, int32_t threads, uint64_t window_bytes,
+                                 void *stream, uint64_t *n_reads, const pa_fastq_opts *opts);
+pa_status pa_align_fastq_prefetched_ex(const pa_index *idx, pa_fastq_prefetch *prefetch, const pa_params *params,
+                                       uint64_t read_index_base, pa_result *acc, void *stream, uint64_t *n_reads,
+                                       const pa_fastq_opts *opts);
+pa_status pa_extract_fastq_file_ex(const pa_index *idx, const char *path, const pa_params *params,
+                                   const pa_extract_spec *spec, int32_t out_fd, uint64_t read_index_base,
+                                   pa_result *acc /* nullable */, int32_t threads, uint64_t window_bytes,
+                                   void *stream, pa_extract_stats *stats, const pa_fastq_opts *opts);
 
 /* dumpref (KmerReference.get_summary, src/kmer.py:300-329; CLI src/main.py:121-158):
  * the "Kmers" object of the summary written to file descriptor fd as

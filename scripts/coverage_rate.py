@@ -8,6 +8,7 @@ genomes, k = 31, synthesized 150-bp reads, 0.5 % substitutions).
     python scripts/coverage_rate.py --mode bootstrap [--reads N] [--runs R] [--replicates B]
     python scripts/coverage_rate.py --mode lineage  [--reads N] [--runs R]
     python scripts/coverage_rate.py --mode containment [--reads N] [--runs R]
+    python scripts/coverage_rate.py --mode trim     [--reads N] [--runs R]
 
 --mode detail times one pa_align_detail call with its lists (the pass a
 coverage add rides on); run it with PA_LIBRARY=<the parent commit's libpa.so>
@@ -77,6 +78,15 @@ same call under PA_PAIR_COMBINE=0 (every pair to the pair-exact kernel),
 pa_align_reads over mates 1 plus over mates 2 (the mates' pass the call rides
 on), pa_align_detail with its lists over the 2 N mates, and the call without a
 result (the difference is k_pair_count and the fetch-free counter pass).
+
+--mode trim times pa_reads_trim next to pa_align (the
+counter pass it stands in front of) and pa_align_reads on the same batch: the
+C2 reads downloaded, given qualities and planted adapters on the host by the
+recipe of tests/test_gpu_trim.py (an eighth each: clean, dim; bad 3' tail; bad
+5' head; two eighths an adapter at a random insert, half with a substitution;
+an adapter with four substitutions; all bad) and uploaded again, so that the
+pass really trims.  With PA_TRIM_TIMING=1 the library prints the split of
+every call (bounds kernel, offset scan, gather kernel) on stderr.
 
 --read-err / --rc-rate / --foreign-rate give bench.py's c2mix reads (0.015, 0.2, 0.2).
 """
@@ -149,6 +159,49 @@ def time_assign(index, reads, prm, runs):
     N._check(st)
     med, ts = timed(lambda: N._check(call()), runs)
     return med, ts, int(total.value)
+
+
+TRUSEQ = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"
+
+
+def make_trim_batch(reads, seed=22, chunk=1_000_000):
+    """The batch's columns with the trim test's kinds of reads (read r is of kind r % 8), made chunk by
+    chunk on the host; every read keeps its length L."""
+    seq, qual, off = reads.download()
+    n, L = reads.n, reads.max_len
+    seq, qual = seq.reshape(n, L).copy(), qual.reshape(n, L).copy()
+    rng = np.random.default_rng(seed)
+    cols = np.arange(L)
+    adapter = np.frombuffer(TRUSEQ, dtype=np.uint8)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    for a in range(0, n, chunk):
+        b = min(n, a + chunk)
+        kind = np.arange(a, b) % 8
+        q = rng.integers(60, 74, (b - a, L), dtype=np.uint8)
+        bad = rng.integers(35, 51, (b - a, L), dtype=np.uint8)
+        at = rng.integers(0, L, b - a)
+        low = ((kind == 1)[:, None] & (cols[None, :] >= at[:, None])) | \
+              ((kind == 2)[:, None] & (cols[None, :] < (1 + at // 2)[:, None])) | (kind == 6)[:, None]
+        q[low] = bad[low]
+        dim = kind == 7
+        q[dim] = rng.integers(56, 60, (int(dim.sum()), L), dtype=np.uint8)
+        qual[a:b] = q
+        s = seq[a:b]
+        rows = np.flatnonzero((kind == 3) | (kind == 4) | (kind == 5))
+        p = np.where(kind[rows] == 5, rng.integers(0, L - len(adapter) + 1, rows.size), at[rows])
+        ad = np.broadcast_to(adapter, (rows.size, len(adapter))).copy()
+        subs = np.where(kind[rows] == 5, 4, (rows % 2))  # (four: one over the three a whole adapter may hold)
+        for j in range(4):
+            hit = np.flatnonzero(subs > j)
+            where = (rng.integers(0, 8, hit.size) + 8 * j) % len(adapter)
+            ad[hit, where] = acgt[(np.searchsorted(acgt, ad[hit, where]) + rng.integers(1, 4, hit.size)) % 4]
+        junk = acgt[rng.integers(0, 4, (rows.size, L))]
+        c = cols[None, :] - p[:, None]
+        tail = c >= 0
+        body = tail & (c < len(adapter))
+        s[rows[:, None], cols[None, :]] = np.where(body, ad[np.arange(rows.size)[:, None], np.clip(c, 0, len(adapter) - 1)],
+                                                   np.where(tail & (kind[rows] != 5)[:, None], junk, s[rows]))
+    return N.Reads.upload(seq.reshape(-1), qual.reshape(-1), off, device=reads.device)
 
 
 def make_pairs(genomes, n, read_len, err, seed, chunk=250_000):
@@ -229,7 +282,7 @@ def run_pairs(args, genomes, out):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=("detail", "coverage", "assign", "pileup", "abundance", "bootstrap", "pairs",
-                                       "lineage", "containment"),
+                                       "lineage", "containment", "trim"),
                     required=True)
     ap.add_argument("--replicates", type=int, default=100, help="bootstrap replicates of --mode bootstrap")
     ap.add_argument("--reads", type=int, default=None, help="reads (default 10 000 000); pairs with --mode pairs (1 000 000)")
@@ -403,6 +456,33 @@ def main():
                    reads_on_root=int(direct[0]), classified=int(clade[0]),
                    no_node=int((nodes == N.NO_NODE).sum()))
         lin.close()
+    elif args.mode == "trim":
+        batch = make_trim_batch(reads)
+        reads.close()
+        spec = N.TrimSpec.make(quality3=55, quality5=55, adapter=TRUSEQ)
+        holder = {}
+
+        def trim_call():
+            if "out" in holder:
+                holder.pop("out")[0].close()
+            holder["out"] = batch.trim(spec)  # (ends in a synchronise: start / end come back to the host)
+        med, ts = timed(trim_call, args.runs)
+        trimmed, _, _, stats = holder["out"]
+        out.update(trim_spec="quality3 = quality5 = 55, the 33-base TruSeq adapter, overlap 3, 100 permille",
+                   reads_trim_s=med, reads_trim_runs_s=ts, trim_reads_per_s=args.reads / med, trim_stats=stats,
+                   trim_bytes_moved=2 * 2 * stats["bases_out"], trim_input_bytes=2 * stats["bases_in"])
+        res = N.Result(index)
+        for name, b in (("untrimmed", batch), ("trimmed", trimmed)):
+            N.align(index, b, prm, 0, res)
+            cmed, cts = timed(lambda: (N.align(index, b, prm, 0, res), res.fetch()), args.runs)
+            amed, ats, entries = time_assign(index, b, prm, args.runs)
+            out.update({f"counter_pass_{name}_s": cmed, f"counter_pass_{name}_runs_s": cts,
+                        f"align_reads_{name}_s": amed, f"list_entries_{name}": entries})
+        out.update(ratio_trim_over_counter_pass_untrimmed=med / out["counter_pass_untrimmed_s"],
+                   ratio_trim_over_counter_pass_trimmed=med / out["counter_pass_trimmed_s"],
+                   ratio_trim_over_align_reads_trimmed=med / out["align_reads_trimmed_s"])
+        trimmed.close()
+        batch.close()
     elif args.mode == "containment":
         med, ts, entries = time_assign(index, reads, prm, args.runs)
         out.update(align_reads_s=med, align_reads_runs_s=ts, list_entries=entries)
